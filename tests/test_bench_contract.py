@@ -150,3 +150,43 @@ def test_every_traffic_file_is_at_least_its_compulsory_bytes():
         if tail is not None:  # the tail alone writes 12 B/px of RGB and reads >= 4 B/px of the last band level
             assert tail >= 0.95 * 16 * H * W, (f.name, tail)
     assert checked >= 2
+
+
+def test_dump_outputs_is_a_fixed_sample_within_budget(tmp_path):
+    """`--dump-outputs DIR`: float32 / float64 .npy files of what the last step returned, one seeded frame sample shared by every
+    per-frame array (the gathered observation included: world x B rows), the whole dump within the byte budget."""
+    from types import SimpleNamespace
+
+    import numpy as np
+    import torch
+
+    bench = _load_bench()
+    B, world = 64, 2
+    g = torch.Generator().manual_seed(3)
+
+    def sensor(k):
+        out = {"tactile_rgb": torch.rand((B, 24, 32, 3), generator=g), "height_map": torch.rand((B, 24, 32), generator=g),
+               "marker_motion": torch.rand((B, 2, 99, 2), generator=g), "tactile_rgb_obs": torch.randint(0, 256, (B, 8, 8, 3), dtype=torch.uint8, generator=g),
+               "init_marker_pos": ([0], [0])}
+        return SimpleNamespace(_data=SimpleNamespace(output=out), indentation_depth=torch.arange(B, dtype=torch.float32) + 1000 * k)
+
+    sensors = [sensor(0), sensor(1)]
+    # the gathered observation: rank r's rows follow rank r - 1's; row j of each rank block carries the env index j
+    obs_rows = torch.arange(world * B, dtype=torch.float64).remainder(B)[:, None].repeat(1, 4)
+    rig = SimpleNamespace(B=B, sensors=sensors, obs=SimpleNamespace(views=lambda: {"indent_0": obs_rows}))
+    budget = 200_000
+    shapes = bench.dump_outputs(rig, tmp_path / "a", budget=budget)
+    files = {p.stem: np.load(p) for p in (tmp_path / "a").glob("*.npy")}
+    assert set(files) == set(shapes) and sum(p.stat().st_size for p in (tmp_path / "a").glob("*.npy")) <= budget
+    assert all(a.dtype in (np.float32, np.float64) for a in files.values())
+    idx = files["frame_index"].astype(np.int64)
+    assert 1 <= len(idx) < B and np.all(np.diff(idx) > 0)
+    np.testing.assert_array_equal(files["tactile_rgb_1"], sensors[1]._data.output["tactile_rgb"].numpy()[idx])
+    np.testing.assert_array_equal(files["tactile_rgb_obs_0"], sensors[0]._data.output["tactile_rgb_obs"].numpy()[idx].astype(np.float32))
+    np.testing.assert_array_equal(files["indentation_depth_1"], idx + 1000.0)
+    assert files["obs_indent_0"].dtype == np.float64 and np.array_equal(files["obs_indent_0"][:, 0], np.concatenate([idx, idx]))
+    # the same arguments give the same sample; a budget that holds everything keeps every frame
+    bench.dump_outputs(rig, tmp_path / "b", budget=budget)
+    assert all(np.array_equal(np.load(tmp_path / "b" / f"{n}.npy"), a) for n, a in files.items())
+    bench.dump_outputs(rig, tmp_path / "c")
+    np.testing.assert_array_equal(np.load(tmp_path / "c" / "frame_index.npy"), np.arange(B))
