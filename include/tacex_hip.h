@@ -32,7 +32,7 @@ extern "C" {
 #endif
 
 #define TACEX_MAX_LEVELS 8
-#define TACEX_ABI_VERSION 15
+#define TACEX_ABI_VERSION 16
 
 typedef struct tacex_taxim_ctx tacex_taxim_ctx;
 typedef struct tacex_fots_ctx tacex_fots_ctx;
@@ -131,6 +131,22 @@ int tacex_depth_from_mesh(const float* verts_dev, const int32_t* tris_dev, int n
                           const float* pos_dev, const float* quat_dev, float fx, float fy, float cx, float cy,
                           float near_clip_m, float far_clip_m, const float* bounding_sphere, float* depth_m_dev, int num_envs, int height,
                           int width, void* stream);
+
+/* Height-map SOURCE for the FEM gel pad itself (ABI 16): the same depth image, rendered from the DEFORMED surface of the pad - per env
+ * vertices straight out of the FEM state, one camera pose per env (the route the reference leaves as a TODO in _get_height_map and
+ * otherwise covers by re-rendering the UIPC meshes after every step, uipc_sim.py:268-284).
+ *   x_dev (B, num_verts, 3) f64 world positions (UipcSim.x, read in place); surf_ids_dev (Vs,) int32 the rendered vertices, each
+ *   < num_verts; tris_dev (T,3) int32 indices into surf_ids_dev, each < Vs (neither is checked on the device);
+ *   cam_pos_dev (B,3) f64 and cam_rot_inv_dev (B,3,3) f64 row-major: camera-frame point p_c[i] = (Rinv[i][0] d0 + Rinv[i][1] d1)
+ *   + Rinv[i][2] d2 with d = x - cam_pos (VisionTactileSensorUIPC.transform_world_to_camera_frame), in f64, rounded once to f32;
+ *   intrinsics, clipping range and depth_m_dev (B,H,W) f32 out as in tacex_depth_from_mesh, whose rasterisation rules and float32
+ *   operations this follows exactly from the f32 camera-frame point on.  Surfaces of up to 2048 vertices are projected once per
+ *   workgroup into LDS; larger ones per triangle (same image).
+ * Returns 2 (no GPU call) on a null buffer, a count <= 0, Vs > num_verts or a clipping range that is not 0 <= near < far. */
+int tacex_depth_from_deformed_mesh(const double* x_dev, int num_verts, const int32_t* surf_ids_dev, int num_surf_verts,
+                                   const int32_t* tris_dev, int num_tris, const double* cam_pos_dev, const double* cam_rot_inv_dev,
+                                   float fx, float fy, float cx, float cy, float near_clip_m, float far_clip_m, float* depth_m_dev,
+                                   int num_envs, int height, int width, void* stream);
 
 /* TS:115-131 on an existing mm height map. frame_min_dev (B,) is also written (re-used by the render);
  * frame_rows_dev (B,4) int32 nullable: contact row / column ranges as in tacex_height_map_from_depth. */

@@ -120,6 +120,170 @@ __global__ __launch_bounds__(256) void mesh_depth_kernel(RasterArgs a) {
   }
 }
 
+
+// ---- Camera depth of the FEM gel pad itself: per-env DEFORMED vertices (UipcSim.x), one camera pose per env ----------------------------
+// The vertices come straight out of the FEM state x (B,V,3) float64 through surf_ids, go into the camera frame in float64 exactly as
+// VisionTactileSensorUIPC.transform_world_to_camera_frame does (p_c[i] = (Rinv[i][0] d0 + Rinv[i][1] d1) + Rinv[i][2] d2, d = x - cam_pos,
+// no FMA in this file) and are rounded ONCE to float32.  From that float32 camera-frame point on every operation is mesh_depth_kernel's,
+// in its order (projection, pixel centres, edge functions with zero inside, 1/z interpolation, IEEE division, [near, far] per fragment,
+// triangles with a vertex at pz <= 1e-6 dropped whole, no culling): oracle/mesh_depth_oracle.py with an identity pose reproduces the
+// image bit for bit from the camera-frame float32 vertices.
+//
+// Workgroup = (env, 64 x 32 tile), 256 threads.
+//  1. Staging: the env's Vs vertices are projected once per workgroup into LDS as (sx, sy, 1/z, front) - up to kDeformStageMax
+//     vertices (32 KB of dynamic LDS; above that nothing is staged and every triangle projects its three vertices itself with the same
+//     function, so the image is the same).  The same loop reduces the screen-space box of the FRONT vertices over the workgroup: a tile
+//     whose pixel centres that box does not reach holds no fragment (every rendered triangle has front vertices only and its pixels lie
+//     inside its own vertex box) and skips the rest.  The contact face covers most of the frame; the skip matters for envs whose pad
+//     is partly or wholly out of view.
+//  2. Triangle setup, 256 triangles per round: each thread sets up one, clips its pixel box to the tile and appends the survivors to
+//     a list in LDS (one wave-uniform broadcast read per list entry later on).
+//  3. Raster: every thread OWNS 8 pixels of the tile (one column, every 4th row) and walks the list, keeping its z-buffer in registers.
+//     No atomics: the nearest fragment is a minimum, which does not depend on the order the fragments arrive in, and each (triangle,
+//     pixel) pair is computed with exactly mesh_depth_kernel's expressions - so the image is the same as a per-triangle scatter with an
+//     atomicMin into LDS would give, without its load imbalance (the pad has ~160 large triangles: a handful per tile, one lane each).
+//     Depths are compared as bit patterns like that atomicMin (positive floats order like their bits).
+constexpr int kDeformStageMax = 2048;  // vertices staged in LDS (16 B each: 32 KB)
+constexpr int kDeformBlock = 256;
+constexpr int kDeformRows = kRasterTileH * kRasterTileW / kDeformBlock;  // pixels per thread (8)
+static_assert(kRasterTileW == 64 && kDeformBlock / 64 * kDeformRows == kRasterTileH, "a wave owns whole 64-pixel tile rows");
+
+struct DeformArgs {
+  const double* x;        // (B,V,3) world positions
+  const int* surf_ids;    // (Vs,) vertex ids into x
+  const int* tris;        // (T,3) indices into surf_ids
+  const double* cam_pos;  // (B,3)
+  const double* rot_inv;  // (B,3,3) world -> camera rotation (row-major)
+  float* depth;           // (B,H,W)
+  int V, Vs, T, B, H, W;
+  float fx, fy, cx, cy, near_m, far_m;
+  int tiles_x, tiles_y, staged;
+};
+
+struct TriSetup {  // one list entry (64 B): what the per-pixel test of mesh_depth_kernel reads
+  float sx[3], sy[3], iz[3], area, inv_area;
+  int jx0, jx1, iy0, iy1, pad;
+};
+
+// (sx, sy, 1/z, front) of surface vertex `sv` of the env - mesh_depth_kernel's projection of the float32 camera-frame point
+__device__ __forceinline__ float4 project_deformed(const DeformArgs& a, const double* xb, const double* cp, const double* R, int sv) {
+  const size_t vi = (size_t)a.surf_ids[sv] * 3;
+  const double d0 = xb[vi] - cp[0], d1 = xb[vi + 1] - cp[1], d2 = xb[vi + 2] - cp[2];
+  const float px = (float)((R[0] * d0 + R[1] * d1) + R[2] * d2);
+  const float py = (float)((R[3] * d0 + R[4] * d1) + R[5] * d2);
+  const float pz = (float)((R[6] * d0 + R[7] * d1) + R[8] * d2);
+  const float iz = 1.0f / pz;
+  return make_float4((a.fx * px) * iz + a.cx, (a.fy * py) * iz + a.cy, iz, pz > 1e-6f ? 1.0f : 0.0f);
+}
+
+__device__ __forceinline__ float wave_min(float v) {
+  for (int o = 32; o > 0; o >>= 1) v = fminf(v, __shfl_xor(v, o));
+  return v;
+}
+__device__ __forceinline__ float wave_max(float v) {
+  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
+  return v;
+}
+
+__global__ __launch_bounds__(kDeformBlock) void deformed_mesh_depth_kernel(DeformArgs a) {
+  extern __shared__ float4 stage[];  // (min(Vs, kDeformStageMax),) when a.staged
+  __shared__ TriSetup list[kDeformBlock];
+  __shared__ float box[4][kDeformBlock / 64];
+  __shared__ int count;
+  const int per_env = a.tiles_x * a.tiles_y;
+  const int env = blockIdx.x / per_env, tile = blockIdx.x - env * per_env;
+  const int ty = tile / a.tiles_x, tx = tile - ty * a.tiles_x;
+  const int x0 = tx * kRasterTileW, y0 = ty * kRasterTileH;
+  const int x1 = min(x0 + kRasterTileW, a.W), y1 = min(y0 + kRasterTileH, a.H);  // exclusive
+  const double* xb = a.x + (size_t)env * a.V * 3;
+  const double* cp = a.cam_pos + (size_t)env * 3;
+  const double* R = a.rot_inv + (size_t)env * 9;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+
+  float minx = INFINITY, maxx = -INFINITY, miny = INFINITY, maxy = -INFINITY;
+  for (int v = tid; v < a.Vs; v += kDeformBlock) {
+    const float4 p = project_deformed(a, xb, cp, R, v);
+    if (a.staged) stage[v] = p;
+    if (p.w != 0.0f) { minx = fminf(minx, p.x); maxx = fmaxf(maxx, p.x); miny = fminf(miny, p.y); maxy = fmaxf(maxy, p.y); }
+  }
+  minx = wave_min(minx); maxx = wave_max(maxx); miny = wave_min(miny); maxy = wave_max(maxy);
+  if (lane == 0) { box[0][wave] = minx; box[1][wave] = maxx; box[2][wave] = miny; box[3][wave] = maxy; }
+  if (tid == 0) count = 0;
+  __syncthreads();
+  for (int w = 0; w < kDeformBlock / 64; ++w) {
+    minx = fminf(minx, box[0][w]); maxx = fmaxf(maxx, box[1][w]); miny = fminf(miny, box[2][w]); maxy = fmaxf(maxy, box[3][w]);
+  }
+  // pixel centres j + 0.5 the box reaches: ceil(minx - 0.5) ... floor(maxx - 0.5), as for one triangle (no front vertex: empty box)
+  const bool tile_empty = !(floorf(maxx - 0.5f) >= (float)x0 && ceilf(minx - 0.5f) <= (float)(x1 - 1) &&
+                            floorf(maxy - 0.5f) >= (float)y0 && ceilf(miny - 0.5f) <= (float)(y1 - 1));
+
+  unsigned zb[kDeformRows];
+#pragma unroll
+  for (int k = 0; k < kDeformRows; ++k) zb[k] = 0x7f800000u;  // +inf
+  const int col = lane, row0 = wave;  // this thread's pixels: (y0 + row0 + 4k, x0 + col)
+  const float pxc = (float)(x0 + col) + 0.5f;
+  for (int base = tile_empty ? a.T : 0; base < a.T; base += kDeformBlock) {
+    const int t = base + tid;
+    if (t < a.T) {
+      float sx[3], sy[3], iz[3];
+      bool ok = true;
+#pragma unroll
+      for (int k = 0; k < 3; ++k) {
+        const int sv = a.tris[3 * t + k];
+        const float4 p = a.staged ? stage[sv] : project_deformed(a, xb, cp, R, sv);
+        sx[k] = p.x; sy[k] = p.y; iz[k] = p.z;
+        ok = ok && p.w != 0.0f;
+      }
+      if (ok) {
+        const float mnx = fminf(fminf(sx[0], sx[1]), sx[2]), mxx = fmaxf(fmaxf(sx[0], sx[1]), sx[2]);
+        const float mny = fminf(fminf(sy[0], sy[1]), sy[2]), mxy = fmaxf(fmaxf(sy[0], sy[1]), sy[2]);
+        const int jx0 = max(x0, (int)ceilf(mnx - 0.5f)), jx1 = min(x1 - 1, (int)floorf(mxx - 0.5f));
+        const int iy0 = max(y0, (int)ceilf(mny - 0.5f)), iy1 = min(y1 - 1, (int)floorf(mxy - 0.5f));
+        const float area = (sx[1] - sx[0]) * (sy[2] - sy[0]) - (sy[1] - sy[0]) * (sx[2] - sx[0]);
+        if (jx0 <= jx1 && iy0 <= iy1 && area != 0.0f) {
+          TriSetup& e = list[atomicAdd(&count, 1)];
+#pragma unroll
+          for (int k = 0; k < 3; ++k) { e.sx[k] = sx[k]; e.sy[k] = sy[k]; e.iz[k] = iz[k]; }
+          e.area = area; e.inv_area = 1.0f / area;
+          e.jx0 = jx0; e.jx1 = jx1; e.iy0 = iy0; e.iy1 = iy1;
+        }
+      }
+    }
+    __syncthreads();
+    const int n = count;
+    for (int l = 0; l < n; ++l) {
+      const TriSetup& e = list[l];
+      if (x0 + col < e.jx0 || x0 + col > e.jx1) continue;
+#pragma unroll
+      for (int k = 0; k < kDeformRows; ++k) {
+        const int i = y0 + row0 + 4 * k;
+        if (i < e.iy0 || i > e.iy1) continue;
+        const float py = (float)i + 0.5f, px = pxc;
+        const float e0 = (e.sx[2] - e.sx[1]) * (py - e.sy[1]) - (e.sy[2] - e.sy[1]) * (px - e.sx[1]);
+        const float e1 = (e.sx[0] - e.sx[2]) * (py - e.sy[2]) - (e.sy[0] - e.sy[2]) * (px - e.sx[2]);
+        const float e2 = (e.sx[1] - e.sx[0]) * (py - e.sy[0]) - (e.sy[1] - e.sy[0]) * (px - e.sx[0]);
+        const bool in = e.area > 0.0f ? (e0 >= 0.0f && e1 >= 0.0f && e2 >= 0.0f) : (e0 <= 0.0f && e1 <= 0.0f && e2 <= 0.0f);
+        if (!in) continue;
+        const float l0 = e0 * e.inv_area, l1 = e1 * e.inv_area, l2 = e2 * e.inv_area;
+        const float invz = (l0 * e.iz[0] + l1 * e.iz[1]) + l2 * e.iz[2];
+        const float z = 1.0f / invz;
+        if (!(z >= a.near_m && z <= a.far_m)) continue;  // clipping range (also drops NaN)
+        zb[k] = min(zb[k], __float_as_uint(z));
+      }
+    }
+    __syncthreads();
+    if (tid == 0) count = 0;
+    __syncthreads();
+  }
+  if (x0 + col < x1) {
+#pragma unroll
+    for (int k = 0; k < kDeformRows; ++k) {
+      const int i = y0 + row0 + 4 * k;
+      if (i < y1) a.depth[((size_t)env * a.H + i) * a.W + x0 + col] = __uint_as_float(zb[k]);
+    }
+  }
+}
+
 }  // namespace tacex
 
 extern "C" int tacex_depth_from_mesh(const float* verts_dev, const int32_t* tris_dev, int num_verts, int num_tris,
@@ -141,5 +305,36 @@ extern "C" int tacex_depth_from_mesh(const float* verts_dev, const int32_t* tris
   hipLaunchKernelGGL(mesh_depth_kernel, dim3((unsigned)(num_envs * a.tiles_x * a.tiles_y)), dim3(256), 0, (hipStream_t)stream, a);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) { set_error("mesh_depth_kernel: %s", hipGetErrorString(e)); return 1; }
+  return 0;
+}
+
+
+extern "C" int tacex_depth_from_deformed_mesh(const double* x_dev, int num_verts, const int32_t* surf_ids_dev, int num_surf_verts,
+                                              const int32_t* tris_dev, int num_tris, const double* cam_pos_dev, const double* cam_rot_inv_dev,
+                                              float fx, float fy, float cx, float cy, float near_clip_m, float far_clip_m, float* depth_m_dev,
+                                              int num_envs, int height, int width, void* stream) {
+  using namespace tacex;
+  if (!x_dev || !surf_ids_dev || !tris_dev || !cam_pos_dev || !cam_rot_inv_dev || !depth_m_dev) {
+    set_error("tacex_depth_from_deformed_mesh: null buffer"); return 2;
+  }
+  if (num_verts <= 0 || num_surf_verts <= 0 || num_surf_verts > num_verts || num_tris <= 0 || num_envs <= 0 || height <= 0 || width <= 0) {
+    set_error("tacex_depth_from_deformed_mesh: bad counts (verts %d, surface verts %d, tris %d, envs %d, image %dx%d)", num_verts,
+              num_surf_verts, num_tris, num_envs, width, height);
+    return 2;
+  }
+  if (!(near_clip_m >= 0.0f) || !(far_clip_m > near_clip_m)) {
+    set_error("tacex_depth_from_deformed_mesh: clipping range (%g, %g)", near_clip_m, far_clip_m); return 2;
+  }
+  DeformArgs a{};
+  a.x = x_dev; a.surf_ids = surf_ids_dev; a.tris = tris_dev; a.cam_pos = cam_pos_dev; a.rot_inv = cam_rot_inv_dev; a.depth = depth_m_dev;
+  a.V = num_verts; a.Vs = num_surf_verts; a.T = num_tris; a.B = num_envs; a.H = height; a.W = width;
+  a.fx = fx; a.fy = fy; a.cx = cx; a.cy = cy; a.near_m = near_clip_m; a.far_m = far_clip_m;
+  a.tiles_x = (width + kRasterTileW - 1) / kRasterTileW; a.tiles_y = (height + kRasterTileH - 1) / kRasterTileH;
+  a.staged = num_surf_verts <= kDeformStageMax;
+  const size_t lds = a.staged ? (size_t)num_surf_verts * sizeof(float4) : 0;
+  hipLaunchKernelGGL(deformed_mesh_depth_kernel, dim3((unsigned)(num_envs * a.tiles_x * a.tiles_y)), dim3(kDeformBlock), lds,
+                     (hipStream_t)stream, a);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) { set_error("deformed_mesh_depth_kernel: %s", hipGetErrorString(e)); return 1; }
   return 0;
 }

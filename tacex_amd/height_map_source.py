@@ -10,6 +10,7 @@ from __future__ import annotations
 
 import ctypes as C
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -87,3 +88,101 @@ class MeshDepthSource:
                 self.H, self.W, _lib.current_stream_handle(self.depth.device))
         _lib.check(rc, "tacex_depth_from_mesh")
         return self.depth
+
+
+def contact_face_triangles(points, tets, optical_axis_w, min_cos: float = 0.5) -> np.ndarray:
+    """(F,3) int32 boundary triangles of a tet mesh whose REST outward unit normal n has n . optical_axis_w > min_cos, wound along n.
+    The outward side of a boundary face is the side away from the fourth vertex of its tet - not the winding of
+    `UipcObject.surface_triangles()`, which looks inward on negatively oriented tets (the gelpad box's)."""
+    P = np.asarray(points, dtype=np.float64)
+    T = np.asarray(tets, dtype=np.int64)
+    faces = T[:, [[1, 2, 3], [0, 2, 3], [0, 1, 3], [0, 1, 2]]].reshape(-1, 3)
+    opposite = T.reshape(-1)  # face k of a tet leaves out its vertex k
+    _, inv, cnt = np.unique(np.sort(faces, axis=1), axis=0, return_inverse=True, return_counts=True)
+    boundary = cnt[inv.reshape(-1)] == 1
+    faces, opposite = faces[boundary], opposite[boundary]
+    a, b, c = (P[faces[:, k]] for k in range(3))
+    n = np.cross(b - a, c - a)
+    inward = np.einsum("ij,ij->i", n, P[opposite] - a) > 0.0
+    n[inward] *= -1.0
+    faces[inward] = faces[inward][:, [0, 2, 1]]
+    axis = np.asarray(optical_axis_w, dtype=np.float64)
+    cosang = (n @ axis) / (np.linalg.norm(n, axis=1) * np.linalg.norm(axis))
+    return np.ascontiguousarray(faces[cosang > min_cos], dtype=np.int32)
+
+
+class FemSurfaceDepthSource:
+    """Camera depth of the FEM gel pad's deformed contact face, per env, straight from the FEM state (`UipcSim.x`) in one HIP launch
+    (`tacex_depth_from_deformed_mesh`): the image the reference's sensor camera takes of the UIPC surface meshes after every step
+    (tacex_uipc uipc_sim.py:268-284, read by GelSightSensor._get_height_map).  `source()` -> (num_envs, H, W) float32 depth in metres,
+    inf where nothing is seen: a drop-in `cfg.sensor_camera_cfg.depth_source`; `fill(...)` is the `set_height_map_source` interface
+    (same render + `tacex_height_map_from_depth`, bit-equal results).  Sensors of a `GelSightSensorGroup` take their depth slices from
+    the group, not from a source.
+
+    Camera: `camera_pos_w` (3,) or (num_envs, 3) and `camera_quat_w_ros` (wxyz, (4,) or (num_envs, 4)) in the convention of
+    `ManiSkillSimulatorCfg.camera_pos_w` / `camera_quat_w_ros` (x right, y down, z along the optical axis).  `pos` (num_envs, 3) and
+    `rot_inv` (num_envs, 3, 3) float64 are device tensors the caller may update in place (a camera that follows the sensor case).
+    Rendered faces: by default the boundary triangles whose rest outward normal looks away from the camera (`n . axis > 0.5`) - the
+    contact face; the back face, which sits at the near plane, and the side walls are left out.  `triangles` (F,3) vertex ids of the
+    object's mesh overrides that choice."""
+
+    def __init__(self, uipc_object, camera_pos_w, camera_quat_w_ros, resolution=(320, 240), intrinsics=(340.0, 325.0, 160.0, 125.0),
+                 clipping_range=(0.024, 0.029), triangles=None):
+        from .simulation_approaches.fem_based.sim.tactile_sensor_uipc import quat_to_matrix
+
+        sim = getattr(uipc_object, "_uipc_sim", None)
+        if sim is None or getattr(sim, "x", None) is None:
+            raise RuntimeError("FemSurfaceDepthSource needs a UipcObject attached to a UipcSim that was set up (setup_sim)")
+        if getattr(uipc_object, "is_affine_body", False):
+            raise ValueError("FemSurfaceDepthSource renders the deformable object (the gel pad), not an affine body")
+        self._sim, dev, B = sim, sim.device, sim.num_envs
+        q = torch.as_tensor(camera_quat_w_ros, dtype=torch.float64).reshape(-1, 4)
+        q = q / q.norm(dim=1, keepdim=True)
+        rot = quat_to_matrix(q)  # camera -> world
+        self.pos = torch.as_tensor(camera_pos_w, dtype=torch.float64).reshape(-1, 3).expand(B, 3).contiguous().to(dev)
+        self.rot_inv = rot.transpose(-1, -2).expand(B, 3, 3).contiguous().to(dev)
+        if triangles is None:
+            tri = contact_face_triangles(uipc_object.points, uipc_object.tets, rot[0, :, 2].numpy())
+        else:
+            tri = np.asarray(triangles, dtype=np.int64).reshape(-1, 3)
+            if len(tri) and (tri.min() < 0 or tri.max() >= uipc_object.num_verts):
+                raise ValueError(f"FemSurfaceDepthSource: triangle indices outside [0, {uipc_object.num_verts})")
+        if len(tri) == 0:
+            raise ValueError("FemSurfaceDepthSource: no triangles to render")
+        ids, local = np.unique(tri.reshape(-1), return_inverse=True)
+        self.triangles = np.ascontiguousarray(tri, dtype=np.int32)  # (F,3) object vertex ids
+        self.surf_ids = torch.from_numpy(ids.astype(np.int32)).to(dev)
+        self.tris = torch.from_numpy(local.reshape(-1, 3).astype(np.int32)).to(dev)
+        self.W, self.H = int(resolution[0]), int(resolution[1])
+        self.fx, self.fy, self.cx, self.cy = (float(v) for v in intrinsics)
+        self.near, self.far = float(clipping_range[0]), float(clipping_range[1])
+        if not (0.0 <= self.near < self.far):
+            raise ValueError(f"FemSurfaceDepthSource: clipping range {clipping_range}")
+        self.depth = torch.empty((B, self.H, self.W), dtype=torch.float32, device=dev)
+        self._lib = _lib.load_library()
+
+    def __call__(self) -> torch.Tensor:
+        sim = self._sim
+        sim.wait_for_step()  # a step enqueued on a side stream (UipcSim.step_done) is ordered before the render
+        x = sim.x
+        with torch.cuda.device(self.depth.device):
+            rc = self._lib.tacex_depth_from_deformed_mesh(
+                _lib.ptr(x), int(x.shape[1]), _lib.ptr(self.surf_ids), int(self.surf_ids.shape[0]), _lib.ptr(self.tris),
+                int(self.tris.shape[0]), _lib.ptr(self.pos), _lib.ptr(self.rot_inv), self.fx, self.fy, self.cx, self.cy, self.near,
+                self.far, _lib.ptr(self.depth), int(self.depth.shape[0]), self.H, self.W, _lib.current_stream_handle(self.depth.device))
+        _lib.check(rc, "tacex_depth_from_deformed_mesh")
+        return self.depth
+
+    def fill(self, hm: torch.Tensor, frame_min: torch.Tensor, indent: torch.Tensor | None, gelpad_height: float,
+             gelpad_to_camera_min_distance: float):
+        """hm (B, H, W) mm, frame_min (B,), indent (B,) or None: the render above, then the depth -> height-map pass
+        (`tacex_height_map_from_depth` with this source's clipping range), both on the current stream."""
+        if tuple(hm.shape) != tuple(self.depth.shape):
+            raise RuntimeError(f"height map has shape {tuple(hm.shape)}, the source renders {tuple(self.depth.shape)}")
+        depth = self()
+        B, H, W = hm.shape
+        with torch.cuda.device(hm.device):
+            rc = self._lib.tacex_height_map_from_depth(
+                _lib.ptr(depth), self.near, self.far, float(gelpad_height), float(gelpad_to_camera_min_distance), _lib.ptr(hm),
+                _lib.ptr(frame_min), _lib.ptr(indent), 0, 0, B, H, W, _lib.current_stream_handle(hm.device))
+        _lib.check(rc, "tacex_height_map_from_depth")
