@@ -32,7 +32,7 @@ extern "C" {
 #endif
 
 #define TACEX_MAX_LEVELS 8
-#define TACEX_ABI_VERSION 16
+#define TACEX_ABI_VERSION 17
 
 typedef struct tacex_taxim_ctx tacex_taxim_ctx;
 typedef struct tacex_fots_ctx tacex_fots_ctx;
@@ -147,6 +147,22 @@ int tacex_depth_from_deformed_mesh(const double* x_dev, int num_verts, const int
                                    const int32_t* tris_dev, int num_tris, const double* cam_pos_dev, const double* cam_rot_inv_dev,
                                    float fx, float fy, float cx, float cy, float near_clip_m, float far_clip_m, float* depth_m_dev,
                                    int num_envs, int height, int width, void* stream);
+
+/* Height-map SOURCE from a mesh LIBRARY (ABI 17): the image of tacex_depth_from_mesh, with every env rendering its OWN mesh.
+ *   verts_dev (V,3) f32 every mesh's object-frame vertices back to back; tris_dev (T,3) int32 every mesh's triangles back to back,
+ *   indexing verts_dev (the concatenated table); mesh_tris_dev (num_meshes,2) int32: first triangle and triangle count of every mesh;
+ *   mesh_spheres_dev (num_meshes,4) f32 device, nullable: bounding sphere {cx, cy, cz, r} of every mesh (r < 0: unknown) for the tile
+ *   skip; max_mesh_tris (host) >= every mesh's triangle count (sizes the launch); mesh_ids_dev (B,) int32 the mesh of every env,
+ *   nullable = mesh 0, read on the device - an id outside [0, num_meshes) renders nothing (+inf); pos / quat / intrinsics / clipping /
+ *   depth_m_dev (B,H,W) as in tacex_depth_from_mesh.  Tables are not checked on the device.  Each env's image is bit-equal to
+ *   tacex_depth_from_mesh on its mesh alone (same float32 operations).  Meshes of more than 1024 triangles are rendered by several
+ *   workgroups per image tile (a second launch on the stream, merged with an atomic minimum).
+ * Returns 2 (no GPU call) on a null buffer, num_meshes or max_mesh_tris <= 0, an empty image or a bad clipping range. */
+int tacex_depth_from_mesh_library(const float* verts_dev, const int32_t* tris_dev, const int32_t* mesh_tris_dev,
+                                  const float* mesh_spheres_dev, int num_meshes, int max_mesh_tris, const int32_t* mesh_ids_dev,
+                                  const float* pos_dev, const float* quat_dev, float fx, float fy, float cx, float cy,
+                                  float near_clip_m, float far_clip_m, float* depth_m_dev, int num_envs, int height, int width,
+                                  void* stream);
 
 /* TS:115-131 on an existing mm height map. frame_min_dev (B,) is also written (re-used by the render);
  * frame_rows_dev (B,4) int32 nullable: contact row / column ranges as in tacex_height_map_from_depth. */
@@ -455,6 +471,21 @@ int tacex_fem_contact_gaps(tacex_fem_ctx* ctx, const double* x_dev, double* gaps
  * the distance is unsigned.  num_tris = 0 removes the mesh.  Tables are copied. */
 int tacex_fem_set_indenter_mesh(tacex_fem_ctx* ctx, int num_verts, const double* verts_host, int num_tris, const int32_t* tris_host);
 
+/* Indenter mesh LIBRARY (ABI 17): one rigid mesh PER ENV for indenter kind 4, chosen by a device id array
+ * (tacex_fem_set_indenter_mesh_ids).  Mesh k has vert_counts[k] vertices and tri_counts[k] triangles; verts_host holds every mesh's
+ * (vert_counts[k],3) f64 vertices back to back, tris_host every mesh's (tri_counts[k],3) int32 triangles back to back, each indexing
+ * its own mesh's vertices.  Each mesh is ordered and clustered exactly as tacex_fem_set_indenter_mesh does it, so an env sees the same
+ * distances as with that mesh alone; tacex_fem_set_indenter_mesh is a library of one with no id array.  num_meshes = 0 removes the
+ * library.  Tables are copied; the id array set before stays in place. */
+int tacex_fem_set_indenter_mesh_library(tacex_fem_ctx* ctx, int num_meshes, const int32_t* vert_counts, const double* verts_host,
+                                        const int32_t* tri_counts, const int32_t* tris_host);
+
+/* ids_dev (B,) int32 device: the library mesh of every env, read by every later call with B envs (the caller may rewrite it between
+ * steps, e.g. to draw new shapes at a reset; it must stay allocated while set).  NULL: every env uses mesh 0.  An id outside
+ * [0, num_meshes) is never dereferenced: that env's kind-4 row acts as no indenter and tacex_fem_step sets flag 32 in its
+ * step_info[., 2]. */
+int tacex_fem_set_indenter_mesh_ids(tacex_fem_ctx* ctx, const int32_t* ids_dev);
+
 /* Block part of the preconditioner: block-tridiagonal LDL^T along VERTEX CHAINS instead of one 3x3 block per vertex.  A chain is a
  * sequence of mesh vertices, consecutive ones sharing a tet (the columns of vertices through a gelpad's thickness: the nearly
  * incompressible material couples the layers of a thin pad most strongly; UipcSim builds them with
@@ -490,14 +521,16 @@ int tacex_fem_newton_step(tacex_fem_ctx* ctx, double* x_dev, const double* x_til
  * vertex: 512 threads per env for meshes of <= 512 vertices, 768 threads for larger ones as long as the env's state fits the CU's
  * 160 KB of LDS - about 600 vertices with friction, 745 without; simple_axle.msh, 593 vertices / 2 003 tets, does with friction; the
  * wide variant takes analytic indenters only and is not available with tacex_fem_set_deterministic) the whole loop is ONE launch; the streaming fallback
- * (any vertex count; analytic indenters with barrier, step bound and - ABI 11 - friction lagged at the step's start; block-Jacobi PCG) launches
+ * (any vertex count; analytic indenters - and since ABI 17 mesh indenters - with barrier, step bound and - ABI 11 - friction lagged at the
+ * step's start; block-Jacobi PCG) launches
  * max_newton kernels on a fixed schedule in which converged envs return at once.  stats_dev (B,4) = [energy_before, energy_after, step_length, pcg_iterations] of the LAST iteration
  * run; step_info_dev (B,4) f64 = [newton_iterations, max |d| of the last iteration, flags, pcg_iterations_total] (both kernels: the fallback
  * sums / ORs over its launches), flags: 1 = a contact vertex was at or beyond its indenter's surface when an iteration started
  * (the caller moved the indenter by more than the gap: that vertex gets no restoring force), 2 = a line search found no decrease;
  * informational: 4 = the env dropped the coarse correction for the rest of the step (its stopping test passed with the residual's
  * 2-norm above |b|: no reduction at all), 8 = its PCG met negative curvature and iterations of the step were solved with the PSD-safe Hessian
- * (|c_J| of the Stable Neo-Hookean d2J/dF2 term clamped per element; the gradient is exact, the minimiser the same).
+ * (|c_J| of the Stable Neo-Hookean d2J/dF2 term clamped per element; the gradient is exact, the minimiser the same); 32 (ABI 17) = the
+ * env's kind-4 row named a mesh id outside the indenter mesh library (tacex_fem_set_indenter_mesh_ids): it had no indenter.
  * workspace_dev: tacex_fem_workspace_bytes(ctx, num_envs). */
 int tacex_fem_step(tacex_fem_ctx* ctx, double* x_dev, double* v_dev, double* x_tilde_dev, const uint8_t* constrained_dev,
                    const double* aim_dev, double* stats_dev, double* step_info_dev, void* workspace_dev, int num_envs,

@@ -11,7 +11,7 @@ from pathlib import Path
 from ._build import LIB, build_library
 
 MAX_LEVELS = 8
-ABI_VERSION = 16  # TACEX_ABI_VERSION of include/tacex_hip.h; bumped whenever a signature or struct layout changes
+ABI_VERSION = 17  # TACEX_ABI_VERSION of include/tacex_hip.h; bumped whenever a signature or struct layout changes
 FLAG_NO_SHIFT = 1
 FLAG_HAVE_FRAME_MIN = 2
 FLAG_WITH_SHADOW = 4
@@ -105,6 +105,7 @@ SIGNATURES = {
     "tacex_taxim_set_frame_rows": (_i, [_vp, _vp, _i]),
     "tacex_depth_from_mesh": (_i, [_vp, _vp, _i, _i, _vp, _vp, _f, _f, _f, _f, _f, _f, _vp, _vp, _i, _i, _i, _vp]),
     "tacex_depth_from_deformed_mesh": (_i, [_vp, _i, _vp, _i, _vp, _i, _vp, _vp, _f, _f, _f, _f, _f, _f, _vp, _i, _i, _i, _vp]),
+    "tacex_depth_from_mesh_library": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _f, _f, _f, _f, _f, _f, _vp, _i, _i, _i, _vp]),
     "tacex_taxim_render": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _u, _vp]),
     "tacex_taxim_render_obs": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _u, _vp]),
     "tacex_taxim_deform": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _u, _vp]),
@@ -140,6 +141,8 @@ SIGNATURES = {
     "tacex_fem_set_coarse_space": (_i, [_vp, _i, _vp, _vp, _vp]),
     "tacex_fem_set_chains": (_i, [_vp, _i, _vp, _vp]),
     "tacex_fem_set_indenter_mesh": (_i, [_vp, _i, _vp, _i, _vp]),
+    "tacex_fem_set_indenter_mesh_library": (_i, [_vp, _i, _vp, _vp, _vp, _vp]),
+    "tacex_fem_set_indenter_mesh_ids": (_i, [_vp, _vp]),
     "tacex_fem_contact_gaps": (_i, [_vp, _vp, _vp, _i, _vp]),
     "tacex_fem_newton_resident": (_i, [_vp]),
     "tacex_fem_set_friction_lag": (_i, [_vp, _i]),

@@ -13,6 +13,8 @@
 #include <math.h>
 #include <stdint.h>
 
+#include <algorithm>
+
 #include "tacex_hip.h"
 #include "tacex_internal.h"
 
@@ -32,32 +34,33 @@ struct RasterArgs {
   float bs[4];          // bounding sphere of the mesh in the object frame (centre, radius); radius < 0: unknown
 };
 
-__global__ __launch_bounds__(256) void mesh_depth_kernel(RasterArgs a) {
-  __shared__ unsigned zbuf[kRasterTileW * kRasterTileH];
-  const int per_env = a.tiles_x * a.tiles_y;
-  const int env = blockIdx.x / per_env, tile = blockIdx.x - env * per_env;
-  const int ty = tile / a.tiles_x, tx = tile - ty * a.tiles_x;
-  const int x0 = tx * kRasterTileW, y0 = ty * kRasterTileH;
-  const int x1 = min(x0 + kRasterTileW, a.W), y1 = min(y0 + kRasterTileH, a.H);  // exclusive
-  for (int i = threadIdx.x; i < kRasterTileW * kRasterTileH; i += blockDim.x) zbuf[i] = 0x7f800000u;  // +inf
-  __syncthreads();
-  // rotation matrix of the env's quaternion: double arithmetic, rounded once to float32 (what the NumPy restatement does)
+// rotation and translation of env `env` into the camera frame: the quaternion normalised in double, the matrix rounded once to float32
+// (what the NumPy restatement does)
+struct RasterPose {
+  float r00, r01, r02, r10, r11, r12, r20, r21, r22, t0, t1, t2;
+};
+__device__ __forceinline__ RasterPose raster_pose(const RasterArgs& a, int env) {
   double qw = a.quat[4 * env], qx = a.quat[4 * env + 1], qy = a.quat[4 * env + 2], qz = a.quat[4 * env + 3];
   const double qn = sqrt(((qw * qw + qx * qx) + qy * qy) + qz * qz);
   qw /= qn; qx /= qn; qy /= qn; qz /= qn;
-  const float r00 = (float)(1.0 - 2.0 * (qy * qy + qz * qz)), r01 = (float)(2.0 * (qx * qy - qz * qw)), r02 = (float)(2.0 * (qx * qz + qy * qw));
-  const float r10 = (float)(2.0 * (qx * qy + qz * qw)), r11 = (float)(1.0 - 2.0 * (qx * qx + qz * qz)), r12 = (float)(2.0 * (qy * qz - qx * qw));
-  const float r20 = (float)(2.0 * (qx * qz - qy * qw)), r21 = (float)(2.0 * (qy * qz + qx * qw)), r22 = (float)(1.0 - 2.0 * (qx * qx + qy * qy));
-  const float t0 = a.pos[3 * env], t1 = a.pos[3 * env + 1], t2 = a.pos[3 * env + 2];
-  // Tiles the mesh cannot touch skip the triangle loop (a contact covers a few percent of the image): conservative screen
-  // bounds of the mesh's bounding sphere - x, y in [c -+ r] over z in [c.z - r, c.z + r] - against the tile.  Exactness is not
-  // at stake: a skipped tile holds no fragment.
+  RasterPose P;
+  P.r00 = (float)(1.0 - 2.0 * (qy * qy + qz * qz)); P.r01 = (float)(2.0 * (qx * qy - qz * qw)); P.r02 = (float)(2.0 * (qx * qz + qy * qw));
+  P.r10 = (float)(2.0 * (qx * qy + qz * qw)); P.r11 = (float)(1.0 - 2.0 * (qx * qx + qz * qz)); P.r12 = (float)(2.0 * (qy * qz - qx * qw));
+  P.r20 = (float)(2.0 * (qx * qz - qy * qw)); P.r21 = (float)(2.0 * (qy * qz + qx * qw)); P.r22 = (float)(1.0 - 2.0 * (qx * qx + qy * qy));
+  P.t0 = a.pos[3 * env]; P.t1 = a.pos[3 * env + 1]; P.t2 = a.pos[3 * env + 2];
+  return P;
+}
+
+// Tiles the mesh cannot touch skip the triangle loop (a contact covers a few percent of the image): conservative screen
+// bounds of the mesh's bounding sphere bs (centre, radius; radius < 0: unknown) - x, y in [c -+ r] over z in [c.z - r, c.z + r] -
+// against the tile [x0, x1) x [y0, y1).  Exactness is not at stake: a skipped tile holds no fragment.
+__device__ __forceinline__ bool raster_tile_empty(const RasterArgs& a, const RasterPose& P, const float bs[4], int x0, int x1, int y0, int y1) {
   bool tile_empty = false;
-  if (a.bs[3] >= 0.0f) {
-    const float r = a.bs[3];
-    const float bx = ((r00 * a.bs[0] + r01 * a.bs[1]) + r02 * a.bs[2]) + t0;
-    const float by = ((r10 * a.bs[0] + r11 * a.bs[1]) + r12 * a.bs[2]) + t1;
-    const float bz = ((r20 * a.bs[0] + r21 * a.bs[1]) + r22 * a.bs[2]) + t2;
+  if (bs[3] >= 0.0f) {
+    const float r = bs[3];
+    const float bx = ((P.r00 * bs[0] + P.r01 * bs[1]) + P.r02 * bs[2]) + P.t0;
+    const float by = ((P.r10 * bs[0] + P.r11 * bs[1]) + P.r12 * bs[2]) + P.t1;
+    const float bz = ((P.r20 * bs[0] + P.r21 * bs[1]) + P.r22 * bs[2]) + P.t2;
     const float zn = bz - r, zf = bz + r;
     if (zf < a.near_m || zn > a.far_m) {
       tile_empty = true;
@@ -70,53 +73,129 @@ __global__ __launch_bounds__(256) void mesh_depth_kernel(RasterArgs a) {
       tile_empty = uhi < (float)x0 || ulo > (float)x1 || vhi < (float)y0 || vlo > (float)y1;
     }
   }
-  for (int t = tile_empty ? a.T : threadIdx.x; t < a.T; t += blockDim.x) {
-    float sx[3], sy[3], iz[3];
-    bool ok = true;
+  return tile_empty;
+}
+
+// triangle t of a.tris (indices into a.verts) into the tile's z-buffer (LDS, atomicMin of the depth's bit pattern)
+__device__ __forceinline__ void raster_triangle(const RasterArgs& a, const RasterPose& P, int t, int x0, int x1, int y0, int y1, unsigned* zbuf) {
+  float sx[3], sy[3], iz[3];
+  bool ok = true;
 #pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      const int vi = a.tris[3 * t + k];
-      const float vx = a.verts[3 * vi], vy = a.verts[3 * vi + 1], vz = a.verts[3 * vi + 2];
-      const float px = ((r00 * vx + r01 * vy) + r02 * vz) + t0;
-      const float py = ((r10 * vx + r11 * vy) + r12 * vz) + t1;
-      const float pz = ((r20 * vx + r21 * vy) + r22 * vz) + t2;
-      ok = ok && pz > 1e-6f;
-      iz[k] = 1.0f / pz;
-      sx[k] = (a.fx * px) * iz[k] + a.cx;
-      sy[k] = (a.fy * py) * iz[k] + a.cy;
-    }
-    if (!ok) continue;
-    const float minx = fminf(fminf(sx[0], sx[1]), sx[2]), maxx = fmaxf(fmaxf(sx[0], sx[1]), sx[2]);
-    const float miny = fminf(fminf(sy[0], sy[1]), sy[2]), maxy = fmaxf(fmaxf(sy[0], sy[1]), sy[2]);
-    // pixel centres j + 0.5 inside [minx, maxx]: j from ceil(minx - 0.5) to floor(maxx - 0.5)
-    const int jx0 = max(x0, (int)ceilf(minx - 0.5f)), jx1 = min(x1 - 1, (int)floorf(maxx - 0.5f));
-    const int iy0 = max(y0, (int)ceilf(miny - 0.5f)), iy1 = min(y1 - 1, (int)floorf(maxy - 0.5f));
-    if (jx0 > jx1 || iy0 > iy1) continue;
-    const float area = (sx[1] - sx[0]) * (sy[2] - sy[0]) - (sy[1] - sy[0]) * (sx[2] - sx[0]);
-    if (area == 0.0f) continue;
-    const float inv_area = 1.0f / area;
-    for (int i = iy0; i <= iy1; ++i) {
-      const float py = (float)i + 0.5f;
-      for (int j = jx0; j <= jx1; ++j) {
-        const float px = (float)j + 0.5f;
-        // edge functions (twice the signed sub-triangle areas); inside when all share the sign of `area` (zero counts as inside)
-        const float e0 = (sx[2] - sx[1]) * (py - sy[1]) - (sy[2] - sy[1]) * (px - sx[1]);
-        const float e1 = (sx[0] - sx[2]) * (py - sy[2]) - (sy[0] - sy[2]) * (px - sx[2]);
-        const float e2 = (sx[1] - sx[0]) * (py - sy[0]) - (sy[1] - sy[0]) * (px - sx[0]);
-        const bool in = area > 0.0f ? (e0 >= 0.0f && e1 >= 0.0f && e2 >= 0.0f) : (e0 <= 0.0f && e1 <= 0.0f && e2 <= 0.0f);
-        if (!in) continue;
-        const float l0 = e0 * inv_area, l1 = e1 * inv_area, l2 = e2 * inv_area;
-        const float invz = (l0 * iz[0] + l1 * iz[1]) + l2 * iz[2];
-        const float z = 1.0f / invz;
-        if (!(z >= a.near_m && z <= a.far_m)) continue;  // clipping range of the camera (also drops NaN)
-        atomicMin(&zbuf[(i - y0) * kRasterTileW + (j - x0)], __float_as_uint(z));
-      }
+  for (int k = 0; k < 3; ++k) {
+    const int vi = a.tris[3 * t + k];
+    const float vx = a.verts[3 * vi], vy = a.verts[3 * vi + 1], vz = a.verts[3 * vi + 2];
+    const float px = ((P.r00 * vx + P.r01 * vy) + P.r02 * vz) + P.t0;
+    const float py = ((P.r10 * vx + P.r11 * vy) + P.r12 * vz) + P.t1;
+    const float pz = ((P.r20 * vx + P.r21 * vy) + P.r22 * vz) + P.t2;
+    ok = ok && pz > 1e-6f;
+    iz[k] = 1.0f / pz;
+    sx[k] = (a.fx * px) * iz[k] + a.cx;
+    sy[k] = (a.fy * py) * iz[k] + a.cy;
+  }
+  if (!ok) return;
+  const float minx = fminf(fminf(sx[0], sx[1]), sx[2]), maxx = fmaxf(fmaxf(sx[0], sx[1]), sx[2]);
+  const float miny = fminf(fminf(sy[0], sy[1]), sy[2]), maxy = fmaxf(fmaxf(sy[0], sy[1]), sy[2]);
+  // pixel centres j + 0.5 inside [minx, maxx]: j from ceil(minx - 0.5) to floor(maxx - 0.5)
+  const int jx0 = max(x0, (int)ceilf(minx - 0.5f)), jx1 = min(x1 - 1, (int)floorf(maxx - 0.5f));
+  const int iy0 = max(y0, (int)ceilf(miny - 0.5f)), iy1 = min(y1 - 1, (int)floorf(maxy - 0.5f));
+  if (jx0 > jx1 || iy0 > iy1) return;
+  const float area = (sx[1] - sx[0]) * (sy[2] - sy[0]) - (sy[1] - sy[0]) * (sx[2] - sx[0]);
+  if (area == 0.0f) return;
+  const float inv_area = 1.0f / area;
+  for (int i = iy0; i <= iy1; ++i) {
+    const float py = (float)i + 0.5f;
+    for (int j = jx0; j <= jx1; ++j) {
+      const float px = (float)j + 0.5f;
+      // edge functions (twice the signed sub-triangle areas); inside when all share the sign of `area` (zero counts as inside)
+      const float e0 = (sx[2] - sx[1]) * (py - sy[1]) - (sy[2] - sy[1]) * (px - sx[1]);
+      const float e1 = (sx[0] - sx[2]) * (py - sy[2]) - (sy[0] - sy[2]) * (px - sx[2]);
+      const float e2 = (sx[1] - sx[0]) * (py - sy[0]) - (sy[1] - sy[0]) * (px - sx[0]);
+      const bool in = area > 0.0f ? (e0 >= 0.0f && e1 >= 0.0f && e2 >= 0.0f) : (e0 <= 0.0f && e1 <= 0.0f && e2 <= 0.0f);
+      if (!in) continue;
+      const float l0 = e0 * inv_area, l1 = e1 * inv_area, l2 = e2 * inv_area;
+      const float invz = (l0 * iz[0] + l1 * iz[1]) + l2 * iz[2];
+      const float z = 1.0f / invz;
+      if (!(z >= a.near_m && z <= a.far_m)) continue;  // clipping range of the camera (also drops NaN)
+      atomicMin(&zbuf[(i - y0) * kRasterTileW + (j - x0)], __float_as_uint(z));
     }
   }
+}
+
+__global__ __launch_bounds__(256) void mesh_depth_kernel(RasterArgs a) {
+  __shared__ unsigned zbuf[kRasterTileW * kRasterTileH];
+  const int per_env = a.tiles_x * a.tiles_y;
+  const int env = blockIdx.x / per_env, tile = blockIdx.x - env * per_env;
+  const int ty = tile / a.tiles_x, tx = tile - ty * a.tiles_x;
+  const int x0 = tx * kRasterTileW, y0 = ty * kRasterTileH;
+  const int x1 = min(x0 + kRasterTileW, a.W), y1 = min(y0 + kRasterTileH, a.H);  // exclusive
+  for (int i = threadIdx.x; i < kRasterTileW * kRasterTileH; i += blockDim.x) zbuf[i] = 0x7f800000u;  // +inf
+  __syncthreads();
+  const RasterPose P = raster_pose(a, env);
+  const bool tile_empty = raster_tile_empty(a, P, a.bs, x0, x1, y0, y1);
+  for (int t = tile_empty ? a.T : threadIdx.x; t < a.T; t += blockDim.x) raster_triangle(a, P, t, x0, x1, y0, y1, zbuf);
   __syncthreads();
   for (int i = threadIdx.x; i < kRasterTileW * kRasterTileH; i += blockDim.x) {
     const int yy = y0 + i / kRasterTileW, xx = x0 + i % kRasterTileW;
     if (yy < y1 && xx < x1) a.depth[((size_t)env * a.H + yy) * a.W + xx] = __uint_as_float(zbuf[i]);
+  }
+}
+
+// ---- The same image from a mesh LIBRARY: every env renders its own mesh (tacex_depth_from_mesh_library) -------------------------------
+// The library is the concatenation of the meshes' vertex and triangle tables (triangles index the concatenated vertices); env b renders
+// triangles [first, first + count) of mesh ids[b] with raster_pose / raster_tile_empty / raster_triangle - mesh_depth_kernel's
+// operations, so every env's image is bit-equal to tacex_depth_from_mesh on its mesh alone (the nearest fragment is a minimum: the
+// order and grouping of the triangles do not matter).
+// Load balance: envs differ in triangle count, and one workgroup walking a long mesh would hold its CU while short meshes' workgroups
+// are long done.  So a workgroup takes at most kLibChunk triangles of its env's mesh (4 per thread): the (env, tile) pairs are split
+// into chunks and a workgroup's length is bounded whatever the mix.  Chunk 0 of every (env, tile) stores the whole tile (like
+// mesh_depth_kernel: +inf where nothing was drawn); a second launch, ordered behind it on the stream, runs the further chunks of the
+// longer meshes and merges them with a global atomicMin on the depth bits of the pixels they drew.  A library whose meshes all fit
+// one chunk takes the first launch only.
+constexpr int kLibChunk = 1024;
+
+struct RasterLibArgs {
+  RasterArgs r;          // verts / tris: the library; bs unused
+  const int* mesh_tris;  // (K,2) first triangle | triangles
+  const float* mesh_bs;  // (K,4) bounding sphere of every mesh (object frame; radius < 0: unknown); nullable
+  const int* ids;        // (B) mesh of every env; nullable: mesh 0
+  int K;
+  int chunk0;            // first chunk of this launch (0 or 1)
+  int nchunk;            // chunks per (env, tile) in this launch
+};
+
+template <bool MERGE>
+__global__ __launch_bounds__(256) void mesh_library_depth_kernel(RasterLibArgs L) {
+  __shared__ unsigned zbuf[kRasterTileW * kRasterTileH];
+  const RasterArgs& a = L.r;
+  const int per_env = a.tiles_x * a.tiles_y;
+  const int chunk = L.chunk0 + (int)(blockIdx.x % (unsigned)L.nchunk);
+  const int et = (int)(blockIdx.x / (unsigned)L.nchunk);
+  const int env = et / per_env, tile = et - env * per_env;
+  const int ty = tile / a.tiles_x, tx = tile - ty * a.tiles_x;
+  const int x0 = tx * kRasterTileW, y0 = ty * kRasterTileH;
+  const int x1 = min(x0 + kRasterTileW, a.W), y1 = min(y0 + kRasterTileH, a.H);  // exclusive
+  const int id = L.ids ? L.ids[env] : 0;
+  const bool valid = id >= 0 && id < L.K;  // an id outside the library renders nothing (never dereferenced)
+  const int first = valid ? L.mesh_tris[2 * id] : 0, count = valid ? L.mesh_tris[2 * id + 1] : 0;
+  const int t0 = chunk * kLibChunk;
+  if (MERGE && t0 >= count) return;  // (workgroup-uniform)
+  const RasterPose P = raster_pose(a, env);
+  float bs[4] = {0.0f, 0.0f, 0.0f, -1.0f};
+  if (valid && L.mesh_bs) { bs[0] = L.mesh_bs[4 * id]; bs[1] = L.mesh_bs[4 * id + 1]; bs[2] = L.mesh_bs[4 * id + 2]; bs[3] = L.mesh_bs[4 * id + 3]; }
+  const bool tile_empty = t0 >= count || raster_tile_empty(a, P, bs, x0, x1, y0, y1);
+  if (MERGE && tile_empty) return;
+  for (int i = threadIdx.x; i < kRasterTileW * kRasterTileH; i += blockDim.x) zbuf[i] = 0x7f800000u;  // +inf
+  __syncthreads();
+  const int t1 = min(count, t0 + kLibChunk);
+  for (int t = tile_empty ? t1 : t0 + (int)threadIdx.x; t < t1; t += blockDim.x) raster_triangle(a, P, first + t, x0, x1, y0, y1, zbuf);
+  __syncthreads();
+  for (int i = threadIdx.x; i < kRasterTileW * kRasterTileH; i += blockDim.x) {
+    const int yy = y0 + i / kRasterTileW, xx = x0 + i % kRasterTileW;
+    if (yy < y1 && xx < x1) {
+      float* d = a.depth + ((size_t)env * a.H + yy) * a.W + xx;
+      if (!MERGE) *d = __uint_as_float(zbuf[i]);
+      else if (zbuf[i] != 0x7f800000u) atomicMin(reinterpret_cast<unsigned*>(d), zbuf[i]);
+    }
   }
 }
 
@@ -336,5 +415,48 @@ extern "C" int tacex_depth_from_deformed_mesh(const double* x_dev, int num_verts
                      (hipStream_t)stream, a);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) { set_error("deformed_mesh_depth_kernel: %s", hipGetErrorString(e)); return 1; }
+  return 0;
+}
+
+
+extern "C" int tacex_depth_from_mesh_library(const float* verts_dev, const int32_t* tris_dev, const int32_t* mesh_tris_dev,
+                                             const float* mesh_spheres_dev, int num_meshes, int max_mesh_tris, const int32_t* mesh_ids_dev,
+                                             const float* pos_dev, const float* quat_dev, float fx, float fy, float cx, float cy,
+                                             float near_clip_m, float far_clip_m, float* depth_m_dev, int num_envs, int height, int width,
+                                             void* stream) {
+  using namespace tacex;
+  if (!verts_dev || !tris_dev || !mesh_tris_dev || !pos_dev || !quat_dev || !depth_m_dev) {
+    set_error("tacex_depth_from_mesh_library: null buffer"); return 2;
+  }
+  if (num_meshes <= 0 || max_mesh_tris <= 0 || height <= 0 || width <= 0) {
+    set_error("tacex_depth_from_mesh_library: empty library or image (meshes %d, max triangles %d, image %dx%d)", num_meshes, max_mesh_tris,
+              width, height);
+    return 2;
+  }
+  if (!(near_clip_m >= 0.0f) || !(far_clip_m > near_clip_m)) {
+    set_error("tacex_depth_from_mesh_library: clipping range (%g, %g)", near_clip_m, far_clip_m); return 2;
+  }
+  if (num_envs <= 0) return 0;
+  RasterLibArgs L{};
+  RasterArgs& a = L.r;
+  a.verts = verts_dev; a.tris = tris_dev; a.pos = pos_dev; a.quat = quat_dev; a.depth = depth_m_dev;
+  a.B = num_envs; a.H = height; a.W = width;
+  a.fx = fx; a.fy = fy; a.cx = cx; a.cy = cy; a.near_m = near_clip_m; a.far_m = far_clip_m;
+  a.bs[3] = -1.0f;
+  a.tiles_x = (width + kRasterTileW - 1) / kRasterTileW; a.tiles_y = (height + kRasterTileH - 1) / kRasterTileH;
+  L.mesh_tris = mesh_tris_dev; L.mesh_bs = mesh_spheres_dev; L.ids = mesh_ids_dev; L.K = num_meshes;
+  const int chunks = (max_mesh_tris + kLibChunk - 1) / kLibChunk;
+  const size_t pairs = (size_t)num_envs * a.tiles_x * a.tiles_y;
+  if (pairs * (size_t)std::max(chunks - 1, 1) >= (size_t)1 << 31) { set_error("tacex_depth_from_mesh_library: grid too large"); return 2; }
+  L.chunk0 = 0; L.nchunk = 1;
+  hipLaunchKernelGGL(mesh_library_depth_kernel<false>, dim3((unsigned)pairs), dim3(256), 0, (hipStream_t)stream, L);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) { set_error("mesh_library_depth_kernel: %s", hipGetErrorString(e)); return 1; }
+  if (chunks > 1) {
+    L.chunk0 = 1; L.nchunk = chunks - 1;
+    hipLaunchKernelGGL(mesh_library_depth_kernel<true>, dim3((unsigned)(pairs * L.nchunk)), dim3(256), 0, (hipStream_t)stream, L);
+    e = hipGetLastError();
+    if (e != hipSuccess) { set_error("mesh_library_depth_kernel: %s", hipGetErrorString(e)); return 1; }
+  }
   return 0;
 }

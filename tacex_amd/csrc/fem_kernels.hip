@@ -23,6 +23,7 @@
 
 #include <algorithm>
 #include <map>
+#include <string>
 #include <utility>
 #include <vector>
 
@@ -60,11 +61,16 @@ struct FemDev {
   const int* cn_vtx;
   const double* cn_w;
   const double* ac_inv;     // (3 nc, 3 nc) inverse of P^T A_0 P, A_0 = rest-state operator incl. the constraint masses
-  // rigid triangle-mesh indenter shared by all envs (indenter kind 4, tacex_fem_set_indenter_mesh)
-  int im_nt;                // triangles
-  const double* im_tri;     // (nt,9) a | b - a | c - a in the mesh frame
-  const double* im_bs;      // (nt,4) bounding sphere: centroid, radius
-  const double* im_cl;      // (ceil(nt / 16),4) bounding sphere of every cluster of 16 consecutive triangles (Morton order)
+  // rigid triangle-mesh indenters (kind 4): a LIBRARY of meshes, one chosen per env (tacex_fem_set_indenter_mesh_library / _ids;
+  // tacex_fem_set_indenter_mesh = a library of one).  Per mesh: (nt,9) triangles a | b - a | c - a in the mesh frame, (nt,4) their
+  // bounding spheres (centroid, radius), (ceil(nt / 16),4) the bounding sphere of every cluster of 16 consecutive triangles (Morton
+  // order of the mesh's own triangles; no cluster straddles two meshes).  (These five fields take the bytes of the one-mesh fields
+  // they replaced: the kernel argument layout - and the code of the MESH = false Newton kernels - stays what it was.)
+  int im_nt;                // triangles of all meshes (0: no library)
+  int im_nm;                // meshes
+  const double* im_lib;     // every mesh's three tables in one allocation, each region 32-byte aligned
+  const int* im_off;        // (nm,4) offsets into im_lib in doubles: triangles | spheres | clusters, then the triangle count
+  const int* im_ids;        // (B) mesh id of every env (tacex_fem_set_indenter_mesh_ids, read at every step); nullptr: mesh 0 everywhere
   // vertex chains of the block-tridiagonal part of the preconditioner (tacex_fem_set_chains); nullptr: every vertex its own chain
   int nch;                  // chains, singletons included (<= V)
   const int* ch_head;       // (nch) first vertex of every chain
@@ -85,6 +91,33 @@ struct ContactEval {
   double d, n[3];
   double e, b1, b2; // energy, dE/dd, d2E/dd2 (already times kappa w, NOT times dt^2)
 };
+// The env's mesh of the library, resolved ONCE per workgroup at kernel entry (wave-uniform: SGPRs).  nt = 0 - no mesh set, an env
+// whose row is not kind 4, or a mesh id outside [0, im_nm), which is never dereferenced - makes a kind-4 row "no indenter"; `bad`
+// reports the last case for a kind-4 row (kFemFlagBadMesh).  MESH = false: nothing is read.
+struct IndMesh {
+  int nt;
+  const double* tri;  // (nt,9) this mesh's tables in FemDev::im_lib
+  const double* bs;   // (nt,4)
+  const double* cl;   // (ceil(nt / 16),4)
+};
+template <bool MESH>
+__device__ __forceinline__ IndMesh env_mesh(const FemDev& m, int b, const double* ind, bool& bad) {
+  IndMesh r{0, nullptr, nullptr, nullptr};
+  bad = false;
+  if (!MESH || !ind || m.im_nm <= 0) return r;
+  const int id = m.im_ids ? __builtin_amdgcn_readfirstlane(m.im_ids[b]) : 0;
+  if (id < 0 || id >= m.im_nm) {
+    bad = (int)ind[0] == 4;
+    return r;
+  }
+  const int* e = m.im_off + 4 * id;
+  r.tri = m.im_lib + (unsigned)__builtin_amdgcn_readfirstlane(e[0]);
+  r.bs = m.im_lib + (unsigned)__builtin_amdgcn_readfirstlane(e[1]);
+  r.cl = m.im_lib + (unsigned)__builtin_amdgcn_readfirstlane(e[2]);
+  r.nt = __builtin_amdgcn_readfirstlane(e[3]);
+  return r;
+}
+
 // Unsigned distance of p (mesh frame) to the nearest triangle of the indenter mesh and the unit vector from the closest point to p.
 // Two-level culling with bounding spheres: clusters of kMeshCluster triangles (Morton order of the centroids, built on the host), then
 // the triangles of a cluster; a sphere farther than the best distance so far is skipped.  The sphere tables are fetched FOUR at a time
@@ -176,7 +209,8 @@ __device__ __noinline__ MeshDist mesh_distance(int nt, const double* __restrict_
 // MESH = false compiles the triangle-mesh indenter (kind 4: a function call in the middle of a 256-register kernel) out: the Newton
 // kernel is instantiated both ways and the mesh-capable one is launched only when a mesh has been set.
 template <bool MESH = true>
-__device__ __forceinline__ ContactEval contact_eval(const FemDev& m, const double* ind, double w, const double x[3], bool need_distance = true) {
+__device__ __forceinline__ ContactEval contact_eval(const FemDev& m, const IndMesh& im, const double* ind, double w, const double x[3],
+                                                    bool need_distance = true) {
   ContactEval c;
   c.active = false; c.penetrating = false; c.d = 1e300; c.e = 0.0; c.b1 = 0.0; c.b2 = 0.0; c.n[0] = c.n[1] = c.n[2] = 0.0;
   if (!ind || !(w > 0.0)) return c;
@@ -203,8 +237,8 @@ __device__ __forceinline__ ContactEval contact_eval(const FemDev& m, const doubl
     c.d = rho - ind[4];
     const double ir = rho > 0.0 ? 1.0 / rho : 0.0;
     c.n[0] = r0 * ir; c.n[1] = r1 * ir; c.n[2] = r2 * ir;
-  } else if (MESH && kind == 4 && m.im_nt > 0) {
-    // rigid triangle mesh (tacex_fem_set_indenter_mesh) at position c with rotation vector (nx, ny, nz), inflated by R: UNSIGNED
+  } else if (MESH && kind == 4 && im.nt > 0) {
+    // rigid triangle mesh (the env's mesh of the library, env_mesh) at position c with rotation vector (nx, ny, nz), inflated by R: UNSIGNED
     // distance to the nearest triangle - R (the step bound keeps a vertex from crossing the surface; a vertex that starts
     // inside the mesh is not detected)
     const double r0 = ind[5], r1 = ind[6], r2 = ind[7];
@@ -218,7 +252,7 @@ __device__ __forceinline__ ContactEval contact_eval(const FemDev& m, const doubl
     const double pl[3] = {R[0] * g0 + R[3] * g1 + R[6] * g2, R[1] * g0 + R[4] * g1 + R[7] * g2, R[2] * g0 + R[5] * g1 + R[8] * g2};  // R^T (x - c)
     // need_distance = false (energy evaluations): anything at or beyond d_hat is as good as infinitely far
     const double reach = m.dhat + ind[4];
-    const MeshDist md = mesh_distance(m.im_nt, m.im_tri, m.im_bs, m.im_cl, pl[0], pl[1], pl[2], need_distance ? 1e300 : reach * reach * (1.0 + 1e-12));
+    const MeshDist md = mesh_distance(im.nt, im.tri, im.bs, im.cl, pl[0], pl[1], pl[2], need_distance ? 1e300 : reach * reach * (1.0 + 1e-12));
     const double nl[3] = {md.n0, md.n1, md.n2};
     c.d = md.d - ind[4];
     c.n[0] = R[0] * nl[0] + R[1] * nl[1] + R[2] * nl[2];
@@ -591,7 +625,7 @@ __device__ __forceinline__ double block_sum_max(double v, double* sh) {
 constexpr int kLsRescueStream = 32;  // rescue halvings of the line search next to a barrier (kLsRescue of the CU-resident kernel)
 
 __device__ double env_energy(const FemDev& m, const double* x, const double* xt, const uint8_t* cons, const double* aim,
-                             double* sh, const double* ind = nullptr, const double* fl = nullptr, const double* xn = nullptr,
+                             double* sh, const IndMesh& im, const double* ind = nullptr, const double* fl = nullptr, const double* xn = nullptr,
                              const double* disp = nullptr) {
   double e = 0.0;
   for (int t = threadIdx.x; t < m.T; t += blockDim.x) {
@@ -613,7 +647,7 @@ __device__ double env_energy(const FemDev& m, const double* x, const double* xt,
       if (cons && cons[v]) { const double c = x[v * 3 + i] - aim[v * 3 + i]; qc += c * c; }
     }
     e += 0.5 * mv * q + 0.5 * m.strength * mv * qc;
-    if (ind && m.area) e += m.dt * m.dt * contact_eval(m, ind, m.area[v], x + v * 3).e;
+    if (ind && m.area) e += m.dt * m.dt * contact_eval(m, im, ind, m.area[v], x + v * 3).e;
     if (fl) e += m.dt * m.dt * friction_eval(m.fric_mu, m.fric_eps, fl + (size_t)v * 4, x + v * 3, xn + v * 3, disp, false).e;
   }
   return block_sum(e, sh);
@@ -652,8 +686,10 @@ __global__ __launch_bounds__(512) void fem_energy_kernel(FemDev m, const double*
   __shared__ double sh[17];
   const int b = blockIdx.x;
   const size_t o = (size_t)b * m.V * 3;
-  const double e = env_energy(m, x + o, xt + o, cons ? cons + (size_t)b * m.V : nullptr, aim ? aim + o : nullptr, sh,
-                              m.indenters ? m.indenters + (size_t)b * 8 : nullptr);
+  const double* ind = m.indenters ? m.indenters + (size_t)b * 8 : nullptr;
+  bool bad;
+  const IndMesh im = env_mesh<true>(m, b, ind, bad);
+  const double e = env_energy(m, x + o, xt + o, cons ? cons + (size_t)b * m.V : nullptr, aim ? aim + o : nullptr, sh, im, ind);
   if (threadIdx.x == 0) E[b] = e;
 }
 
@@ -663,6 +699,8 @@ __global__ __launch_bounds__(512) void fem_gradient_kernel(FemDev m, const doubl
   const int b = blockIdx.x;
   const size_t o = (size_t)b * m.V * 3;
   double* ge = ws_ge + (size_t)b * 12 * m.T;
+  bool bad;
+  const IndMesh im = env_mesh<true>(m, b, m.indenters ? m.indenters + (size_t)b * 8 : nullptr, bad);
   env_tet_gradients(m, x + o, ge);
   __syncthreads();
   for (int v = threadIdx.x; v < m.V; v += blockDim.x) {
@@ -677,7 +715,7 @@ __global__ __launch_bounds__(512) void fem_gradient_kernel(FemDev m, const doubl
       g[o + v * 3 + i] = gi;
     }
     if (m.indenters && m.area) {
-      const ContactEval ce = contact_eval(m, m.indenters + (size_t)b * 8, m.area[v], x + o + v * 3);
+      const ContactEval ce = contact_eval(m, im, m.indenters + (size_t)b * 8, m.area[v], x + o + v * 3);
       if (ce.active)
 #pragma unroll
         for (int i = 0; i < 3; ++i) g[o + v * 3 + i] += m.dt * m.dt * ce.b1 * ce.n[i];
@@ -753,6 +791,8 @@ constexpr int kFemFlagPenetration = 1;  // a contact vertex was at or beyond the
 constexpr int kFemFlagLsFailed = 2;     // a line search found no decrease even after the rescue halvings
 constexpr int kFemFlagCoarseOff = 4;    // informational: the coarse correction was switched off for the rest of the step (see kCoarseTrust)
 constexpr int kFemFlagPsdSafe = 8;      // informational: the PCG met negative curvature and the env solved iterations of the step in PSD-safe mode
+// (16: fem_ball.h's pair-list overflow)
+constexpr int kFemFlagBadMesh = 32;     // the env's kind-4 row named a mesh id outside the library: no indenter this step (env_mesh)
 __global__ __launch_bounds__(512) void fem_newton_kernel(FemDev m, double* xg, const double* xtg, const uint8_t* consg,
                                                          const double* aimg, double* stats, double* wsg,
                                                          int pcg_max_iter, double pcg_tol_rate, int ls_max_iter, double* dxg, double dx_tol,
@@ -806,6 +846,8 @@ __global__ __launch_bounds__(512) void fem_newton_kernel(FemDev m, double* xg, c
   // Vertex chains, the coarse correction, the contact-following start and the edge snap exist in the CU-resident kernel only - this
   // is the path of meshes with more vertices than its workgroup has threads.
   const double* ind = (m.indenters && m.area) ? m.indenters + (size_t)b * 8 : nullptr;
+  bool mesh_bad;
+  const IndMesh im = env_mesh<true>(m, b, ind, mesh_bad);
   const bool fric = ind && m.fric_mu > 0.0 && xprevg != nullptr && dispg != nullptr;
   const double* xn = fric ? xprevg + o : nullptr;
   double disp3[3] = {0, 0, 0};
@@ -843,7 +885,7 @@ __global__ __launch_bounds__(512) void fem_newton_kernel(FemDev m, double* xg, c
     double cg[3] = {0, 0, 0};
     {
       const double xv[3] = {x[v * 3], x[v * 3 + 1], x[v * 3 + 2]};
-      const ContactEval ce = contact_eval(m, ind, ind ? m.area[v] : 0.0, xv);
+      const ContactEval ce = contact_eval(m, im, ind, ind ? m.area[v] : 0.0, xv);
       if (ce.penetrating) pen = 1;
       const double cb2 = ce.active ? dt2 * ce.b2 : 0.0;
       cdat[(size_t)v * 5] = cb2;
@@ -898,11 +940,11 @@ __global__ __launch_bounds__(512) void fem_newton_kernel(FemDev m, double* xg, c
           for (int k = 0; k < 8; ++k) indp[k] = ind[k];
           indp[1] -= disp3[0]; indp[2] -= disp3[1]; indp[3] -= disp3[2];
           const double xn3[3] = {xn[v * 3], xn[v * 3 + 1], xn[v * 3 + 2]};
-          const ContactEval cp = contact_eval(m, indp, m.area[v], xn3);
+          const ContactEval cp = contact_eval(m, im, indp, m.area[v], xn3);
           lam = (cp.active && !cp.penetrating) ? -cp.b1 : 0.0;
           ln[0] = cp.n[0]; ln[1] = cp.n[1]; ln[2] = cp.n[2];
         } else {
-          const ContactEval ce = contact_eval(m, ind, m.area[v], xv);
+          const ContactEval ce = contact_eval(m, im, ind, m.area[v], xv);
           if (ce.active) {
             double go[3];
 #pragma unroll
@@ -1082,7 +1124,7 @@ __global__ __launch_bounds__(512) void fem_newton_kernel(FemDev m, double* xg, c
   }
   __syncthreads();
   // ---- backtracking line search on the incremental potential (accept the first E(x + step d) <= E(x)) ----
-  const double E0 = env_energy(m, x, xt, cons, aim, sh, ind, fl, xn, disp3);  // (lag rows: written and read by the vertex's own thread)
+  const double E0 = env_energy(m, x, xt, cons, aim, sh, im, ind, fl, xn, disp3);  // (lag rows: written and read by the vertex's own thread)
   double step = 1.0, E1 = E0;
   if (ind) {  // conservative step bound (1-Lipschitz distance): no surface vertex may use more than kCcdSlack of its gap
     double amax = 1.0;
@@ -1104,7 +1146,7 @@ __global__ __launch_bounds__(512) void fem_newton_kernel(FemDev m, double* xg, c
   for (int ls = 0; ls <= ls_cap; ++ls) {
     for (int k = threadIdx.x; k < 3 * V; k += blockDim.x) xc[k] = x[k] + step * vd[k];
     __syncthreads();
-    const double Ec = env_energy(m, xc, xt, cons, aim, sh, ind, fl, xn, disp3);
+    const double Ec = env_energy(m, xc, xt, cons, aim, sh, im, ind, fl, xn, disp3);
     if (Ec <= E0) { E1 = Ec; accepted = true; break; }
     step *= 0.5;
   }
@@ -1120,7 +1162,8 @@ __global__ __launch_bounds__(512) void fem_newton_kernel(FemDev m, double* xg, c
     if (dxg) dxg[b] = (step_info && !accepted && !(dmax <= dx_tol)) ? 0.0 : dmax;  // (tacex_fem_step only: tacex_fem_newton_step's callers read max |d| itself)
     stats[(size_t)b * 4 + 0] = E0; stats[(size_t)b * 4 + 1] = E1; stats[(size_t)b * 4 + 2] = step; stats[(size_t)b * 4 + 3] = (double)it;
     if (step_info) {
-      const int fl = (any_pen ? kFemFlagPenetration : 0) | ((!accepted && !(dmax <= dx_tol)) ? kFemFlagLsFailed : 0);
+      const int fl = (any_pen ? kFemFlagPenetration : 0) | ((!accepted && !(dmax <= dx_tol)) ? kFemFlagLsFailed : 0) |
+                     (mesh_bad ? kFemFlagBadMesh : 0);
       double* si = step_info + (size_t)b * 4;
       si[0] = (accumulate ? si[0] : 0.0) + 1.0;
       si[1] = dmax;
@@ -1188,7 +1231,7 @@ __device__ __forceinline__ double block_sum1(double v, double* sh2 /* 2 x NT / 6
 template <bool MESH, int NT>
 __device__ __forceinline__ double env_energy_lds(const FemDev& m, const double* xl, const double x3[3], const double* xt,
                                                  bool own, bool c, const double* aim, double* sh, int& phase,
-                                                 const double* ind = nullptr, double wv = 0.0, const double* fv = nullptr,
+                                                 const IndMesh& im, const double* ind = nullptr, double wv = 0.0, const double* fv = nullptr,
                                                  const double* xn = nullptr, const double* disp = nullptr, const double* e_tets = nullptr) {
   // e_tets: this thread's share of the elastic energy, already summed over the same tets in the same order by the gradient sweep of the
   // Newton iteration (same x): the line search's E(x) then costs no tet sweep of its own - and is the same bits as with one
@@ -1215,7 +1258,7 @@ __device__ __forceinline__ double env_energy_lds(const FemDev& m, const double* 
       if (c) { const double cc = x3[i] - aim[v * 3 + i]; qc += cc * cc; }
     }
     e += 0.5 * mv * q + 0.5 * m.strength * mv * qc;
-    if (ind) e += dt2 * contact_eval<MESH>(m, ind, wv, x3, false).e;
+    if (ind) e += dt2 * contact_eval<MESH>(m, im, ind, wv, x3, false).e;
     if (fv) {
       const double xn3[3] = {xn[v * 3], xn[v * 3 + 1], xn[v * 3 + 2]};
       e += dt2 * friction_eval(m.fric_mu, m.fric_eps, fv + v * 4, x3, xn3, disp, false).e;
@@ -1325,6 +1368,8 @@ __global__ __launch_bounds__(NT) void fem_newton_lds_kernel(FemDev m, double* xg
   // contact: this vertex's weight and the env's indenter (nullptr: contact off)
   const double* ind = (m.indenters && m.area) ? m.indenters + (size_t)b * 8 : nullptr;
   const double wv = (ind && own) ? m.area[tid] : 0.0;
+  bool mesh_bad;
+  const IndMesh im = env_mesh<MESH>(m, b, ind, mesh_bad);
   // friction needs the positions the step started from: tacex_fem_step only
   const bool fric = ind && m.fric_mu > 0.0 && xprevg != nullptr && dispg != nullptr;
   const double* xn = fric ? xprevg + o : nullptr;
@@ -1346,11 +1391,11 @@ __global__ __launch_bounds__(NT) void fem_newton_lds_kernel(FemDev m, double* xg
     // nothing is moved: the shrunken gap raises the barrier force and that start already converges in two iterations (following
     // there was measured: the over-displaced surface has to come back up into the barrier and line searches fail).
     if ((follow & 1) && ind && wv > 0.0 && (disp3[0] != 0.0 || disp3[1] != 0.0 || disp3[2] != 0.0)) {
-      const ContactEval c0 = contact_eval<MESH>(m, ind, wv, x3);
+      const ContactEval c0 = contact_eval<MESH>(m, im, ind, wv, x3);
       const double dn = disp3[0] * c0.n[0] + disp3[1] * c0.n[1] + disp3[2] * c0.n[2];
       if (dn < 0.0 && !c0.penetrating && c0.d < 1e299) {
         const double xm[3] = {x3[0] + dn * c0.n[0], x3[1] + dn * c0.n[1], x3[2] + dn * c0.n[2]};
-        const ContactEval cf = contact_eval<MESH>(m, ind, wv, xm);
+        const ContactEval cf = contact_eval<MESH>(m, im, ind, wv, xm);
         if (cf.active && !cf.penetrating) { x3[0] = xm[0]; x3[1] = xm[1]; x3[2] = xm[2]; }
       }
     }
@@ -1575,7 +1620,7 @@ restart_iteration:
   }
   // barrier of this vertex at x: gradient b1 n, curvature b2 n n^T (the b1 * hess(d) part is negative semi-definite for a
   // convex indenter and dropped: the usual PSD projection of IPC)
-  const ContactEval ce = contact_eval<MESH>(m, ind, wv, x3);
+  const ContactEval ce = contact_eval<MESH>(m, im, ind, wv, x3);
   if (ce.penetrating) flags |= kFemFlagPenetration;  // (per thread; or-reduced into step_info at the end)
   if (ce.active) {
 #pragma unroll
@@ -1604,7 +1649,7 @@ restart_iteration:
         for (int k = 0; k < 8; ++k) indp[k] = ind[k];
         indp[1] -= disp3[0]; indp[2] -= disp3[1]; indp[3] -= disp3[2];
         const double xn3[3] = {xn[tid * 3], xn[tid * 3 + 1], xn[tid * 3 + 2]};
-        const ContactEval cp = contact_eval<MESH>(m, indp, wv, xn3);
+        const ContactEval cp = contact_eval<MESH>(m, im, indp, wv, xn3);
         lam = (cp.active && !cp.penetrating) ? -cp.b1 : 0.0;
         ln[0] = cp.n[0]; ln[1] = cp.n[1]; ln[2] = cp.n[2];
       } else if (ce.active) {
@@ -2029,9 +2074,9 @@ restart_iteration:
   FEM_PHASE(2);
   // ---- backtracking line search on the incremental potential (accept the first E(x + step d) <= E(x)) ----
 #ifdef TACEX_FEM_SEPARATE_E0  // (A/B hook: E(x) by a tet sweep of its own, as before)
-  const double E0 = env_energy_lds<MESH, NT>(m, xs, x3, xt, own, c, aim, sh, phase, ind, wv, fric_phase ? fl : nullptr, xn, disp3);
+  const double E0 = env_energy_lds<MESH, NT>(m, xs, x3, xt, own, c, aim, sh, phase, im, ind, wv, fric_phase ? fl : nullptr, xn, disp3);
 #else
-  const double E0 = env_energy_lds<MESH, NT>(m, xs, x3, xt, own, c, aim, sh, phase, ind, wv, fric_phase ? fl : nullptr, xn, disp3, &e_tets);
+  const double E0 = env_energy_lds<MESH, NT>(m, xs, x3, xt, own, c, aim, sh, phase, im, ind, wv, fric_phase ? fl : nullptr, xn, disp3, &e_tets);
 #endif
   double step = 1.0, E1 = E0;
   if (ind) {
@@ -2060,7 +2105,7 @@ restart_iteration:
       for (int i = 0; i < 3; ++i) { xc3[i] = x3[i] + step * d3[i]; ps[tid * 3 + i] = xc3[i]; }
     }
     __syncthreads();
-    const double Ec = env_energy_lds<MESH, NT>(m, ps, xc3, xt, own, c, aim, sh, phase, ind, wv, fric_phase ? fl : nullptr, xn, disp3);
+    const double Ec = env_energy_lds<MESH, NT>(m, ps, xc3, xt, own, c, aim, sh, phase, im, ind, wv, fric_phase ? fl : nullptr, xn, disp3);
     if (Ec <= E0) { E1 = Ec; accepted = true; break; }
     step *= 0.5;
   }
@@ -2109,7 +2154,7 @@ restart_iteration:
       fric_phase = true;
       bool touching = false;
       if (own) {
-        const ContactEval cf = contact_eval<MESH>(m, ind, wv, x3);
+        const ContactEval cf = contact_eval<MESH>(m, im, ind, wv, x3);
         touching = cf.active;
         fl[tid * 4] = 0.0; fl[tid * 4 + 1] = 0.0; fl[tid * 4 + 2] = 0.0; fl[tid * 4 + 3] = 0.0;
       }
@@ -2131,7 +2176,7 @@ restart_iteration:
     // (__syncthreads_or returns a truth value, not the OR of the bits: one reduction per flag)
     const int any = (__syncthreads_or(flags & kFemFlagPenetration) ? kFemFlagPenetration : 0) |
                     (__syncthreads_or(flags & kFemFlagLsFailed) ? kFemFlagLsFailed : 0) |
-                    (flags & (kFemFlagCoarseOff | kFemFlagPsdSafe));  // (these two are block-uniform)
+                    (flags & (kFemFlagCoarseOff | kFemFlagPsdSafe)) | (mesh_bad ? kFemFlagBadMesh : 0);  // (these are block-uniform)
     if (tid == 0) {
       step_info[(size_t)b * 4 + 0] = (double)n_newton; step_info[(size_t)b * 4 + 1] = dmax_last;
       step_info[(size_t)b * 4 + 2] = (double)any; step_info[(size_t)b * 4 + 3] = pcg_total;
@@ -2547,10 +2592,12 @@ static int fem_upload(tacex_fem_ctx* c, const std::vector<T>& h, const T** out) 
 __global__ __launch_bounds__(256) void fem_contact_gaps_kernel(FemDev m, const double* xg, double* gaps) {
   const int b = blockIdx.x;
   const double* ind = m.indenters ? m.indenters + (size_t)b * 8 : nullptr;
+  bool bad;
+  const IndMesh im = env_mesh<true>(m, b, ind, bad);
   for (int v = threadIdx.x; v < m.V; v += blockDim.x) {
     const double* x = xg + ((size_t)b * m.V + v) * 3;
     const double x3[3] = {x[0], x[1], x[2]};
-    const ContactEval c = contact_eval<true>(m, ind, 1.0, x3);
+    const ContactEval c = contact_eval<true>(m, im, ind, 1.0, x3);
     gaps[(size_t)b * m.V + v] = c.d < 1e299 ? c.d : INFINITY;
   }
 }
@@ -2826,20 +2873,13 @@ int tacex_fem_set_friction_lag(tacex_fem_ctx* c, int mode) {
 
 int tacex_fem_newton_resident(const tacex_fem_ctx* c) { return c ? c->last_resident : -1; }
 
-int tacex_fem_set_indenter_mesh(tacex_fem_ctx* c, int num_verts, const double* verts_host, int num_tris, const int32_t* tris_host) {
-  if (!c) { set_error("tacex_fem_set_indenter_mesh: null context"); return 2; }
-  if (num_tris == 0) {
-    bool synced = false;
-    (void)hipSetDevice(c->device);
-    fem_release(c, c->dev.im_tri, &synced); fem_release(c, c->dev.im_bs, &synced); fem_release(c, c->dev.im_cl, &synced);
-    c->dev_nwt.im_tri = nullptr; c->dev_nwt.im_bs = nullptr; c->dev_nwt.im_cl = nullptr;
-    c->dev.im_nt = c->dev_nwt.im_nt = 0;
-    return 0;
-  }
-  if (num_verts < 3 || num_tris < 1 || !verts_host || !tris_host) { set_error("tacex_fem_set_indenter_mesh: bad arguments"); return 2; }
+// One mesh's tables for the library: triangles in Morton order of their centroids (10 bits per axis over the mesh's bounding box),
+// 16 consecutive ones form a cluster.  Appended to tri / bs / cl: a mesh's slice is the same whatever else the library holds.
+static int pack_indenter_mesh(const char* who, int num_verts, const double* verts_host, int num_tris, const int32_t* tris_host,
+                              std::vector<double>& tri, std::vector<double>& bs, std::vector<double>& cl) {
+  if (num_verts < 3 || num_tris < 1 || !verts_host || !tris_host) { set_error("%s: bad arguments", who); return 2; }
   for (int k = 0; k < num_tris * 3; ++k)
-    if (tris_host[k] < 0 || tris_host[k] >= num_verts) { set_error("tacex_fem_set_indenter_mesh: vertex index %d out of range", tris_host[k]); return 2; }
-  // triangles in Morton order of their centroids (10 bits per axis over the bounding box): 16 consecutive ones form a cluster
+    if (tris_host[k] < 0 || tris_host[k] >= num_verts) { set_error("%s: vertex index %d out of range", who, tris_host[k]); return 2; }
   double lo[3] = {1e300, 1e300, 1e300}, hi[3] = {-1e300, -1e300, -1e300};
   for (int i = 0; i < num_verts; ++i)
     for (int k = 0; k < 3; ++k) { lo[k] = fmin(lo[k], verts_host[(size_t)i * 3 + k]); hi[k] = fmax(hi[k], verts_host[(size_t)i * 3 + k]); }
@@ -2857,50 +2897,123 @@ int tacex_fem_set_indenter_mesh(tacex_fem_ctx* c, int num_verts, const double* v
   }
   std::sort(order.begin(), order.end());
   const int ncl = (num_tris + kMeshCluster - 1) / kMeshCluster;
-  std::vector<double> tri((size_t)num_tris * 9), bs((size_t)num_tris * 4), cl((size_t)ncl * 4);
+  const size_t tb = tri.size() / 9, cb = cl.size() / 4;  // this mesh's first triangle / cluster in the library
+  tri.resize((tb + num_tris) * 9); bs.resize((tb + num_tris) * 4); cl.resize((cb + ncl) * 4);
+  double* tr = tri.data() + tb * 9;
+  double* bsp = bs.data() + tb * 4;
+  double* clp = cl.data() + cb * 4;
   for (int s = 0; s < num_tris; ++s) {
     const int t = order[s].second;
     const double* v[3];
     for (int k = 0; k < 3; ++k) v[k] = verts_host + (size_t)tris_host[(size_t)t * 3 + k] * 3;
     double cen[3];
     for (int k = 0; k < 3; ++k) {
-      tri[(size_t)s * 9 + k] = v[0][k];
-      tri[(size_t)s * 9 + 3 + k] = v[1][k] - v[0][k];
-      tri[(size_t)s * 9 + 6 + k] = v[2][k] - v[0][k];
+      tr[(size_t)s * 9 + k] = v[0][k];
+      tr[(size_t)s * 9 + 3 + k] = v[1][k] - v[0][k];
+      tr[(size_t)s * 9 + 6 + k] = v[2][k] - v[0][k];
       cen[k] = (v[0][k] + v[1][k] + v[2][k]) / 3.0;
-      bs[(size_t)s * 4 + k] = cen[k];
+      bsp[(size_t)s * 4 + k] = cen[k];
     }
     double r = 0.0;
     for (int j = 0; j < 3; ++j) {
       const double d0 = v[j][0] - cen[0], d1 = v[j][1] - cen[1], d2 = v[j][2] - cen[2];
       r = fmax(r, sqrt(d0 * d0 + d1 * d1 + d2 * d2));
     }
-    bs[(size_t)s * 4 + 3] = r * (1.0 + 1e-12);
+    bsp[(size_t)s * 4 + 3] = r * (1.0 + 1e-12);
   }
   for (int q = 0; q < ncl; ++q) {
     const int s0 = q * kMeshCluster, s1 = std::min(num_tris, s0 + kMeshCluster);
     double cen[3] = {0, 0, 0};
     for (int s = s0; s < s1; ++s)
-      for (int k = 0; k < 3; ++k) cen[k] += bs[(size_t)s * 4 + k] / (s1 - s0);
+      for (int k = 0; k < 3; ++k) cen[k] += bsp[(size_t)s * 4 + k] / (s1 - s0);
     double r = 0.0;
     for (int s = s0; s < s1; ++s) {
-      const double d0 = bs[(size_t)s * 4] - cen[0], d1 = bs[(size_t)s * 4 + 1] - cen[1], d2 = bs[(size_t)s * 4 + 2] - cen[2];
-      r = fmax(r, sqrt(d0 * d0 + d1 * d1 + d2 * d2) + bs[(size_t)s * 4 + 3]);
+      const double d0 = bsp[(size_t)s * 4] - cen[0], d1 = bsp[(size_t)s * 4 + 1] - cen[1], d2 = bsp[(size_t)s * 4 + 2] - cen[2];
+      r = fmax(r, sqrt(d0 * d0 + d1 * d1 + d2 * d2) + bsp[(size_t)s * 4 + 3]);
     }
-    for (int k = 0; k < 3; ++k) cl[(size_t)q * 4 + k] = cen[k];
-    cl[(size_t)q * 4 + 3] = r * (1.0 + 1e-12);
+    for (int k = 0; k < 3; ++k) clp[(size_t)q * 4 + k] = cen[k];
+    clp[(size_t)q * 4 + 3] = r * (1.0 + 1e-12);
+  }
+  return 0;
+}
+
+// replaces the library (num_meshes = 0: removes it); the per-env id array stays the caller's
+static int set_indenter_library(tacex_fem_ctx* c, const char* who, int num_meshes, const int32_t* vert_counts, const double* verts_host,
+                                const int32_t* tri_counts, const int32_t* tris_host) {
+  if (num_meshes < 0 || (num_meshes > 0 && (!vert_counts || !verts_host || !tri_counts || !tris_host))) {
+    set_error("%s: bad arguments", who);
+    return 2;
+  }
+  std::vector<double> tri, bs, cl;
+  std::vector<int> off((size_t)4 * num_meshes, 0);
+  const double* vp = verts_host;
+  const int32_t* tp = tris_host;
+  for (int k = 0; k < num_meshes; ++k) {
+    off[(size_t)4 * k] = (int)(tri.size() / 9);   // (first triangle | first cluster for now: offsets into im_lib below)
+    off[(size_t)4 * k + 2] = (int)(cl.size() / 4);
+    off[(size_t)4 * k + 3] = tri_counts[k];
+    if (int rc = pack_indenter_mesh(who, vert_counts[k], vp, tri_counts[k], tp, tri, bs, cl)) {
+      if (num_meshes > 1) {
+        const std::string why = tacex_last_error();
+        set_error("mesh %d: %s", k, why.c_str());
+      }
+      return rc;
+    }
+    if ((tri.size() + bs.size() + cl.size()) >= (size_t)1 << 31) { set_error("%s: library of more than 2^31 doubles", who); return 2; }
+    vp += (size_t)vert_counts[k] * 3;
+    tp += (size_t)tri_counts[k] * 3;
+  }
+  // im_lib = triangles | spheres | clusters, every region starting on a multiple of 4 doubles (the sphere tables are read as 32-byte vectors)
+  const size_t nt = tri.size() / 9;
+  const size_t bs0 = (tri.size() + 3) & ~(size_t)3, cl0 = bs0 + bs.size();
+  std::vector<double> lib(cl0 + cl.size(), 0.0);
+  std::copy(tri.begin(), tri.end(), lib.begin());
+  std::copy(bs.begin(), bs.end(), lib.begin() + (long)bs0);
+  std::copy(cl.begin(), cl.end(), lib.begin() + (long)cl0);
+  for (int k = 0; k < num_meshes; ++k) {
+    const size_t t0 = (size_t)off[(size_t)4 * k], c0 = (size_t)off[(size_t)4 * k + 2];
+    off[(size_t)4 * k] = (int)(t0 * 9);
+    off[(size_t)4 * k + 1] = (int)(bs0 + t0 * 4);
+    off[(size_t)4 * k + 2] = (int)(cl0 + c0 * 4);
   }
   hipError_t e = hipSetDevice(c->device);
   if (e != hipSuccess) return fail_hip(e, "hipSetDevice");
   FemDev& d = c->dev;
   {
     bool synced = false;
-    fem_release(c, d.im_tri, &synced); fem_release(c, d.im_bs, &synced); fem_release(c, d.im_cl, &synced);
-    d.im_nt = c->dev_nwt.im_nt = 0;
+    fem_release(c, d.im_lib, &synced); fem_release(c, d.im_off, &synced);
+    d.im_nt = d.im_nm = 0;
+    c->dev_nwt.im_lib = nullptr; c->dev_nwt.im_off = nullptr; c->dev_nwt.im_nt = c->dev_nwt.im_nm = 0;
   }
-  if (int rc = fem_upload(c, tri, &d.im_tri) | fem_upload(c, bs, &d.im_bs) | fem_upload(c, cl, &d.im_cl)) return rc;
-  d.im_nt = num_tris;
-  c->dev_nwt.im_nt = num_tris; c->dev_nwt.im_tri = d.im_tri; c->dev_nwt.im_bs = d.im_bs; c->dev_nwt.im_cl = d.im_cl;
+  if (num_meshes > 0) {
+    if (int rc = fem_upload(c, lib, &d.im_lib) | fem_upload(c, off, &d.im_off)) return rc;
+    d.im_nt = (int)nt;
+    d.im_nm = num_meshes;
+  }
+  FemDev& n2 = c->dev_nwt;
+  n2.im_nt = d.im_nt; n2.im_nm = d.im_nm; n2.im_lib = d.im_lib; n2.im_off = d.im_off;
+  return 0;
+}
+
+int tacex_fem_set_indenter_mesh(tacex_fem_ctx* c, int num_verts, const double* verts_host, int num_tris, const int32_t* tris_host) {
+  if (!c) { set_error("tacex_fem_set_indenter_mesh: null context"); return 2; }
+  // a library of one, shared by every env
+  if (num_tris != 0 && (num_verts < 3 || num_tris < 1 || !verts_host || !tris_host)) { set_error("tacex_fem_set_indenter_mesh: bad arguments"); return 2; }
+  const int32_t nv = num_verts, nt = num_tris;
+  const int rc = set_indenter_library(c, "tacex_fem_set_indenter_mesh", num_tris == 0 ? 0 : 1, &nv, verts_host, &nt, tris_host);
+  if (rc == 0) c->dev.im_ids = c->dev_nwt.im_ids = nullptr;
+  return rc;
+}
+
+int tacex_fem_set_indenter_mesh_library(tacex_fem_ctx* c, int num_meshes, const int32_t* vert_counts, const double* verts_host,
+                                        const int32_t* tri_counts, const int32_t* tris_host) {
+  if (!c) { set_error("tacex_fem_set_indenter_mesh_library: null context"); return 2; }
+  return set_indenter_library(c, "tacex_fem_set_indenter_mesh_library", num_meshes, vert_counts, verts_host, tri_counts, tris_host);
+}
+
+int tacex_fem_set_indenter_mesh_ids(tacex_fem_ctx* c, const int32_t* ids_dev) {
+  if (!c) { set_error("tacex_fem_set_indenter_mesh_ids: null context"); return 2; }
+  c->dev.im_ids = c->dev_nwt.im_ids = ids_dev;
   return 0;
 }
 
@@ -3077,12 +3190,6 @@ static int launch_newton(tacex_fem_ctx* c, double* x, const double* xt, const ui
   }
   if (resident) *resident = false;
   c->last_resident = 0;
-  if (c->dev.indenters && c->dev.im_nt > 0) {
-    set_error("FEM Newton: a mesh indenter needs the CU-resident Newton kernel (mesh with <= 512 vertices whose state fits the CU's 160 KB of "
-              "LDS - this one needs %zu bytes; TACEX_FEM_NEWTON_LDS != 0); the streaming kernel of larger meshes handles analytic indenters "
-              "(barrier, step bound, friction) only", lds);
-    return 2;
-  }
   // x, p and the H.p accumulators in LDS when the summation order is free (atomic mode) and they fit (9 V doubles: ~2 200 vertices)
   static const int stream_lds = getenv("TACEX_FEM_STREAM_LDS") ? atoi(getenv("TACEX_FEM_STREAM_LDS")) : 2;  // A/B hook: 0 none, 1 x / p / accumulators, 2 all PCG vectors
   const bool lds_all = stream_lds != 1 && (size_t)21 * V * sizeof(double) <= 160 * 1024;  // (TACEX_FEM_STREAM_LDS=1: x, p, accumulators only)

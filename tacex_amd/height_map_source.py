@@ -90,6 +90,79 @@ class MeshDepthSource:
         return self.depth
 
 
+class MeshLibraryDepthSource:
+    """Camera depth of a rigid triangle mesh per env, each env rendering ITS OWN mesh of a library (`tacex_depth_from_mesh_library`,
+    one HIP launch plus one for meshes of more than 1024 triangles): the TiledCamera read-out of a scene whose envs hold different
+    objects (a multi-asset spawner).  Same calling contract as `MeshDepthSource`: `source()` -> (num_envs, H, W) float32 depth in metres,
+    inf where nothing is seen; the caller updates `pos` (num_envs, 3), `quat` (num_envs, 4, wxyz) - the object's pose in the CAMERA
+    frame - and `mesh_ids` (num_envs,) int32 in place.  Each env's image is bit-equal to `MeshDepthSource(*meshes[id])` with the same
+    pose; an id outside [0, len(meshes)) renders nothing.  `fill(...)` is the `set_height_map_source` interface (render +
+    `tacex_height_map_from_depth` with this source's clipping range)."""
+
+    def __init__(self, meshes, num_envs: int, device, resolution=(320, 240), intrinsics=(340.0, 325.0, 160.0, 125.0),
+                 clipping_range=(0.024, 0.029)):
+        dev = torch.device(device)
+        if dev.type != "cuda":
+            raise _lib.TacexHipError("MeshLibraryDepthSource needs an AMD GPU device (no CPU fallback)")
+        if len(meshes) == 0:
+            raise ValueError("MeshLibraryDepthSource: empty mesh library")
+        verts, tris, table, spheres, base = [], [], [], [], 0
+        for k, (v, t) in enumerate(meshes):
+            v = torch.as_tensor(v, dtype=torch.float32).reshape(-1, 3).cpu()
+            t = torch.as_tensor(t, dtype=torch.int32).reshape(-1, 3).cpu()
+            if t.numel() == 0 or int(t.min()) < 0 or int(t.max()) >= v.shape[0]:
+                raise ValueError(f"MeshLibraryDepthSource: mesh {k}: triangle indices out of range")
+            vd = v.double()
+            c = 0.5 * (vd.min(0).values + vd.max(0).values)  # (the bounding sphere of MeshDepthSource)
+            spheres.append([float(c[0]), float(c[1]), float(c[2]), float((vd - c).norm(dim=1).max()) * 1.0001])
+            table.append([sum(len(x) for x in tris), t.shape[0]])
+            verts.append(v)
+            tris.append(t + base)
+            base += v.shape[0]
+        self.num_meshes = len(meshes)
+        self.verts = torch.cat(verts).contiguous().to(dev)
+        self.tris = torch.cat(tris).contiguous().to(dev)
+        self.mesh_tris = torch.tensor(table, dtype=torch.int32, device=dev)
+        self.mesh_spheres = torch.tensor(spheres, dtype=torch.float32, device=dev)
+        self._max_tris = max(n for _, n in table)
+        self.W, self.H = int(resolution[0]), int(resolution[1])
+        self.fx, self.fy, self.cx, self.cy = (float(v) for v in intrinsics)
+        self.near, self.far = float(clipping_range[0]), float(clipping_range[1])
+        self.pos = torch.zeros((num_envs, 3), dtype=torch.float32, device=dev)
+        self.pos[:, 2] = 1.0  # out of range until the caller places the object
+        self.quat = torch.zeros((num_envs, 4), dtype=torch.float32, device=dev)
+        self.quat[:, 0] = 1.0
+        self.mesh_ids = torch.zeros((num_envs,), dtype=torch.int32, device=dev)
+        self.depth = torch.empty((num_envs, self.H, self.W), dtype=torch.float32, device=dev)
+        self._lib = _lib.load_library()
+
+    def __call__(self) -> torch.Tensor:
+        if self.mesh_ids.dtype != torch.int32 or self.mesh_ids.shape != (self.depth.shape[0],) or not self.mesh_ids.is_contiguous():
+            raise ValueError(f"MeshLibraryDepthSource.mesh_ids must stay a contiguous ({self.depth.shape[0]},) int32 tensor")
+        with torch.cuda.device(self.depth.device):
+            rc = self._lib.tacex_depth_from_mesh_library(
+                _lib.ptr(self.verts), _lib.ptr(self.tris), _lib.ptr(self.mesh_tris), _lib.ptr(self.mesh_spheres), self.num_meshes,
+                self._max_tris, _lib.ptr(self.mesh_ids), _lib.ptr(self.pos), _lib.ptr(self.quat), self.fx, self.fy, self.cx, self.cy,
+                self.near, self.far, _lib.ptr(self.depth), int(self.depth.shape[0]), self.H, self.W,
+                _lib.current_stream_handle(self.depth.device))
+        _lib.check(rc, "tacex_depth_from_mesh_library")
+        return self.depth
+
+    def fill(self, hm: torch.Tensor, frame_min: torch.Tensor, indent: torch.Tensor | None, gelpad_height: float,
+             gelpad_to_camera_min_distance: float):
+        """hm (B, H, W) mm, frame_min (B,), indent (B,) or None: the render above, then the depth -> height-map pass
+        (`tacex_height_map_from_depth` with this source's clipping range), both on the current stream."""
+        if tuple(hm.shape) != tuple(self.depth.shape):
+            raise RuntimeError(f"height map has shape {tuple(hm.shape)}, the source renders {tuple(self.depth.shape)}")
+        depth = self()
+        B, H, W = hm.shape
+        with torch.cuda.device(hm.device):
+            rc = self._lib.tacex_height_map_from_depth(
+                _lib.ptr(depth), self.near, self.far, float(gelpad_height), float(gelpad_to_camera_min_distance), _lib.ptr(hm),
+                _lib.ptr(frame_min), _lib.ptr(indent), 0, 0, B, H, W, _lib.current_stream_handle(hm.device))
+        _lib.check(rc, "tacex_height_map_from_depth")
+
+
 def contact_face_triangles(points, tets, optical_axis_w, min_cos: float = 0.5) -> np.ndarray:
     """(F,3) int32 boundary triangles of a tet mesh whose REST outward unit normal n has n . optical_axis_w > min_cos, wound along n.
     The outward side of a boundary face is the side away from the fourth vertex of its tet - not the winding of

@@ -300,6 +300,7 @@ class UipcSim:
         """Rigid triangle mesh for indenter kind 4 (one mesh per scene, shared by the envs; every env places it with its indenter row):
         vertices (Nv,3) in the mesh's own frame, triangles (Nt,3).  The barrier acts between every surface vertex of the gelpad and
         its nearest triangle (`tacex_fem_set_indenter_mesh`).  None removes it."""
+        self.indenter_meshes = self.indenter_mesh_ids = None  # (the C call drops a library and its id array)
         if vertices is None:
             _lib.check(self._lib.tacex_fem_set_indenter_mesh(self._handle, 0, 0, 0, 0), "tacex_fem_set_indenter_mesh")
             self.indenter_mesh = None
@@ -309,9 +310,65 @@ class UipcSim:
         _lib.check(self._lib.tacex_fem_set_indenter_mesh(self._handle, len(v), v.ctypes.data, len(t), t.ctypes.data), "tacex_fem_set_indenter_mesh")
         self.indenter_mesh = (v, t)
 
+    def set_indenter_meshes(self, meshes, mesh_ids=None):
+        """A LIBRARY of rigid triangle meshes for indenter kind 4, one chosen per env: `meshes` a list of (vertices (Nv,3), triangles
+        (Nt,3)) in each mesh's own frame, `mesh_ids` (num_envs,) ints (None: every env mesh 0).  Every env places ITS mesh with its
+        indenter row; an env sees exactly what `set_indenter_mesh(meshes[id])` would show it (`tacex_fem_set_indenter_mesh_library`).
+        `self.indenter_mesh_ids` is the (num_envs,) int32 device tensor the kernels read at every step: mutate it in place (or call
+        `set_indenter_mesh_ids`) to re-draw shapes, e.g. at a reset.  An id outside [0, len(meshes)) found on the device leaves that env
+        without an indenter for the step and flags it (`check_step()["bad_mesh_id_envs"]`).  None / [] removes the library."""
+        if not meshes:
+            self.set_indenter_mesh(None, None)
+            return
+        vs = [np.ascontiguousarray(v, np.float64).reshape(-1, 3) for v, _ in meshes]
+        ts = [np.ascontiguousarray(t, np.int32).reshape(-1, 3) for _, t in meshes]
+        for k, (v, t) in enumerate(zip(vs, ts)):
+            if len(v) < 3 or len(t) < 1 or t.min() < 0 or t.max() >= len(v):
+                raise ValueError(f"set_indenter_meshes: mesh {k} needs >= 3 vertices, >= 1 triangle and triangle indices in [0, {len(v)})")
+        ids = self._check_mesh_ids(mesh_ids, len(vs))
+        vc = np.array([len(v) for v in vs], np.int32)
+        tc = np.array([len(t) for t in ts], np.int32)
+        V, T = np.ascontiguousarray(np.concatenate(vs)), np.ascontiguousarray(np.concatenate(ts))
+        _lib.check(self._lib.tacex_fem_set_indenter_mesh_library(self._handle, len(vs), vc.ctypes.data, V.ctypes.data, tc.ctypes.data, T.ctypes.data),
+                   "tacex_fem_set_indenter_mesh_library")
+        self.indenter_mesh = None
+        self.indenter_meshes = list(zip(vs, ts))
+        self.indenter_mesh_ids = torch.from_numpy(ids).to(self.device)
+        _lib.check(self._lib.tacex_fem_set_indenter_mesh_ids(self._handle, _lib.ptr(self.indenter_mesh_ids)), "tacex_fem_set_indenter_mesh_ids")
+
+    def set_indenter_mesh_ids(self, mesh_ids):
+        """Writes new per-env mesh ids into `self.indenter_mesh_ids` (in stream order; checked on the host against the library)."""
+        if getattr(self, "indenter_meshes", None) is None:
+            raise RuntimeError("set_indenter_mesh_ids: no mesh library (set_indenter_meshes)")
+        ids = self._check_mesh_ids(mesh_ids, len(self.indenter_meshes))
+        self.indenter_mesh_ids.copy_(torch.from_numpy(ids))
+
+    def _check_mesh_ids(self, mesh_ids, num_meshes) -> np.ndarray:
+        if mesh_ids is None:
+            return np.zeros(self.num_envs, np.int32)
+        ids = mesh_ids.detach().cpu().numpy() if isinstance(mesh_ids, torch.Tensor) else np.asarray(mesh_ids)
+        ids = ids.reshape(-1)
+        if ids.shape != (self.num_envs,):
+            raise ValueError(f"mesh ids: need {self.num_envs} (one per env), got {ids.shape[0]}")
+        if not np.issubdtype(ids.dtype, np.integer) or (len(ids) and (ids.min() < 0 or ids.max() >= num_meshes)):
+            raise ValueError(f"mesh ids must be integers in [0, {num_meshes})")
+        return np.ascontiguousarray(ids, np.int32)
+
     def _mesh_gaps(self, x, ind):
-        """torch restatement of the kernel's point-triangle distance (diagnostic; triangles in chunks to bound the memory)."""
-        v, t = self.indenter_mesh
+        """torch restatement of the kernel's point-triangle distance (diagnostic; triangles in chunks to bound the memory).  With a
+        mesh library every env measures against its own mesh (an id outside the library: +inf, no indenter)."""
+        lib = getattr(self, "indenter_meshes", None)
+        if lib is None:
+            return self._mesh_gaps_one(x, ind, *self.indenter_mesh)
+        ids = self.indenter_mesh_ids.cpu().numpy()
+        out = torch.full(x.shape[:2], float("inf"), dtype=torch.float64, device=self.device)
+        for k, (v, t) in enumerate(lib):
+            sel = torch.from_numpy(np.nonzero(ids == k)[0]).to(self.device)
+            if len(sel):
+                out[sel] = self._mesh_gaps_one(x[sel], ind[sel], v, t)
+        return out
+
+    def _mesh_gaps_one(self, x, ind, v, t):
         vt = torch.from_numpy(v).to(self.device)
         r = ind[:, 5:8]
         th = r.norm(dim=-1).clamp_min(1e-300)
@@ -377,7 +434,8 @@ class UipcSim:
         t = (pl / aa).clamp(-1.0, 1.0)
         cap = (x - c - t[..., None] * n).norm(dim=-1) - ind[:, None, 4]
         inf = torch.full_like(sph, float("inf"))
-        msh = self._mesh_gaps(x, ind) if getattr(self, "indenter_mesh", None) is not None and bool((ind[:, 0] == 4).any()) else inf
+        has_mesh = getattr(self, "indenter_mesh", None) is not None or getattr(self, "indenter_meshes", None) is not None
+        msh = self._mesh_gaps(x, ind) if has_mesh and bool((ind[:, 0] == 4).any()) else inf
         return torch.where(kind == 1, sph, torch.where(kind == 2, pl, torch.where(kind == 3, cap, torch.where(kind == 4, msh, inf))))
 
     # -- animation targets (uipc_attachments.py:364-385) ----------------------------------------------------------
@@ -621,14 +679,15 @@ class UipcSim:
         Newton iteration started - the caller moved the indenter by more than the gap between two steps (`set_contact_indenters`
         documents the contract) and that vertex gets no restoring force; flag 2 = a line search found no decrease.  Informational:
         4 = the env dropped the coarse correction for the rest of the step, 8 = it met negative curvature and finished the step with
-        the PSD-safe Hessian (csrc/fem_kernels.hip, kFemFlagCoarseOff / kFemFlagPsdSafe)."""
+        the PSD-safe Hessian (csrc/fem_kernels.hip, kFemFlagCoarseOff / kFemFlagPsdSafe); 32 = its kind-4 row named a mesh id outside
+        the library (`set_indenter_meshes`): the env ran the step without an indenter ("bad_mesh_id_envs")."""
         self.wait_for_step()  # a step enqueued on a side stream (FemGelpad(side_stream=True)): `.cpu()` only drains the CURRENT stream
         si = self.step_info.cpu().numpy()
         flags = si[:, 2].astype(np.int64)
         out = {"newton_iters": si[:, 0].astype(np.int64), "max_d": si[:, 1], "penetrating_envs": np.nonzero(flags & 1)[0],
                "line_search_failed_envs": np.nonzero(flags & 2)[0], "pcg_iters": si[:, 3].astype(np.int64),
                "coarse_dropped_envs": np.nonzero(flags & 4)[0], "psd_safe_envs": np.nonzero(flags & 8)[0],
-               "pair_list_overflow_envs": np.nonzero(flags & 16)[0]}  # (affine-body scenes: a candidate list of csrc/fem_ball.h overflowed)
+               "pair_list_overflow_envs": np.nonzero(flags & 16)[0], "bad_mesh_id_envs": np.nonzero(flags & 32)[0]}  # (affine-body scenes: a candidate list of csrc/fem_ball.h overflowed)
         if raise_on_penetration and len(out["penetrating_envs"]):
             raise RuntimeError(f"gelpad penetrated by its indenter in envs {out['penetrating_envs'][:8].tolist()}: the indenter moved by "
                                "more than the contact gap between two steps (see UipcSim.set_contact_indenters)")
