@@ -32,7 +32,7 @@ extern "C" {
 #endif
 
 #define TACEX_MAX_LEVELS 8
-#define TACEX_ABI_VERSION 17
+#define TACEX_ABI_VERSION 18
 
 typedef struct tacex_taxim_ctx tacex_taxim_ctx;
 typedef struct tacex_fots_ctx tacex_fots_ctx;
@@ -438,6 +438,13 @@ int tacex_fem_set_friction_lag(tacex_fem_ctx* ctx, int mode);
  * 0 = the streaming fallback (larger meshes, the deterministic switch on more than 512 vertices), -1 = none yet.  (ABI 11) */
 int tacex_fem_newton_resident(const tacex_fem_ctx* ctx);
 
+/* The route of the last Newton launch of the context (tacex_fem_step, tacex_fem_newton_step, tacex_fem_ball_step) (ABI 18):
+ *   threads  = threads per env: 256, 512 or 768 for the CU-resident kernel, the block size of the streaming and ball kernels; 0 = none yet
+ *   lds_mode = -1 for the CU-resident and ball kernels; for the streaming kernel 2 = every PCG vector in LDS (21 V doubles),
+ *              1 = x, p and the H.p accumulators (9 V doubles), 0 = global memory (the deterministic switch, or neither fits).
+ * Every kernel's dynamic LDS must fit next to its static __shared__ in a CU's 160 KB; a pad that does not fit one route takes the next. */
+int tacex_fem_newton_route(const tacex_fem_ctx* ctx, int* threads, int* lds_mode);
+
 /* Contact-following start of tacex_fem_step's Newton loop (default on): a surface vertex inside the barrier zone of the indenter's
  * previous position starts the iteration displaced by the indenter's translation since the previous step (its gap is what it was).
  * An initial guess only - the step's minimiser is unchanged - but the one that lets a RETREATING indenter cost 2-3 Newton iterations
@@ -600,6 +607,13 @@ int tacex_fem_ball_step(tacex_fem_ctx* ctx, double* x_dev, double* v_dev, double
  * mode.  workspace_dev: the workspace tacex_fem_step runs with (nullable before the first step).  Enqueued on `stream`. */
 int tacex_fem_reset_envs(tacex_fem_ctx* ctx, const int32_t* env_ids_dev, int num_reset, const double* positions_dev, double* x_dev,
                          double* v_dev, double* step_info_dev, void* workspace_dev, int num_envs, void* stream);
+
+/* The affine body's part of a per-env reset (ABI 18): q[env] <- q0_dev (4,3) f64, qv[env] <- 0 for the listed envs (env_ids_dev NULL:
+ * all).  For a KINEMATIC body, the pose its next step measures the body's motion from (the end of the previous step, kept in
+ * ball_workspace_dev) becomes q0 as well, so friction sees no motion in that step, like the first step of a fresh scene; the other
+ * envs keep theirs.  Enqueued on `stream`. */
+int tacex_fem_ball_reset_envs(tacex_fem_ctx* ctx, const int32_t* env_ids_dev, int num_reset, const double* q0_dev, double* q_dev,
+                              double* qv_dev, void* ball_workspace_dev, int num_envs, void* stream);
 
 /* Attachment animation (UA:364-428: `_compute_aim_positions` + the animator callback `animate_tet` UA:365-385) for all envs:
  *   aim_position[b, idx[a]] = R(body_quat[b]) * offsets[a] + body_pos[b];  is_constrained[b, idx[a]] = 1

@@ -11,7 +11,7 @@ from pathlib import Path
 from ._build import LIB, build_library
 
 MAX_LEVELS = 8
-ABI_VERSION = 17  # TACEX_ABI_VERSION of include/tacex_hip.h; bumped whenever a signature or struct layout changes
+ABI_VERSION = 18  # TACEX_ABI_VERSION of include/tacex_hip.h; bumped whenever a signature or struct layout changes
 FLAG_NO_SHIFT = 1
 FLAG_HAVE_FRAME_MIN = 2
 FLAG_WITH_SHADOW = 4
@@ -145,6 +145,7 @@ SIGNATURES = {
     "tacex_fem_set_indenter_mesh_ids": (_i, [_vp, _vp]),
     "tacex_fem_contact_gaps": (_i, [_vp, _vp, _vp, _i, _vp]),
     "tacex_fem_newton_resident": (_i, [_vp]),
+    "tacex_fem_newton_route": (_i, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "tacex_fem_set_friction_lag": (_i, [_vp, _i]),
     "tacex_fem_set_affine_body": (_i, [_vp, _i, _vp, _i, _vp, _d, _d, _vp, _i, _vp, _d, _d, _d, _i, _i]),
     "tacex_fem_ball_workspace_bytes": (_sz, [_vp, _i]),
@@ -154,6 +155,7 @@ SIGNATURES = {
     "tacex_fem_ball_terms": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
     "tacex_fem_ball_step": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, C.POINTER(C.c_double), _i, _d, _d, _i, _d, _i, _vp]),
     "tacex_fem_reset_envs": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
+    "tacex_fem_ball_reset_envs": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp]),
     "tacex_fem_set_friction": (_i, [_vp, _d, _d]),
     "tacex_fem_set_contact_following": (_i, [_vp, _i]),
     "tacex_fem_set_deterministic": (_i, [_vp, _i]),

@@ -1134,7 +1134,7 @@ __global__ __launch_bounds__(NT_, NT_ >= 512 ? TACEX_BALL_WG_PER_CU : 1) void fe
     //      the pair records are what it reads from memory ----
     for (int k = tid; k < 3 * V; k += NT) acc[k] = 0.0;  // (xs holds x since the kernel's start / the last accepted step)
     __syncthreads();
-    constexpr int VS = 1024 / NT;  // vertices per thread (V <= 780: ball_lds_ok)
+    constexpr int VS = 1024 / NT;  // vertices per thread (V <= 697: ball_lds_ok)
     double md_r[VS], cb_r[VS];  // this thread's vertices: mass (+ constraint) diagonal and ground curvature, constant through the PCG loop
 #pragma unroll
     for (int sl = 0; sl < VS; ++sl) {

@@ -2550,6 +2550,8 @@ struct tacex_fem_ctx {
   int ind_prev_B = 0;
   const double* rest = nullptr;  // (V,3) rest positions (tacex_fem_reset_envs)
   int last_resident = -1;       // which Newton kernel the last launch used: 1 CU-resident, 0 streaming, -1 none yet (tacex_fem_newton_resident)
+  int last_threads = 0;         // block size of the last Newton launch (tacex_fem_newton_route), 0 = none yet
+  int last_lds_mode = -1;       // its streaming-kernel LDS mode (2, 1, 0), -1 for the CU-resident and ball kernels
   int ls_refine = 4;            // bisections after a cut line search in fem_ball_newton_kernel (tacex_fem_set_line_search_refine)
   int fric_lag_mode = 0;        // 0: lag at the step's start state, capped by the contact reaction (round 4); 1: IPC's previous-configuration lag
   bool deterministic = false;   // window + CSR-gather sweeps (fixed summation order) instead of LDS atomics (tacex_fem_set_deterministic)
@@ -2873,6 +2875,13 @@ int tacex_fem_set_friction_lag(tacex_fem_ctx* c, int mode) {
 
 int tacex_fem_newton_resident(const tacex_fem_ctx* c) { return c ? c->last_resident : -1; }
 
+int tacex_fem_newton_route(const tacex_fem_ctx* c, int* threads, int* lds_mode) {
+  if (!c || !threads || !lds_mode) { set_error("tacex_fem_newton_route: null argument"); return 2; }
+  *threads = c->last_threads;
+  *lds_mode = c->last_lds_mode;
+  return 0;
+}
+
 // One mesh's tables for the library: triangles in Morton order of their centroids (10 bits per axis over the mesh's bounding box),
 // 16 consecutive ones form a cluster.  Appended to tri / bs / cl: a mesh's slice is the same whatever else the library holds.
 static int pack_indenter_mesh(const char* who, int num_verts, const double* verts_host, int num_tris, const int32_t* tris_host,
@@ -3157,13 +3166,12 @@ static int launch_newton(tacex_fem_ctx* c, double* x, const double* xt, const ui
   static const int nt256 = getenv("TACEX_FEM_NT256") ? atoi(getenv("TACEX_FEM_NT256")) : 1;
   const int nt = (nt256 && V <= 256 && atom && !mesh) ? 256 : (V <= 512 ? 512 : 768);
   const size_t lds = nwt_lds_bytes(V, c->dev.T, fric, nt);
-  if (use_lds && V <= 768 && (nt <= 512 ? 4 * c->dev.T < 65535 : (atom && !mesh)) && lds <= 160 * 1024) {
-    if (resident) *resident = true;
-    c->last_resident = 1;
-    static size_t granted[6][64] = {};  // per kernel instantiation and device: the attribute is per kernel AND device
-    using kern_t = decltype(&fem_newton_lds_kernel<false, true, 512>);
-    kern_t kern;
-    int slot;
+  hipError_t ea = hipSetDevice(c->device);  // (the LDS limits and opt-ins below are per device)
+  if (ea != hipSuccess) return fail_hip(ea, "hipSetDevice");
+  using kern_t = decltype(&fem_newton_lds_kernel<false, true, 512>);
+  kern_t kern = nullptr;
+  int slot = 0;
+  if (use_lds && V <= 768 && (nt <= 512 ? 4 * c->dev.T < 65535 : (atom && !mesh))) {
     if (nt == 256) {
       kern = fem_newton_lds_kernel<false, true, 256>;
       slot = 5;
@@ -3175,8 +3183,20 @@ static int launch_newton(tacex_fem_ctx* c, double* x, const double* xt, const ui
       kern = fem_newton_lds_kernel<false, true, 768>;
       slot = 4;
     }
-    hipError_t ea = hipSetDevice(c->device);
-    if (ea == hipSuccess) ea = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), lds, granted[slot]);
+    // the env's state must fit next to the kernel's static __shared__; a pad that does not (e.g. 750 vertices on 768 threads) streams
+    static size_t avail[6][64] = {};
+    size_t limit = 0;
+    ea = dynamic_lds_limit(reinterpret_cast<const void*>(kern), avail[slot], &limit);
+    if (ea != hipSuccess) return fail_hip(ea, "hipFuncGetAttributes(fem_newton_lds_kernel)");
+    if (lds > limit) kern = nullptr;
+  }
+  if (kern) {
+    if (resident) *resident = true;
+    c->last_resident = 1;
+    c->last_threads = nt;
+    c->last_lds_mode = -1;
+    static size_t granted[6][64] = {};  // per kernel instantiation and device: the attribute is per kernel AND device
+    ea = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), lds, granted[slot]);
     if (ea != hipSuccess) return fail_hip(ea, "hipFuncSetAttribute(fem_newton_lds_kernel)");
     // elastic preconditioner blocks of all envs at the state this launch starts from -> workspace ((V,16) per env)
     if (int rc = launch_assemble(c, x, ws, B, dx_dev, dx_tol, st, atom)) return rc;
@@ -3190,17 +3210,23 @@ static int launch_newton(tacex_fem_ctx* c, double* x, const double* xt, const ui
   }
   if (resident) *resident = false;
   c->last_resident = 0;
-  // x, p and the H.p accumulators in LDS when the summation order is free (atomic mode) and they fit (9 V doubles: ~2 200 vertices)
+  // x, p and the H.p accumulators in LDS when the summation order is free (atomic mode) and they fit next to the kernel's static
+  // __shared__ (9 V doubles: ~2 200 vertices); all PCG vectors when 21 V doubles fit (~950 vertices); else global memory
   static const int stream_lds = getenv("TACEX_FEM_STREAM_LDS") ? atoi(getenv("TACEX_FEM_STREAM_LDS")) : 2;  // A/B hook: 0 none, 1 x / p / accumulators, 2 all PCG vectors
-  const bool lds_all = stream_lds != 1 && (size_t)21 * V * sizeof(double) <= 160 * 1024;  // (TACEX_FEM_STREAM_LDS=1: x, p, accumulators only)
+  static size_t avail_s[64] = {};
+  size_t limit_s = 0;
+  ea = dynamic_lds_limit(reinterpret_cast<const void*>(fem_newton_kernel), avail_s, &limit_s);
+  if (ea != hipSuccess) return fail_hip(ea, "hipFuncGetAttributes(fem_newton_kernel)");
+  const bool lds_all = stream_lds != 1 && (size_t)21 * V * sizeof(double) <= limit_s;  // (TACEX_FEM_STREAM_LDS=1: x, p, accumulators only)
   const size_t lds_s = (size_t)(lds_all ? 21 : 9) * V * sizeof(double);
-  const bool lds_sweep = stream_lds != 0 && atom && lds_s <= 160 * 1024;
+  const bool lds_sweep = stream_lds != 0 && atom && lds_s <= limit_s;
   if (lds_sweep) {
     static size_t granted_s[64] = {};
-    hipError_t es = hipSetDevice(c->device);
-    if (es == hipSuccess) es = ensure_dynamic_lds(reinterpret_cast<const void*>(fem_newton_kernel), lds_s, granted_s);
+    const hipError_t es = ensure_dynamic_lds(reinterpret_cast<const void*>(fem_newton_kernel), lds_s, granted_s);
     if (es != hipSuccess) return fail_hip(es, "hipFuncSetAttribute(fem_newton_kernel)");
   }
+  c->last_threads = 512;
+  c->last_lds_mode = lds_sweep ? (lds_all ? 2 : 1) : 0;
   hipLaunchKernelGGL(fem_newton_kernel, dim3(B), dim3(512), lds_sweep ? lds_s : 0, st, c->dev, x, xt, cons, aim, stats, static_cast<double*>(ws), pcg_max_iter,
                      pcg_tol_rate, ls_max_iter, dx_dev, dx_tol, step_info, stream_accumulate ? 1 : 0, fric ? xprev : nullptr, fric ? disp : nullptr,
                      c->fric_lag_mode == 1 ? 1 : 0, lds_sweep ? (lds_all ? 2 : 1) : 0);
@@ -3378,14 +3404,23 @@ static int ball_threads() {
   return nt == 256 ? 256 : 512;
 }
 
+// The ball kernel has no smaller LDS mode: a pad whose state does not fit next to the kernel's static __shared__ (18.8 KB at 512 threads:
+// up to 696 vertices; 697 at 256 threads) is refused with this message before anything is launched.
 static int ball_lds_ok(tacex_fem_ctx* c, const char* who) {
   const size_t lds = ball_lds_bytes(c->dev.V);
-  if (lds > 160 * 1024) { set_error("%s: pad of %d vertices (x, p, accumulators and chain factors of one env must fit a CU's 160 KB of LDS)", who, c->dev.V); return 2; }
-  static size_t granted[2][64] = {};
+  const int k = ball_threads() == 256 ? 0 : 1;
+  const void* kern = k == 0 ? reinterpret_cast<const void*>(fem_ball_newton_kernel<256>) : reinterpret_cast<const void*>(fem_ball_newton_kernel<512>);
+  static size_t avail[2][64] = {}, granted[2][64] = {};
   hipError_t e = hipSetDevice(c->device);
-  if (e == hipSuccess)
-    e = ball_threads() == 256 ? ensure_dynamic_lds(reinterpret_cast<const void*>(fem_ball_newton_kernel<256>), lds, granted[0])
-                              : ensure_dynamic_lds(reinterpret_cast<const void*>(fem_ball_newton_kernel<512>), lds, granted[1]);
+  size_t limit = 0;
+  if (e == hipSuccess) e = dynamic_lds_limit(kern, avail[k], &limit);
+  if (e != hipSuccess) return fail_hip(e, "hipFuncGetAttributes(fem_ball_newton_kernel)");
+  if (lds > limit) {
+    set_error("%s: pad of %d vertices (x, p, accumulators and chain factors of one env must fit a CU's 160 KB of LDS: %zu B next to the kernel's "
+              "%zu B of static LDS)", who, c->dev.V, lds, (size_t)160 * 1024 - limit);
+    return 2;
+  }
+  e = ensure_dynamic_lds(kern, lds, granted[k]);
   return e == hipSuccess ? 0 : fail_hip(e, "hipFuncSetAttribute(fem_ball_newton_kernel)");
 }
 
@@ -3412,6 +3447,12 @@ int tacex_fem_ball_terms(tacex_fem_ctx* c, const double* x, const double* xt, co
   return e == hipSuccess ? 0 : fail_hip(e, "fem_ball_newton_kernel(terms)");
 }
 
+// the (B,12) rows "q at the end of the previous step" of a ball workspace (see tacex_fem_ball_step)
+static double* ball_qlast(const tacex_fem_ctx* c, void* ws, int B) {
+  const size_t n3 = (size_t)B * c->dev.V * 3;
+  return static_cast<double*>(ws) + (size_t)B * ball_ws_doubles(c->dev.V, c->dev.T, c->ball.nv, c->ball.nt) + 2 * n3 + (size_t)B * 24;
+}
+
 int tacex_fem_ball_step(tacex_fem_ctx* c, double* x, double* v, double* q, double* qv, const uint8_t* cons, const double* aim, double* step_info,
                         void* ws, int B, const double gravity[3], int max_newton, double velocity_tol, double transrate_tol, int pcg_max_iter,
                         double pcg_tol_rate, int ls_max_iter, void* stream) {
@@ -3422,6 +3463,9 @@ int tacex_fem_ball_step(tacex_fem_ctx* c, double* x, double* v, double* q, doubl
     return 2;
   }
   if (B <= 0) return 0;
+  if (int rc = ball_lds_ok(c, "tacex_fem_ball_step")) return rc;  // (before the predictors: a refused step leaves x, v, q and qv as they were)
+  c->last_threads = ball_threads();
+  c->last_lds_mode = -1;
   static const int ball_coarse_off = getenv("TACEX_BALL_COARSE") ? (atoi(getenv("TACEX_BALL_COARSE")) == 0) : 0;  // A/B hook: block Jacobi alone on the pad rows
   hipStream_t st = (hipStream_t)stream;
   const int V = c->dev.V;
@@ -3432,7 +3476,7 @@ int tacex_fem_ball_step(tacex_fem_ctx* c, double* x, double* v, double* q, doubl
   double* qt = xt + n3;
   // A KINEMATIC body is moved by the caller between steps: friction then slides relative to where the body stood at the END of the previous
   // step (kept here; the first step with this workspace sees no body motion), like the analytic indenters' displacement in tacex_fem_step
-  double* qlast = qt + (size_t)B * 12;
+  double* qlast = ball_qlast(c, ws, B);
   const bool have_last = c->ball.kinematic && c->ball_last_ws == ws && c->ball_last_B == B;
   const double dt = c->dev.dt;
   hipLaunchKernelGGL(fem_predict_kernel, dim3((unsigned)((n3 + 255) / 256)), dim3(256), 0, st, x, v, xt, xprev, static_cast<double*>(nullptr), n3, B, dt,
@@ -3445,7 +3489,6 @@ int tacex_fem_ball_step(tacex_fem_ctx* c, double* x, double* v, double* q, doubl
     env_order = reinterpret_cast<int*>(qlast + (size_t)B * 12 + 1);
     hipLaunchKernelGGL(fem_env_order_kernel, dim3(1), dim3(1024), 0, st, step_info, B, env_order);
   }
-  if (int rc = ball_lds_ok(c, "tacex_fem_ball_step")) return rc;
   // elastic preconditioner blocks D | E of every env at the state the step starts from (what fem_newton_lds_kernel's launch does too)
   double* blk = reinterpret_cast<double*>(reinterpret_cast<char*>(qlast + (size_t)B * 12) + (((size_t)B + 1) / 2 + 2) * sizeof(double));
   {
@@ -3489,6 +3532,24 @@ int tacex_fem_reset_envs(tacex_fem_ctx* c, const int32_t* env_ids, int num_reset
                      ind_prev, V, B);
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? 0 : fail_hip(e, "fem_reset_envs_kernel");
+}
+
+int tacex_fem_ball_reset_envs(tacex_fem_ctx* c, const int32_t* env_ids, int num_reset, const double* q0, double* q, double* qv, void* ws, int B,
+                              void* stream) {
+  if (!c || !q0 || !q || !qv) { set_error("tacex_fem_ball_reset_envs: null argument"); return 2; }
+  if (c->ball.nv == 0) { set_error("tacex_fem_ball_reset_envs: no affine body (tacex_fem_set_affine_body)"); return 2; }
+  if (B <= 0 || num_reset == 0) return 0;
+  if (num_reset < 0 || (!env_ids && num_reset != B)) { set_error("tacex_fem_ball_reset_envs: without env_ids, num_reset must equal num_envs"); return 2; }
+  // q and qv are (B,4,3): the pad's reset kernel with V = 4 and q0 as the rest positions
+  hipLaunchKernelGGL(fem_reset_envs_kernel, dim3(num_reset), dim3(256), 0, (hipStream_t)stream, env_ids, static_cast<const double*>(nullptr), q0, q, qv,
+                     static_cast<double*>(nullptr), static_cast<double*>(nullptr), 4, B);
+  // a kinematic body's friction reference: the next step measures the body's motion from q0, not from where it stood before the reset
+  // (the rows of the other envs stay valid)
+  if (c->ball.kinematic && ws && c->ball_last_ws == ws && c->ball_last_B == B)
+    hipLaunchKernelGGL(fem_reset_envs_kernel, dim3(num_reset), dim3(256), 0, (hipStream_t)stream, env_ids, static_cast<const double*>(nullptr), q0,
+                       ball_qlast(c, ws, B), qv, static_cast<double*>(nullptr), static_cast<double*>(nullptr), 4, B);  // (qv: zeroed again)
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? 0 : fail_hip(e, "fem_reset_envs_kernel(ball)");
 }
 
 int tacex_fem_set_attachment_targets(const float* body_pos, const float* body_quat, const float* offsets, const int32_t* idx,

@@ -181,6 +181,22 @@ inline hipError_t ensure_dynamic_lds(const void* kern, size_t lds, size_t (&gran
   return e;
 }
 
+// The dynamic LDS one workgroup of `kern` can get on the current device: a CU's 160 KB less the kernel's static __shared__
+// (hipFuncGetAttributes' sharedSizeBytes).  `avail` is the per-kernel table (a function-local static at the call site, like
+// `granted` above) that caches it per device; 0 = not read yet.
+inline hipError_t dynamic_lds_limit(const void* kern, size_t (&avail)[64], size_t* limit) {
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
+  if (!avail[dev]) {
+    hipFuncAttributes a{};
+    const hipError_t e = hipFuncGetAttributes(&a, kern);
+    if (e != hipSuccess) return e;
+    avail[dev] = a.sharedSizeBytes < 160 * 1024 ? 160 * 1024 - a.sharedSizeBytes : 1;  // (1: nothing fits, and the table stays filled)
+  }
+  *limit = avail[dev];
+  return hipSuccess;
+}
+
 // thread-local error string (tacex_last_error)
 void set_error(const char* fmt, ...);
 int fail_hip(hipError_t e, const char* what);

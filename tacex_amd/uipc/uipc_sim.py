@@ -500,10 +500,11 @@ class UipcSim:
             rc = self._lib.tacex_fem_reset_envs(self._handle, _lib.ptr(ids), n, _lib.ptr(pos), _lib.ptr(self.x), _lib.ptr(self.v),
                                                 _lib.ptr(si), _lib.ptr(self._ws), B, self._stream())
         _lib.check(rc, "tacex_fem_reset_envs")
-        if self._body is not None:  # the env's free affine body goes back to where the scene placed it, at rest
-            rows = slice(None) if ids is None else ids.long()
-            self.q[rows] = self._q0
-            self.qv[rows] = 0.0
+        if self._body is not None:  # the env's affine body goes back to where the scene placed it, at rest (a kinematic one: its friction reference too)
+            with torch.cuda.device(self.device):
+                rc = self._lib.tacex_fem_ball_reset_envs(self._handle, _lib.ptr(ids), n, _lib.ptr(self._q0), _lib.ptr(self.q), _lib.ptr(self.qv),
+                                                         _lib.ptr(self._ball_ws), B, self._stream())
+            _lib.check(rc, "tacex_fem_ball_reset_envs")
         # (a later side-stream step is ordered behind this: FemGelpad.step makes its stream wait for the caller's before every step)
 
     def refresh_preconditioner(self):
@@ -666,6 +667,15 @@ class UipcSim:
         streaming fallback (meshes whose state does not fit a CU's LDS, the deterministic switch on more than 512 vertices), None = no step yet."""
         r = int(self._lib.tacex_fem_newton_resident(self._handle))
         return None if r < 0 else bool(r)
+
+    @property
+    def newton_route(self) -> tuple[int, int] | None:
+        """(threads, lds_mode) of the last Newton launch (`tacex_fem_newton_route`): threads per env - 256, 512 or 768 for the CU-resident
+        kernel, the block size of the streaming and ball kernels - and lds_mode -1 for the CU-resident and ball kernels, 2 / 1 / 0 for the
+        streaming kernel (every PCG vector / x, p and the accumulators / nothing in LDS).  None = no step yet."""
+        threads, mode = C.c_int(0), C.c_int(0)
+        _lib.check(self._lib.tacex_fem_newton_route(self._handle, C.byref(threads), C.byref(mode)), "tacex_fem_newton_route")
+        return None if threads.value == 0 else (threads.value, mode.value)
 
     @property
     def last_newton_iters(self) -> int:
