@@ -13,9 +13,12 @@ height map + indentation depth -> Taxim RGB -> FOTS markers, then the low-resolu
 (2 x 32x32x3 uint8 + markers + indentation) is packed and collected with ONE all-gather (RCCL over xGMI when N > 1).
 Weak scaling: every GPU holds 1024 envs.
 
-At N = 1 the same process then times the other BASELINE configurations as `config.sweep[]` (not the headline value):
-C2 (256 envs x 1 sensor), the 512-env shard of the 4096-env headline target, C4's per-GPU shard (512 envs RGB + markers +
-the gelpad FEM step on a ~2k-tet mesh) and C5's per-GPU shard (1024 envs at 640x480 + FEM-driven markers).
+A plain run times the headline alone: set-up, warm-up, the timed steps, `--dump-outputs` if given, the line.  With `--full`
+the same process then measures everything else (not the headline value): the per-stage roofline leg, the 4096-env whole-node
+leg, at N > 1 the headline without the observation gather, and at N = 1 the other BASELINE configurations as
+`config.sweep[]` - C2 (256 envs x 1 sensor), the 512-env shard of the 4096-env headline target, C4's per-GPU shard (512 envs
+RGB + markers + the gelpad FEM step on a ~2k-tet mesh) and C5's per-GPU shard (1024 envs at 640x480 + FEM-driven markers) -
+and the CPU baseline.  `--no-roofline` / `--no-node-leg` / `--no-sweep` / `--no-cpu-baseline` drop single legs of a full run.
 Prints ONE JSON line on rank 0.
 """
 from __future__ import annotations
@@ -71,6 +74,9 @@ def parse(argv=None):
                          "overlap rocprofv3 reports 1084 us for a tail launch that takes 762 us alone)")
     ap.add_argument("--no-group", action="store_true",
                     help="update the sensors of an env one by one (two launch sequences per step) instead of as one GelSightSensorGroup")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, measure everything else: roofline leg, 4096-env node leg, sweep of the other configurations, "
+                         "CPU baseline, and at N > 1 the headline without the gather (a plain run times the headline alone)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--no-node-leg", action="store_true", help="skip the 4096-env whole-node leg (value_node4096*)")
@@ -972,7 +978,7 @@ def dry_run_rank(args):
     full["data"] = "dry-run"
     if multi is not None:
         full["multi_gpu"] = multi
-    if not args.no_node_leg:
+    if args.full and not args.no_node_leg:
         full["node4096"] = node4096_leg(args, shard, "cpu", use_dist, (lambda: dist.barrier()) if use_dist else (lambda: None), dry=True)
     if use_dist:
         dist.barrier()
@@ -1187,7 +1193,7 @@ def main(argv=None):
     value = frames_per_step * args.steps / elapsed
     # the same job without the observation collection (frames/s with AND without the gather), N > 1 only: at N = 1
     # the sweep carries the `--gather none` entry
-    if use_dist and args.gather != "none" and args.gpus > 1:
+    if args.full and use_dist and args.gather != "none" and args.gpus > 1:
         rig2 = Rig(B, H, W, args.sensors, markers, dev, shard.world_size, seed=1 + shard.rank, gather="none", obs_dtype=args.obs_dtype,
                    sensor_streams=args.sensor_streams, group=not args.no_group)
         e2 = rig2.timed(max(5, args.steps // 4), 2, barrier)
@@ -1199,7 +1205,7 @@ def main(argv=None):
         torch.cuda.empty_cache()
 
     roofline = None
-    if not args.no_roofline and shard.rank == 0:
+    if args.full and not args.no_roofline and shard.rank == 0:
         roofline = roofline_leg(rig, markers)
     obs_bytes = None if rig.obs is None else rig.obs.payload_bytes()
     sensor_streams_on = bool(rig.streams)
@@ -1208,7 +1214,7 @@ def main(argv=None):
     torch.cuda.empty_cache()
 
     node = None
-    if not args.no_node_leg:
+    if args.full and not args.no_node_leg:
         try:
             node = node4096_leg(args, shard, dev, use_dist, barrier)
         except Exception as ex:
@@ -1217,11 +1223,11 @@ def main(argv=None):
             node = {"error": f"{type(ex).__name__}: {ex}"[:300]}
 
     sw = None
-    if args.gpus == 1 and not args.no_sweep and shard.rank == 0 and not use_dist:
+    if args.full and args.gpus == 1 and not args.no_sweep and shard.rank == 0 and not use_dist:
         sw = sweep(args, dev)
 
     cpu = None
-    if not args.no_cpu_baseline and shard.rank == 0 and args.gpus == 1:
+    if args.full and not args.no_cpu_baseline and shard.rank == 0 and args.gpus == 1:
         log("cpu baseline leg")
         cpu = cpu_baseline(args.cpu_baseline_seconds)
     log("done")

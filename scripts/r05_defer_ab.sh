@@ -4,7 +4,7 @@ OUT=$GRAFT_REPO_ROOT/gpurun_out/${1:-r05defer}; mkdir -p $OUT; cd $GRAFT_REPO_RO
 timeout 1200 python -m pytest tests/test_sensor_gpu.py tests/test_taxim_gpu.py tests/test_edge_cases_gpu.py tests/test_sensor_configs_gpu.py -x -q -m gpu 2>&1 | tail -3 | tee $OUT/test.log
 run() { # label, env...
   lab=$1; shift
-  env "$@" timeout 600 python bench.py --no-sweep --no-cpu-baseline --steps 40 --details-out $OUT/d.json 2>$OUT/err.log | python -c "
+  env "$@" timeout 600 python bench.py --full --no-sweep --no-cpu-baseline --steps 40 --details-out $OUT/d.json 2>$OUT/err.log | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); det=json.load(open('$OUT/d.json'))
 print('[$lab] C3', d['value'], d['ms_per_step'], {k: round(v['avg_ms']*1e3,1) for k, v in det['roofline']['stages'].items()})" | tee -a $OUT/ab.log

@@ -5,5 +5,5 @@ timeout 1500 python -m pytest tests/test_fem_gpu.py tests/test_fem_physics_gpu.p
 for rep in 1 2; do for tag in sepe0 _; do t=$tag; [ "$tag" = "_" ] && t=""
 echo "[$tag] rep $rep" | tee -a $OUT/ab.log
 TACEX_LIB_TAG=$t TACEX_LIB_FROZEN=1 timeout 300 python scripts/fem_bench.py 2>&1 | grep "FemGelpad scene" | tee -a $OUT/ab.log
-TACEX_LIB_TAG=$t TACEX_LIB_FROZEN=1 timeout 600 python bench.py --no-cpu-baseline --steps 10 --sweep-keys c4,c4_one_stream,c4_rolling,c5,axle --details-out $OUT/d2.json > /dev/null 2>$OUT/err2.log; python scripts/print_sweep.py $OUT/d2.json | grep -v headline | cut -c1-150 | tee -a $OUT/ab.log
+TACEX_LIB_TAG=$t TACEX_LIB_FROZEN=1 timeout 600 python bench.py --full --no-cpu-baseline --steps 10 --sweep-keys c4,c4_one_stream,c4_rolling,c5,axle --details-out $OUT/d2.json > /dev/null 2>$OUT/err2.log; python scripts/print_sweep.py $OUT/d2.json | grep -v headline | cut -c1-150 | tee -a $OUT/ab.log
 done; done

@@ -9,5 +9,4 @@ PYTHONPATH=. timeout 300 python scripts/r06/ball_probe.py 512 > gpurun_out/r06_e
 tail -4 gpurun_out/r06_e_probe_ee.log
 TACEX_BALL_EDGE_EDGE=0 PYTHONPATH=. timeout 300 python scripts/r06/ball_probe.py 512 > gpurun_out/r06_e_probe_noee.log 2>&1
 tail -4 gpurun_out/r06_e_probe_noee.log
-timeout 900 python bench.py --no-node-leg --no-cpu-baseline --sweep-keys c4_ball > gpurun_out/r06_e_bench.log 2>&1 || true
-tail -2 gpurun_out/r06_e_bench.log | cut -c1-600
+timeout 900 python bench.py --full --no-node-leg --no-cpu-baseline --sweep-keys c4_ball 2>&1 | tail -2 | cut -c1-600

@@ -14,7 +14,6 @@ L=[l for l in open('gpurun_out/r06_n_probe.log')]
 ms=[float(l.split()[2]) for l in L]; nw=[float(l.split('newton mean')[1].split()[0]) for l in L]; mx=[int(l.split('max')[1].split()[0]) for l in L]; pc=[float(l.split('pcg/newton')[1].split()[0]) for l in L]
 print(f"NT={os.environ['TACEX_BALL_NT']} probe steps 6-29: ms mean {np.mean(ms[6:]):.2f} (max {np.max(ms[6:]):.2f}); newton mean {np.mean(nw[6:]):.2f}, worst env {max(mx[6:])}; pcg/newton {np.mean(pc[6:]):.1f}")
 PY
-  timeout 900 python bench.py --no-node-leg --no-cpu-baseline --no-roofline --sweep-keys c4_ball,c4_ball4096 --details-out gpurun_out/r06_n_details.json > gpurun_out/r06_n_bench.log 2>&1 || true
-  echo "NT=$nt $(tail -1 gpurun_out/r06_n_bench.log | grep -o '"value_c4_ball[^,]*,"value_c4_ball4096[^,]*')"
+  echo "NT=$nt $(timeout 900 python bench.py --full --no-node-leg --no-cpu-baseline --no-roofline --sweep-keys c4_ball,c4_ball4096 2>/dev/null | grep -o '"value_c4_ball[^,]*,"value_c4_ball4096[^,]*')"
 done
 rm -f gpurun_out/r06_n_tests_done

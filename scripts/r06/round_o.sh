@@ -14,5 +14,4 @@ print(f"refine={os.environ['TACEX_BALL_LS_REFINE']} probe steps 6-29: ms mean {n
 PY
 done
 unset TACEX_BALL_LS_REFINE
-timeout 900 python bench.py --no-node-leg --no-cpu-baseline --no-roofline --sweep-keys c4_ball,c4_ball4096 > gpurun_out/r06_o_bench.log 2>&1 || true
-echo "default cfg: $(tail -1 gpurun_out/r06_o_bench.log | grep -o '"value_c4_ball[^,]*,"value_c4_ball4096[^,]*')"
+echo "default cfg: $(timeout 900 python bench.py --full --no-node-leg --no-cpu-baseline --no-roofline --sweep-keys c4_ball,c4_ball4096 2>/dev/null | grep -o '"value_c4_ball[^,]*,"value_c4_ball4096[^,]*')"

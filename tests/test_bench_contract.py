@@ -5,6 +5,8 @@ import csv
 import json
 from pathlib import Path
 
+import pytest
+
 REPO = Path(__file__).resolve().parent.parent
 
 
@@ -190,3 +192,51 @@ def test_dump_outputs_is_a_fixed_sample_within_budget(tmp_path):
     assert all(np.array_equal(np.load(tmp_path / "b" / f"{n}.npy"), a) for n, a in files.items())
     bench.dump_outputs(rig, tmp_path / "c")
     np.testing.assert_array_equal(np.load(tmp_path / "c" / "frame_index.npy"), np.arange(B))
+
+
+# what only `--full` measures: none of it may appear on (or delay) a plain run's line
+_FULL_ONLY = ("roofline", "cpu_baseline", "value_node4096", "value_node4096_fem", "strong_scaling_base", "sweep_errors")
+
+
+def _bench_line(args, tmp_path, timeout):
+    import os
+    import subprocess
+    import sys
+
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    det = tmp_path / f"details_{len(list(tmp_path.iterdir()))}.json"
+    r = subprocess.run([sys.executable, str(REPO / "bench.py"), *args, "--details-out", str(det)], env=env, capture_output=True, text=True,
+                       timeout=timeout)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = r.stdout.strip().splitlines()
+    assert len(lines) == 1, r.stdout[-2000:]
+    return json.loads(lines[0]), json.loads(det.read_text())
+
+
+def test_plain_run_times_the_headline_alone_and_full_adds_the_rest(tmp_path):
+    """`bench.py --gpus N --steps K --warmup W` does only what its headline needs; everything else waits for `--full` (--cpu-dry-run:
+    the same gating around a stand-in step, where the whole-node leg is the one extra leg that runs without a GPU)."""
+    bench = _load_bench()
+    args = ["--gpus", "1", "--steps", "3", "--warmup", "1", "--cpu-dry-run"]
+    plain, det = _bench_line(args, tmp_path, 300)
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in plain, k
+    assert plain["steps"] == 3 and plain["warmup"] == 1
+    for k in _FULL_ONLY + tuple(bench._SWEEP_SCALARS.values()):
+        assert k not in plain, k
+    assert "node4096" not in det and "sweep" not in det["config"]
+    full, det = _bench_line(args + ["--full"], tmp_path, 300)
+    assert full["value_node4096"] > 0 and full["value_node4096_fem"] > 0 and det["node4096"]["envs_total"] == bench.NODE_ENVS
+    assert not bench.parse([]).full
+
+
+@pytest.mark.gpu
+def test_plain_run_on_the_gpu_box_measures_the_headline_only(tmp_path):
+    """A plain run on real hardware: the headline line, no roofline / node / sweep / CPU-baseline leg behind it."""
+    bench = _load_bench()
+    d, det = _bench_line(["--gpus", "1", "--steps", "3", "--warmup", "1", "--envs-per-gpu", "64"], tmp_path, 600)
+    assert d["n_gpus"] == 1 and d["data"] == "synthetic" and d["value"] > 0 and d["config"]["frames_per_step"] == 64 * 2
+    assert abs(d["value"] - d["config"]["frames_per_step"] / (d["ms_per_step"] * 1e-3)) <= 1e-3 * d["value"]
+    for k in _FULL_ONLY + tuple(bench._SWEEP_SCALARS.values()):
+        assert k not in d, k
+    assert not ({"roofline", "cpu_baseline", "node4096"} & set(det)) and "sweep" not in det["config"]

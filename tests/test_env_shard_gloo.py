@@ -67,7 +67,7 @@ def test_bench_gpus_2_starts_its_own_ranks_and_prints_one_compact_line(tmp_path)
 
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     det = tmp_path / "details.json"
-    r = subprocess.run([sys.executable, str(REPO / "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1", "--cpu-dry-run",
+    r = subprocess.run([sys.executable, str(REPO / "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1", "--cpu-dry-run", "--full",
                         "--details-out", str(det)], env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = r.stdout.strip().splitlines()
@@ -163,8 +163,8 @@ def test_bench_self_launch_with_rccl_on_the_gpu_box(tmp_path):
 
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(TACEX_BENCH_FORCE_LAUNCH="1", TACEX_FORCE_DIST="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
-    r = subprocess.run([sys.executable, str(REPO / "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--envs-per-gpu", "64", "--no-sweep",
-                        "--no-cpu-baseline", "--details-out", str(tmp_path / "d.json")], env=env, capture_output=True, text=True, timeout=900)
+    r = subprocess.run([sys.executable, str(REPO / "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--envs-per-gpu", "64", "--full",
+                        "--no-sweep", "--no-cpu-baseline", "--details-out", str(tmp_path / "d.json")], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = r.stdout.strip().splitlines()
     assert len(lines) == 1 and len(lines[0]) <= 6000, r.stdout[-2000:]
