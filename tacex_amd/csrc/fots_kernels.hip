@@ -94,6 +94,18 @@ struct FotsArgs {
   float mm2pix, shear_max, theta_max_rad_f;
 };
 
+// int(t * mm2pix + half) with TWO float32 roundings (product, then sum), like the reference's NumPy scalars (MM:177-178,
+// 194-195).  The library is built with -ffp-contract=fast, under which `t * mm2pix + half` became one v_pk_fma_f32 feeding
+// the v_cvt_i32_f32: a single rounding, 1 ulp under the integer when the contact centroid is a whole pixel (a patch symmetric
+// about a pixel), truncated to the pixel before.  Neither __fmul_rn / __fadd_rn (plain `*` / `+` in HIP's headers) nor a
+// product formed in float64 and cast back (folded to the float32 multiply) survives the backend's contraction, so the rounded
+// product passes through an empty asm statement: the add then has no multiply in sight.  Nothing else in the file changes.
+__device__ __forceinline__ int centre_px(float t, float mm2pix, float half) {
+  float prod = t * mm2pix;
+  asm volatile("" : "+v"(prod));
+  return (int)(prod + half);
+}
+
 __global__ __launch_bounds__(128) void fots_marker_kernel(FotsArgs a) {
   const int e = blockIdx.x;
   const int M = a.nrow * a.ncol;
@@ -208,8 +220,10 @@ __global__ __launch_bounds__(128) void fots_marker_kernel(FotsArgs a) {
 
   if (tlen >= 2) {
     // ---- shear (MM:176-187,78-88): float32 products (traj entries are np.float32), int() truncation ----
-    const int scx = (int)(t0x * a.mm2pix + (float)(a.W / 2.0));
-    const int scy = (int)(t0y * a.mm2pix + (float)(a.H / 2.0));
+    // The centres are int(t * mm2pix + W / 2) with the product AND the sum rounded to float32, as NumPy does: centre_px().
+    const float half_w = (float)(a.W / 2.0), half_h = (float)(a.H / 2.0);
+    const int scx = centre_px(t0x, a.mm2pix, half_w);
+    const int scy = centre_px(t0y, a.mm2pix, half_h);
     int shx = (int)((tlx - t0x) * a.mm2pix);
     int shy = (int)((tly - t0y) * a.mm2pix);
     const int smax = (int)a.shear_max;
@@ -224,8 +238,8 @@ __global__ __launch_bounds__(128) void fots_marker_kernel(FotsArgs a) {
     // ---- twist (MM:193-205,90-109): theta and its cos/sin are float32 (np.float32 scalar), cos(theta-1) sic ----
     float theta = tlt - t0t;
     theta = fminf(fmaxf(theta, -a.theta_max_rad_f), a.theta_max_rad_f);
-    const int tcx = (int)(tlx * a.mm2pix + (float)(a.W / 2.0));
-    const int tcy = (int)(tly * a.mm2pix + (float)(a.H / 2.0));
+    const int tcx = centre_px(tlx, a.mm2pix, half_w);
+    const int tcy = centre_px(tly, a.mm2pix, half_h);
     const double c1 = (double)cosf(theta - 1.0f);
     const double s1 = (double)sinf(theta);
     const double ox = (double)(px - tcx), oy = (double)(py - tcy);

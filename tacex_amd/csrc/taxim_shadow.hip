@@ -93,7 +93,12 @@ __global__ __launch_bounds__(256) void shadow_ray_kernel(ShadowRayArgs a) {
   int nidx = (int)floorf((a.gdir[(size_t)b * npix + p] + 3.14159274101257324f) / a.disc_prec);
   nidx = min(max(nidx, 0), a.ndir - 1);
   const float contact_px = (a.gel[p] - z[p]) / a.pixmm;
-  int hidx = (int)floorf((contact_px * a.pixmm - a.depth0) / a.height_prec) + 6;
+  // (the pragma above does not bind the backend under -ffp-contract=fast: this product and difference came out as one v_fma_f32
+  // feeding the floor, one bin off where the quotient is an integer - e.g. a gel height of -0.9 mm.  An empty asm statement
+  // between the two leaves the subtraction no multiply to fuse with.)
+  float contact_mm = contact_px * a.pixmm;
+  asm volatile("" : "+v"(contact_mm));
+  int hidx = (int)floorf((contact_mm - a.depth0) / a.height_prec) + 6;
   const int max_h = a.nheight - 1;
   if (hidx < 0 || hidx >= max_h) hidx = max_h;
   const float* __restrict__ tab = a.table + ((size_t)nidx * a.nheight + hidx) * a.nstep * 4;

@@ -454,6 +454,46 @@ def test_shadow_ray_samples_exact_vs_oracle(taxim, golden_dir, calib_dir, shape)
     np.testing.assert_array_equal(got, ref)                            # ... and the table values that landed there
 
 
+def test_shadow_height_bin_on_a_bin_edge_vs_oracle(taxim, golden_dir, calib_dir):
+    """The height bin of a ray-casting pixel is floor((contact_px * pixmm - depth_0) / height_precision) in float32 with the
+    product and the difference rounded separately (TT:280-287).  For gel heights that put the quotient on an integer - -0.9 mm,
+    the float32 below -1 mm and below -2 mm with the shipped calibration - a fused multiply-subtract lands in the neighbouring bin,
+    i.e. another row of the shadow table.  Ring pixels of the golden frames are set to those heights; sample set and values must
+    still equal the oracle's exactly."""
+    from oracle.taxim_oracle import TaximOracle
+    from parity import unpack_mask
+
+    H, W = 240, 320
+    g = dict(np.load(golden_dir / f"taxim_{H}x{W}.npz"))
+    n = 4
+    Z = g["Z"][:n].astype(np.float32).copy()
+    M = unpack_mask(g["M"], g["Z"].shape)[:n]
+    o = TaximOracle(calib_dir, (H, W), "direct")
+    F32 = np.float32
+    dil = M.astype(F32)
+    for (kw, kh) in o.shadow_attachment_rounds():
+        dil = o._box_dilate_same(dil, int(kh), int(kw))
+    bi, yi, xi = np.nonzero((dil != 0) & ~M)  # the pixels that cast rays
+    assert len(bi) > 500
+    edge_z = np.array([-0.9, np.nextafter(F32(-1.0), F32(0)), np.nextafter(F32(-2.0), F32(0))], F32)
+    pick = np.arange(0, len(bi), 5)
+    Z[bi[pick], yi[pick], xi[pick]] = edge_z[np.arange(len(pick)) % 3]
+    # the inputs have teeth: two roundings and one rounding give different bins there (and the bins are inside the table)
+    pixmm, d0, hp = F32(o.p.pixmm), F32(o.shadow_depth_0), F32(o.p.sim["height_precision"])
+    zz, gel = Z[bi[pick], yi[pick], xi[pick]], o.gel[yi[pick], xi[pick]]
+    cp = ((gel - zz) / pixmm).astype(F32)
+    two = np.floor((cp * pixmm - d0) / hp).astype(np.int64) + 6
+    one = np.floor((cp.astype(np.float64) * np.float64(pixmm) - np.float64(d0)).astype(F32) / hp).astype(np.int64) + 6
+    assert (two != one).all() and (two >= 0).all() and (two < o.shadow_table.shape[2] - 1).all() and (one < o.shadow_table.shape[2] - 1).all()
+    assert not np.array_equal(o.shadow_table[:, :, 10], o.shadow_table[:, :, 11])
+    ref, gdir = o.shadow_map(Z, M)
+    assert np.isfinite(ref).any()
+    got = taxim.shadow_rays(torch.from_numpy(Z).cuda(), torch.from_numpy(M.astype(np.uint8)).cuda(), torch.from_numpy(gdir.astype(np.float32)).cuda())
+    got = got.cpu().numpy()
+    np.testing.assert_array_equal(np.isfinite(got), np.isfinite(ref))
+    np.testing.assert_array_equal(got, ref)
+
+
 def test_shadow_branch_640x480_vs_reference(taxim, golden_dir):
     """with_shadow=True at BASELINE config C5's resolution against the reference's own render (frame 0 of the 480x640 fixture):
     same protocol as at 320x240 - ALL pixels whose receptive field of the two blurs (k = 5 and k = 9 here) is well conditioned."""
