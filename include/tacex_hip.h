@@ -32,7 +32,7 @@ extern "C" {
 #endif
 
 #define TACEX_MAX_LEVELS 8
-#define TACEX_ABI_VERSION 18
+#define TACEX_ABI_VERSION 19
 
 typedef struct tacex_taxim_ctx tacex_taxim_ctx;
 typedef struct tacex_fots_ctx tacex_fots_ctx;
@@ -493,6 +493,33 @@ int tacex_fem_set_indenter_mesh_library(tacex_fem_ctx* ctx, int num_meshes, cons
  * step_info[., 2]. */
 int tacex_fem_set_indenter_mesh_ids(tacex_fem_ctx* ctx, const int32_t* ids_dev);
 
+/* Gel MATERIAL LIBRARY (ABI 19): one gel material PER ENV, chosen by a device id array (tacex_fem_set_material_ids) - the reference's
+ * per-object StableNeoHookeanCfg(youngs_modulus, poisson_rate) / mass_density (tacex_uipc/objects/uipc_object.py:54-92) and the
+ * per-element friction ratio of its contact tabular, for envs that share one context.  Host arrays of num_materials entries: youngs
+ * [Pa] > 0, -1 < poisson < 0.5, density [kg/m^3] > 0, friction_ratio >= 0 (as tacex_fem_create / tacex_fem_set_friction).  Per material
+ * the library holds what tacex_fem_create builds for the scene's one material - the Stable Neo-Hookean constants and the (V) mass
+ * table, by the same expressions in the same order - so an env of material k computes bit for bit (tacex_fem_set_deterministic) what a
+ * context created with material k and tacex_fem_set_friction(ratio k) computes.  Honoured by tacex_fem_step, tacex_fem_newton_step,
+ * tacex_fem_element_terms, tacex_fem_energy and tacex_fem_gradient (every Newton kernel route).  While a library is set the ratio of
+ * tacex_fem_set_friction is not used (its eps_velocity is); friction is on for the scene when any material's ratio is > 0, an env
+ * whose material has ratio 0 runs without.  d_hat, contact stiffness, eps_velocity, dt and the constraint strength stay scene-wide.
+ * num_materials = 0 removes the library (and its coarse inverses): the scene is again what tacex_fem_create / tacex_fem_set_friction
+ * made.  Not implemented together with tacex_fem_set_affine_body: either call fails when the other is in force.  Tables are copied;
+ * the id array set before stays in place. */
+int tacex_fem_set_material_library(tacex_fem_ctx* ctx, int num_materials, const double* youngs, const double* poisson,
+                                   const double* density, const double* friction_ratio);
+
+/* ids_dev (B,) int32 device: the library material of every env, read by every later call with B envs (the caller may rewrite it
+ * between steps, e.g. to draw new gels at a reset; it must stay allocated while set).  NULL: every env uses material 0.  An id outside
+ * [0, num_materials) is never dereferenced: that env computes with material 0 and tacex_fem_step sets flag 64 in its step_info[., 2]. */
+int tacex_fem_set_material_ids(tacex_fem_ctx* ctx, const int32_t* ids_dev);
+
+/* The coarse inverse of tacex_fem_set_coarse_space depends on the material: coarse_inverses_host (num_materials, 3 num_coarse,
+ * 3 num_coarse) f64, one per material of the library, each built as the coarse_inverse_host of a scene of that material alone.  Call
+ * after tacex_fem_set_material_library and tacex_fem_set_coarse_space (either of them drops these tables); without it every env uses
+ * the scene's one inverse (a valid, weaker preconditioner for the other materials).  num_materials = 0 removes them.  Copied. */
+int tacex_fem_set_material_coarse_inverses(tacex_fem_ctx* ctx, int num_materials, const double* coarse_inverses_host);
+
 /* Block part of the preconditioner: block-tridiagonal LDL^T along VERTEX CHAINS instead of one 3x3 block per vertex.  A chain is a
  * sequence of mesh vertices, consecutive ones sharing a tet (the columns of vertices through a gelpad's thickness: the nearly
  * incompressible material couples the layers of a thin pad most strongly; UipcSim builds them with
@@ -537,7 +564,8 @@ int tacex_fem_newton_step(tacex_fem_ctx* ctx, double* x_dev, const double* x_til
  * informational: 4 = the env dropped the coarse correction for the rest of the step (its stopping test passed with the residual's
  * 2-norm above |b|: no reduction at all), 8 = its PCG met negative curvature and iterations of the step were solved with the PSD-safe Hessian
  * (|c_J| of the Stable Neo-Hookean d2J/dF2 term clamped per element; the gradient is exact, the minimiser the same); 32 (ABI 17) = the
- * env's kind-4 row named a mesh id outside the indenter mesh library (tacex_fem_set_indenter_mesh_ids): it had no indenter.
+ * env's kind-4 row named a mesh id outside the indenter mesh library (tacex_fem_set_indenter_mesh_ids): it had no indenter; 64 (ABI 19)
+ * = the env's material id lay outside the material library (tacex_fem_set_material_ids): it stepped with material 0.
  * workspace_dev: tacex_fem_workspace_bytes(ctx, num_envs). */
 int tacex_fem_step(tacex_fem_ctx* ctx, double* x_dev, double* v_dev, double* x_tilde_dev, const uint8_t* constrained_dev,
                    const double* aim_dev, double* stats_dev, double* step_info_dev, void* workspace_dev, int num_envs,

@@ -11,7 +11,7 @@ from pathlib import Path
 from ._build import LIB, build_library
 
 MAX_LEVELS = 8
-ABI_VERSION = 18  # TACEX_ABI_VERSION of include/tacex_hip.h; bumped whenever a signature or struct layout changes
+ABI_VERSION = 19  # TACEX_ABI_VERSION of include/tacex_hip.h; bumped whenever a signature or struct layout changes
 FLAG_NO_SHIFT = 1
 FLAG_HAVE_FRAME_MIN = 2
 FLAG_WITH_SHADOW = 4
@@ -143,6 +143,9 @@ SIGNATURES = {
     "tacex_fem_set_indenter_mesh": (_i, [_vp, _i, _vp, _i, _vp]),
     "tacex_fem_set_indenter_mesh_library": (_i, [_vp, _i, _vp, _vp, _vp, _vp]),
     "tacex_fem_set_indenter_mesh_ids": (_i, [_vp, _vp]),
+    "tacex_fem_set_material_library": (_i, [_vp, _i, _vp, _vp, _vp, _vp]),
+    "tacex_fem_set_material_ids": (_i, [_vp, _vp]),
+    "tacex_fem_set_material_coarse_inverses": (_i, [_vp, _i, _vp]),
     "tacex_fem_contact_gaps": (_i, [_vp, _vp, _vp, _i, _vp]),
     "tacex_fem_newton_resident": (_i, [_vp]),
     "tacex_fem_newton_route": (_i, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),

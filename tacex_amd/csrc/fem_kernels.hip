@@ -77,6 +77,18 @@ struct FemDev {
   const int* ch_next;       // (V) successor in the chain, -1 at its end
   const int* ch_prev;       // (V) predecessor, -1 at its head
 };
+// Gel MATERIAL LIBRARY (tacex_fem_set_material_library / _ids): K materials, one chosen per env.  Per material a record of kMatHead + V
+// doubles: mu | lam | alpha | psi_rest | friction ratio | 3 pad | the (V) mass table of its density.  A kernel launched with MAT = true
+// resolves its env's record once at entry (env_material) and overwrites mu, lam, alpha, psi_rest, fric_mu, mass and ac_inv of ITS copy
+// of FemDev with it; with no library (n = 0) the MAT = false instantiations run and the argument is not read.  It is the LAST argument
+// of every kernel that takes it and FemDev is what it was: no older argument moves, and the MAT = false kernels keep their code.
+struct FemMat {
+  int n;                // materials (0: no library)
+  const double* lib;    // (n, kMatHead + V)
+  const int* ids;       // (B) material id of every env (tacex_fem_set_material_ids, read at every step); nullptr: material 0 everywhere
+  const double* ac;     // (n, 3 nc, 3 nc) coarse inverse per material (tacex_fem_set_material_coarse_inverses); nullptr: FemDev::ac_inv for all
+};
+constexpr int kMatHead = 8;
 constexpr int kFemMaxCoarse = 64;
 
 // ---- IPC barrier of one surface vertex against the env's analytic indenter ------------------------------------------
@@ -116,6 +128,32 @@ __device__ __forceinline__ IndMesh env_mesh(const FemDev& m, int b, const double
   r.cl = m.im_lib + (unsigned)__builtin_amdgcn_readfirstlane(e[2]);
   r.nt = __builtin_amdgcn_readfirstlane(e[3]);
   return r;
+}
+
+// The env's material of the library, resolved ONCE per workgroup at kernel entry like env_mesh: every FEM kernel takes its env from
+// the block index (fem_newton_lds_kernel through env_order), so no wave straddles two envs and the id, the five constants and the
+// two table addresses are wave-uniform (readfirstlane: SGPRs, scalar loads).  REPLACES the material fields of the kernel's own copy
+// of the scene description; everything downstream keeps reading `m.mu`, `m.mass[v]`, `m.ac_inv`, `m.fric_mu`.  An id outside
+// [0, mat.n) is never dereferenced: the env takes material 0 and `bad` reports it (kFemFlagBadMaterial).  MAT = false: `m` is not
+// touched - those instantiations are, statement for statement, the kernels from before the library.
+__device__ __forceinline__ double uniform_f64(double v) {
+  return __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(v)), __builtin_amdgcn_readfirstlane(__double2loint(v)));
+}
+template <bool MAT>
+__device__ __forceinline__ bool env_material(FemDev& m, const FemMat& mat, int b) {
+  bool bad = false;
+  if constexpr (MAT) {
+    if (mat.n > 0) {
+      int id = mat.ids ? __builtin_amdgcn_readfirstlane(mat.ids[b]) : 0;
+      if (id < 0 || id >= mat.n) { bad = true; id = 0; }
+      const double* rec = mat.lib + (size_t)id * (size_t)(kMatHead + m.V);
+      m.mu = uniform_f64(rec[0]); m.lam = uniform_f64(rec[1]); m.alpha = uniform_f64(rec[2]); m.psi_rest = uniform_f64(rec[3]);
+      m.fric_mu = uniform_f64(rec[4]);
+      m.mass = rec + kMatHead;
+      if (mat.ac) m.ac_inv = mat.ac + (size_t)id * (size_t)(9 * m.nc * m.nc);
+    }
+  }
+  return bad;
 }
 
 // Unsigned distance of p (mesh frame) to the nearest triangle of the indenter mesh and the unit vector from the closest point to p.
@@ -474,7 +512,9 @@ __device__ __forceinline__ void element_gradient(const TetState& s, const double
 }
 
 // cyclic Jacobi eigen-decomposition of a symmetric 9x9 (PSD-projection path only; arrays live in scratch)
-__device__ void jacobi_psd9(double* A) {
+// (forced inline: with ONE caller the compiler inlined it by itself; the element kernel now has two PSD instantiations, and called
+// out of line the 12 x 12 block of the caller went to scratch as well - 1860 against 384 B/lane)
+__device__ __forceinline__ void jacobi_psd9(double* A) {
   double V[81];
   for (int i = 0; i < 81; ++i) V[i] = (i / 9 == i % 9) ? 1.0 : 0.0;
   for (int sweep = 0; sweep < 12; ++sweep) {
@@ -519,13 +559,14 @@ __device__ void jacobi_psd9(double* A) {
 }
 
 // ---- K17a: element terms, one tet per lane, SoA outputs ---------------------------------------------------
-template <bool PROJECT_PSD>
+template <bool PROJECT_PSD, bool MAT>
 __global__ __launch_bounds__(256) void fem_element_terms_kernel(FemDev m, const double* __restrict__ x,
                                                                 double* __restrict__ energy, double* __restrict__ grad,
-                                                                double* __restrict__ hess) {
+                                                                double* __restrict__ hess, FemMat mat) {
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
   const int b = blockIdx.y;
   if (t >= m.T) return;
+  (void)env_material<MAT>(m, mat, b);  // (a bad id is reported by the step kernels)
   int v[4];
   double Di[9], F[9], r[12];
   load_tet(m, t, v, Di);
@@ -681,10 +722,12 @@ __device__ __forceinline__ void gather_vertex(const FemDev& m, const double* ge,
   }
 }
 
+template <bool MAT>
 __global__ __launch_bounds__(512) void fem_energy_kernel(FemDev m, const double* x, const double* xt,
-                                                         const uint8_t* cons, const double* aim, double* E) {
+                                                         const uint8_t* cons, const double* aim, double* E, FemMat mat) {
   __shared__ double sh[17];
   const int b = blockIdx.x;
+  (void)env_material<MAT>(m, mat, b);  // (a bad id is reported by the step kernels)
   const size_t o = (size_t)b * m.V * 3;
   const double* ind = m.indenters ? m.indenters + (size_t)b * 8 : nullptr;
   bool bad;
@@ -693,10 +736,12 @@ __global__ __launch_bounds__(512) void fem_energy_kernel(FemDev m, const double*
   if (threadIdx.x == 0) E[b] = e;
 }
 
+template <bool MAT>
 __global__ __launch_bounds__(512) void fem_gradient_kernel(FemDev m, const double* x, const double* xt,
                                                            const uint8_t* cons, const double* aim, double* g,
-                                                           double* ws_ge /* (B,12,T) */) {
+                                                           double* ws_ge /* (B,12,T) */, FemMat mat) {
   const int b = blockIdx.x;
+  (void)env_material<MAT>(m, mat, b);  // (a bad id is reported by the step kernels)
   const size_t o = (size_t)b * m.V * 3;
   double* ge = ws_ge + (size_t)b * 12 * m.T;
   bool bad;
@@ -793,11 +838,13 @@ constexpr int kFemFlagCoarseOff = 4;    // informational: the coarse correction 
 constexpr int kFemFlagPsdSafe = 8;      // informational: the PCG met negative curvature and the env solved iterations of the step in PSD-safe mode
 // (16: fem_ball.h's pair-list overflow)
 constexpr int kFemFlagBadMesh = 32;     // the env's kind-4 row named a mesh id outside the library: no indenter this step (env_mesh)
+constexpr int kFemFlagBadMaterial = 64; // the env's material id lay outside the library: it stepped with material 0 (env_material)
+template <bool MAT>
 __global__ __launch_bounds__(512) void fem_newton_kernel(FemDev m, double* xg, const double* xtg, const uint8_t* consg,
                                                          const double* aimg, double* stats, double* wsg,
                                                          int pcg_max_iter, double pcg_tol_rate, int ls_max_iter, double* dxg, double dx_tol,
                                                          double* step_info, int accumulate, const double* xprevg, const double* dispg,
-                                                         int fric_ipc, int lds_sweep) {
+                                                         int fric_ipc, int lds_sweep, FemMat mat) {
   // step_info (nullable): the row of this env [Newton iterations, max |d|, flags, PCG iterations] - SET by the first launch of a time
   // step (accumulate = 0), added to / OR-ed by the later ones: tacex_fem_step runs this kernel once per Newton iteration, and
   // UipcSim.check_step() must see a penetrating vertex or a dead line search of ANY of them (the row used to be zeroed)
@@ -813,6 +860,7 @@ __global__ __launch_bounds__(512) void fem_newton_kernel(FemDev m, double* xg, c
     if (threadIdx.x == 0) { stats[(size_t)b * 4 + 2] = 0.0; stats[(size_t)b * 4 + 3] = 0.0; }
     return;
   }
+  const bool mat_bad = env_material<MAT>(m, mat, b);
   const int V = m.V, T = m.T;
   const size_t o = (size_t)b * V * 3;
   double* x = xg + o;
@@ -1163,7 +1211,7 @@ __global__ __launch_bounds__(512) void fem_newton_kernel(FemDev m, double* xg, c
     stats[(size_t)b * 4 + 0] = E0; stats[(size_t)b * 4 + 1] = E1; stats[(size_t)b * 4 + 2] = step; stats[(size_t)b * 4 + 3] = (double)it;
     if (step_info) {
       const int fl = (any_pen ? kFemFlagPenetration : 0) | ((!accepted && !(dmax <= dx_tol)) ? kFemFlagLsFailed : 0) |
-                     (mesh_bad ? kFemFlagBadMesh : 0);
+                     (mesh_bad ? kFemFlagBadMesh : 0) | (mat_bad ? kFemFlagBadMaterial : 0);
       double* si = step_info + (size_t)b * 4;
       si[0] = (accumulate ? si[0] : 0.0) + 1.0;
       si[1] = dmax;
@@ -1315,13 +1363,13 @@ constexpr double kCoarseTrust = 1.0;
 // arithmetic of the next (no barrier between batches: wave skew no longer costs).  The price is the summation ORDER of a vertex's
 // ~24 contributions, which then depends on the timing of the waves: results agree to round-off (1e-16 relative per add), not
 // bit for bit from run to run.  `tacex_fem_set_deterministic(ctx, 1)` selects the window path (ATOM = false).
-template <bool MESH, bool ATOM, int NT>
+template <bool MESH, bool ATOM, int NT, bool MAT>
 __global__ __launch_bounds__(NT) void fem_newton_lds_kernel(FemDev m, double* xg, const double* xtg,
                                                                      const uint8_t* consg, const double* aimg, double* stats,
                                                                      int pcg_max_iter, double pcg_tol_rate, int ls_max_iter,
                                                                      double* dxg, double dx_tol, int max_newton, double* step_info,
                                                                      const double* xprevg, const double* dispg, const int* env_order,
-                                                                     int follow, double* lagg) {
+                                                                     int follow, double* lagg, FemMat mat) {
   extern __shared__ __attribute__((aligned(16))) double nlds[];
   constexpr int CH = NT;  // tets per pass of a sweep (one per thread) = tets per exchange window
   constexpr bool BIG = NT > kNwtThreads;  // meshes of more than 512 vertices: see nwt_lds_bytes
@@ -1334,6 +1382,8 @@ __global__ __launch_bounds__(NT) void fem_newton_lds_kernel(FemDev m, double* xg
   double* hv = ps + 3 * V;      // (12, CH) per-tet rows of the current window | accumulators, exchange arrays (nwt_window_doubles)
   double* sh = hv + nwt_window_doubles(V, NT);  // 2 x NT / 64 wave partials of block_sum1 (+2 pad)
   // friction (tacex_fem_step with a friction ratio): (V,4) lagged normal force and normal, (V,6) Hessian blocks (floats)
+  // (this is still the SCENE's friction switch - with a material library the largest ratio of the library, what the host sized the
+  // allocation with: the LDS layout is one for all envs; whether THIS env has friction follows its own material: `fric` below)
   const bool fric_lds = m.indenters && m.area && m.fric_mu > 0.0 && xprevg != nullptr && dispg != nullptr;  // (xprevg is only handed over with friction)
   double* fl = sh + 2 * (NT / 64) + 2;
   double* mdl = fl + (fric_lds ? 4 * V : 0);  // (V) diagonal mass term m_v (1 + s c_v): read back per PCG iteration (per-thread constants
@@ -1355,6 +1405,7 @@ __global__ __launch_bounds__(NT) void fem_newton_lds_kernel(FemDev m, double* xg
     if (threadIdx.x == 0) { stats[(size_t)b * 4 + 2] = 0.0; stats[(size_t)b * 4 + 3] = 0.0; }
     return;
   }
+  const bool mat_bad = env_material<MAT>(m, mat, b);  // (looked up with the env b, not with blockIdx.x: env_order)
   const size_t o = (size_t)b * V * 3;
   double* x = xg + o;
   const double* xt = xtg + o;
@@ -2176,7 +2227,8 @@ restart_iteration:
     // (__syncthreads_or returns a truth value, not the OR of the bits: one reduction per flag)
     const int any = (__syncthreads_or(flags & kFemFlagPenetration) ? kFemFlagPenetration : 0) |
                     (__syncthreads_or(flags & kFemFlagLsFailed) ? kFemFlagLsFailed : 0) |
-                    (flags & (kFemFlagCoarseOff | kFemFlagPsdSafe)) | (mesh_bad ? kFemFlagBadMesh : 0);  // (these are block-uniform)
+                    (flags & (kFemFlagCoarseOff | kFemFlagPsdSafe)) | (mesh_bad ? kFemFlagBadMesh : 0) |
+                    (mat_bad ? kFemFlagBadMaterial : 0);  // (these are block-uniform)
     if (tid == 0) {
       step_info[(size_t)b * 4 + 0] = (double)n_newton; step_info[(size_t)b * 4 + 1] = dmax_last;
       step_info[(size_t)b * 4 + 2] = (double)any; step_info[(size_t)b * 4 + 3] = pcg_total;
@@ -2248,13 +2300,14 @@ __device__ __forceinline__ void tet_block_offdiag(const FemDev& m, const TetStat
 #else
 #define ASM_ADD(p, v) atomicAdd((p), (v))
 #endif
-template <bool ATOM>
+template <bool ATOM, bool MAT>
 __global__ __launch_bounds__(512) void fem_assemble_blocks_kernel(FemDev m, const double* __restrict__ xg, double* __restrict__ lagg,
-                                                                   const double* __restrict__ dxg, double dx_tol) {
+                                                                   const double* __restrict__ dxg, double dx_tol, FemMat mat) {
   extern __shared__ __attribute__((aligned(16))) double alds[];
   constexpr int NT = 512;
   const int V = m.V, T = m.T, b = blockIdx.x, tid = threadIdx.x;
   if (dxg && dxg[b] <= dx_tol) return;
+  (void)env_material<MAT>(m, mat, b);  // (a bad id is reported by the step kernels)
   double* xs = alds;           // (V,3)
   double* xa = xs + 3 * V;     // (V,15) accumulators (ATOM)
   const double* x = xg + (size_t)b * V * 3;
@@ -2542,6 +2595,7 @@ struct tacex_fem_ctx {
   int device = 0;
   FemDev dev{};
   FemDev dev_nwt{};  // same mesh with the tets renumbered for fem_newton_lds_kernel (see tacex_fem_create)
+  FemMat mat{};      // the gel material library (tacex_fem_set_material_library); one copy: every launch hands it over
   // Friction slides relative to the indenter's displacement since the previous tacex_fem_step.  The previous positions (B,3) live
   // in the caller's workspace (no allocation in a compute call); the context remembers WHICH workspace and env count they were
   // written for, so another workspace or num_envs never reads stale data, and a new indenter TENSOR for the same contact (the
@@ -2561,6 +2615,10 @@ struct tacex_fem_ctx {
   tacex::BallDev ball{};     // the env's free affine body + ground (tacex_fem_set_affine_body); nv == 0: none
   const void* ball_last_ws = nullptr;  // workspace / env count whose "q at the end of the previous step" rows are valid (kinematic bodies)
   int ball_last_B = 0;
+  // what tacex_fem_set_material_library needs to build a material's mass table the way tacex_fem_create built the scene's
+  std::vector<int> tets_host;    // (4,T) SoA, re-oriented
+  std::vector<double> vol_host;  // (T)
+  double fric_scene = 0.0;       // the ratio tacex_fem_set_friction gave (FemDev::fric_mu is the library's largest while a library is set)
   std::vector<void*> allocs;
 };
 
@@ -2679,6 +2737,7 @@ int tacex_fem_create(int device_id, const tacex_fem_params* p, tacex_fem_ctx** o
   if (e != hipSuccess) return fail_hip(e, "hipSetDevice");
   auto* c = new tacex_fem_ctx();
   c->device = device_id;
+  c->tets_host = tets; c->vol_host = vol;
   FemDev& d = c->dev;
   d.V = V; d.T = T;
   {
@@ -2769,12 +2828,10 @@ int tacex_fem_element_terms(tacex_fem_ctx* c, const double* x, double* energy, d
                             int project_psd, int B, void* stream) {
   if (!c || !x) { set_error("tacex_fem_element_terms: null argument"); return 2; }
   if (B <= 0) return 0;
-  if (project_psd && hess)
-    hipLaunchKernelGGL(fem_element_terms_kernel<true>, dim3((c->dev.T + 255) / 256, B), dim3(256), 0, (hipStream_t)stream,
-                       c->dev, x, energy, grad, hess);
-  else
-    hipLaunchKernelGGL(fem_element_terms_kernel<false>, dim3((c->dev.T + 255) / 256, B), dim3(256), 0, (hipStream_t)stream,
-                       c->dev, x, energy, grad, hess);
+  const bool mat = c->mat.n > 0;
+  auto ke = (project_psd && hess) ? (mat ? fem_element_terms_kernel<true, true> : fem_element_terms_kernel<true, false>)
+                                  : (mat ? fem_element_terms_kernel<false, true> : fem_element_terms_kernel<false, false>);
+  hipLaunchKernelGGL(ke, dim3((c->dev.T + 255) / 256, B), dim3(256), 0, (hipStream_t)stream, c->dev, x, energy, grad, hess, c->mat);
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? 0 : fail_hip(e, "fem_element_terms_kernel");
 }
@@ -2785,7 +2842,8 @@ int tacex_fem_energy(tacex_fem_ctx* c, const double* x, const double* xt, const 
   if (!c || !x || !xt || !E) { set_error("tacex_fem_energy: null argument"); return 2; }
   if ((cons == nullptr) != (aim == nullptr)) { set_error("tacex_fem_energy: constrained_dev and aim_dev go together"); return 2; }
   if (B <= 0) return 0;
-  hipLaunchKernelGGL(fem_energy_kernel, dim3(B), dim3(512), 0, (hipStream_t)stream, c->dev, x, xt, cons, aim, E);
+  hipLaunchKernelGGL(c->mat.n > 0 ? fem_energy_kernel<true> : fem_energy_kernel<false>, dim3(B), dim3(512), 0, (hipStream_t)stream, c->dev, x, xt, cons,
+                     aim, E, c->mat);
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? 0 : fail_hip(e, "fem_energy_kernel");
 }
@@ -2795,8 +2853,8 @@ int tacex_fem_gradient(tacex_fem_ctx* c, const double* x, const double* xt, cons
   if (!c || !x || !xt || !g || !ws) { set_error("tacex_fem_gradient: null argument"); return 2; }
   if ((cons == nullptr) != (aim == nullptr)) { set_error("tacex_fem_gradient: constrained_dev and aim_dev go together"); return 2; }
   if (B <= 0) return 0;
-  hipLaunchKernelGGL(fem_gradient_kernel, dim3(B), dim3(512), 0, (hipStream_t)stream, c->dev, x, xt, cons, aim, g,
-                     static_cast<double*>(ws));
+  hipLaunchKernelGGL(c->mat.n > 0 ? fem_gradient_kernel<true> : fem_gradient_kernel<false>, dim3(B), dim3(512), 0, (hipStream_t)stream, c->dev, x, xt,
+                     cons, aim, g, static_cast<double*>(ws), c->mat);
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? 0 : fail_hip(e, "fem_gradient_kernel");
 }
@@ -2855,7 +2913,8 @@ int tacex_fem_set_friction(tacex_fem_ctx* c, double friction_ratio, double eps_v
     set_error("tacex_fem_set_friction: need friction_ratio >= 0 and eps_velocity > 0");
     return 2;
   }
-  c->dev.fric_mu = c->dev_nwt.fric_mu = friction_ratio;
+  c->fric_scene = friction_ratio;
+  if (c->mat.n == 0) c->dev.fric_mu = c->dev_nwt.fric_mu = friction_ratio;  // (with a material library: its largest ratio, set there)
   c->dev.fric_eps = c->dev_nwt.fric_eps = eps_velocity * c->dev.dt;
   return 0;
 }
@@ -3026,6 +3085,85 @@ int tacex_fem_set_indenter_mesh_ids(tacex_fem_ctx* c, const int32_t* ids_dev) {
   return 0;
 }
 
+// ---- gel material library -----------------------------------------------------------------------------------------------------------
+int tacex_fem_set_material_library(tacex_fem_ctx* c, int num_materials, const double* youngs, const double* poisson, const double* density,
+                                   const double* friction_ratio) {
+  if (!c) { set_error("tacex_fem_set_material_library: null context"); return 2; }
+  if (num_materials < 0 || (num_materials > 0 && (!youngs || !poisson || !density || !friction_ratio))) {
+    set_error("tacex_fem_set_material_library: bad arguments (num_materials = %d)", num_materials);
+    return 2;
+  }
+  if (num_materials > 0 && c->ball.nv > 0) {
+    set_error("tacex_fem_set_material_library: not implemented for a scene with an affine body (tacex_fem_set_affine_body)");
+    return 2;
+  }
+  const int V = c->dev.V, T = c->dev.T;
+  const size_t stride = (size_t)kMatHead + V;
+  std::vector<double> lib(stride * num_materials, 0.0);
+  double fmax_ = 0.0;
+  for (int k = 0; k < num_materials; ++k) {
+    if (!(poisson[k] > -1.0 && poisson[k] < 0.5) || !(youngs[k] > 0.0) || !(density[k] > 0.0) || !(friction_ratio[k] >= 0.0)) {
+      set_error("tacex_fem_set_material_library: material %d needs youngs > 0, -1 < poisson < 0.5, density > 0, friction_ratio >= 0", k);
+      return 2;
+    }
+    // the expressions and the summation order of tacex_fem_create: an env of material k computes bit for bit what a scene created
+    // with that material computes
+    double* rec = lib.data() + stride * k;
+    const double mu_l = youngs[k] / (2.0 * (1.0 + poisson[k]));
+    const double lam_l = youngs[k] * poisson[k] / ((1.0 + poisson[k]) * (1.0 - 2.0 * poisson[k]));
+    const double mu = 4.0 / 3.0 * mu_l;
+    const double lam = lam_l + 5.0 / 6.0 * mu_l;
+    const double alpha = 1.0 + 0.75 * mu / lam;
+    rec[0] = mu; rec[1] = lam; rec[2] = alpha;
+    rec[3] = 0.5 * lam * (1.0 - alpha) * (1.0 - alpha) - 0.5 * mu * log(4.0);
+    rec[4] = friction_ratio[k];
+    double* mass = rec + kMatHead;
+    for (int t = 0; t < T; ++t)
+      for (int j = 0; j < 4; ++j) mass[c->tets_host[(size_t)j * T + t]] += density[k] * c->vol_host[t] / 4.0;
+    fmax_ = fmax(fmax_, friction_ratio[k]);
+  }
+  hipError_t e = hipSetDevice(c->device);
+  if (e != hipSuccess) return fail_hip(e, "hipSetDevice");
+  FemDev& d = c->dev;
+  FemDev& n2 = c->dev_nwt;
+  {
+    // (the per-material coarse inverses belong to the library they were built for: they go with it)
+    bool synced = false;
+    fem_release(c, c->mat.lib, &synced); fem_release(c, c->mat.ac, &synced);
+    c->mat.n = 0;
+    d.fric_mu = n2.fric_mu = c->fric_scene;
+  }
+  if (num_materials > 0) {
+    if (int rc = fem_upload(c, lib, &c->mat.lib)) return rc;
+    c->mat.n = num_materials;
+    d.fric_mu = n2.fric_mu = fmax_;  // sizes the friction state of the Newton kernels; an env's own ratio comes from its material
+  }
+  return 0;
+}
+
+int tacex_fem_set_material_ids(tacex_fem_ctx* c, const int32_t* ids_dev) {
+  if (!c) { set_error("tacex_fem_set_material_ids: null context"); return 2; }
+  c->mat.ids = ids_dev;
+  return 0;
+}
+
+int tacex_fem_set_material_coarse_inverses(tacex_fem_ctx* c, int num_materials, const double* coarse_inverses_host) {
+  if (!c) { set_error("tacex_fem_set_material_coarse_inverses: null context"); return 2; }
+  FemDev& d = c->dev;
+  if (num_materials != 0 && (num_materials != c->mat.n || !coarse_inverses_host || d.nc <= 0)) {
+    set_error("tacex_fem_set_material_coarse_inverses: need one inverse per material of the library (%d), got %d, and a coarse space (nc = %d)", c->mat.n,
+              num_materials, d.nc);
+    return 2;
+  }
+  hipError_t e = hipSetDevice(c->device);
+  if (e != hipSuccess) return fail_hip(e, "hipSetDevice");
+  bool synced = false;
+  fem_release(c, c->mat.ac, &synced);
+  if (num_materials == 0) return 0;
+  std::vector<double> ai(coarse_inverses_host, coarse_inverses_host + (size_t)num_materials * 9 * d.nc * d.nc);
+  return fem_upload(c, ai, &c->mat.ac);
+}
+
 int tacex_fem_set_chains(tacex_fem_ctx* c, int num_chains, const int32_t* chain_offsets_host, const int32_t* chain_vertices_host) {
   if (!c) { set_error("tacex_fem_set_chains: null context"); return 2; }
   FemDev& d = c->dev;
@@ -3077,6 +3215,7 @@ int tacex_fem_set_coarse_space(tacex_fem_ctx* c, int num_coarse, const int32_t* 
     FemDev& d0 = c->dev;
     fem_release(c, d0.cv_node, &synced); fem_release(c, d0.cv_w, &synced); fem_release(c, d0.cn_off, &synced);
     fem_release(c, d0.cn_vtx, &synced); fem_release(c, d0.cn_w, &synced); fem_release(c, d0.ac_inv, &synced);
+    fem_release(c, c->mat.ac, &synced);  // (the per-material inverses were built for the space that goes: tacex_fem_set_material_coarse_inverses again)
     FemDev& n0 = c->dev_nwt;
     n0.cv_node = nullptr; n0.cv_w = nullptr; n0.cn_off = nullptr; n0.cn_vtx = nullptr; n0.cn_w = nullptr; n0.ac_inv = nullptr;
     d0.nc = n0.nc = 0;
@@ -3131,16 +3270,18 @@ int tacex_fem_set_newton_early_exit(tacex_fem_ctx* c, double* dx_dev, double dx_
 // streaming fallback (mesh with more vertices than a workgroup has threads; TACEX_FEM_NEWTON_LDS=0)
 // elastic preconditioner blocks of all envs at x -> the env blocks of the workspace ((V,16) per env); dx_dev / dx_tol: envs already converged are skipped
 static int launch_assemble(tacex_fem_ctx* c, const double* x, void* ws, int B, const double* dx_dev, double dx_tol, hipStream_t st, bool atom) {
-  static size_t granted_a[2][64] = {};
+  static size_t granted_a[4][64] = {};
   // TACEX_FEM_ASSEMBLE: 1 = tet-centric with LDS atomics, 0 = vertex-centric in a fixed order (A/B hook; default: follows the atomics switch)
   static const int asm_env = getenv("TACEX_FEM_ASSEMBLE") ? atoi(getenv("TACEX_FEM_ASSEMBLE")) : -1;
   const bool asm_atom = asm_env < 0 ? atom : (asm_env != 0 && !c->deterministic);
   const int V = c->dev.V;
   const size_t lds_a = ((size_t)3 * V + (asm_atom ? (size_t)15 * V : 0)) * sizeof(double);
-  auto ka = asm_atom ? fem_assemble_blocks_kernel<true> : fem_assemble_blocks_kernel<false>;
-  hipError_t ea = ensure_dynamic_lds(reinterpret_cast<const void*>(ka), lds_a, granted_a[asm_atom ? 1 : 0]);
+  const bool mat = c->mat.n > 0;
+  auto ka = asm_atom ? (mat ? fem_assemble_blocks_kernel<true, true> : fem_assemble_blocks_kernel<true, false>)
+                     : (mat ? fem_assemble_blocks_kernel<false, true> : fem_assemble_blocks_kernel<false, false>);
+  hipError_t ea = ensure_dynamic_lds(reinterpret_cast<const void*>(ka), lds_a, granted_a[(asm_atom ? 1 : 0) + (mat ? 2 : 0)]);
   if (ea != hipSuccess) return fail_hip(ea, "hipFuncSetAttribute(fem_assemble_blocks_kernel)");
-  hipLaunchKernelGGL(ka, dim3(B), dim3(512), lds_a, st, c->dev_nwt, x, static_cast<double*>(ws), dx_dev, dx_tol);
+  hipLaunchKernelGGL(ka, dim3(B), dim3(512), lds_a, st, c->dev_nwt, x, static_cast<double*>(ws), dx_dev, dx_tol, c->mat);
   ea = hipGetLastError();
   return ea == hipSuccess ? 0 : fail_hip(ea, "fem_assemble_blocks_kernel");
 }
@@ -3168,23 +3309,29 @@ static int launch_newton(tacex_fem_ctx* c, double* x, const double* xt, const ui
   const size_t lds = nwt_lds_bytes(V, c->dev.T, fric, nt);
   hipError_t ea = hipSetDevice(c->device);  // (the LDS limits and opt-ins below are per device)
   if (ea != hipSuccess) return fail_hip(ea, "hipSetDevice");
-  using kern_t = decltype(&fem_newton_lds_kernel<false, true, 512>);
+  const bool mat = c->mat.n > 0;  // the material-library instantiations only when a library has been set
+  using kern_t = decltype(&fem_newton_lds_kernel<false, true, 512, false>);
   kern_t kern = nullptr;
   int slot = 0;
   if (use_lds && V <= 768 && (nt <= 512 ? 4 * c->dev.T < 65535 : (atom && !mesh))) {
     if (nt == 256) {
-      kern = fem_newton_lds_kernel<false, true, 256>;
+      kern = mat ? fem_newton_lds_kernel<false, true, 256, true> : fem_newton_lds_kernel<false, true, 256, false>;
       slot = 5;
     } else if (nt == 512) {
-      kern = mesh ? (atom ? fem_newton_lds_kernel<true, true, 512> : fem_newton_lds_kernel<true, false, 512>)
-                  : (atom ? fem_newton_lds_kernel<false, true, 512> : fem_newton_lds_kernel<false, false, 512>);
+      if (mat)
+        kern = mesh ? (atom ? fem_newton_lds_kernel<true, true, 512, true> : fem_newton_lds_kernel<true, false, 512, true>)
+                    : (atom ? fem_newton_lds_kernel<false, true, 512, true> : fem_newton_lds_kernel<false, false, 512, true>);
+      else
+        kern = mesh ? (atom ? fem_newton_lds_kernel<true, true, 512, false> : fem_newton_lds_kernel<true, false, 512, false>)
+                    : (atom ? fem_newton_lds_kernel<false, true, 512, false> : fem_newton_lds_kernel<false, false, 512, false>);
       slot = (mesh ? 1 : 0) + (atom ? 2 : 0);
     } else {
-      kern = fem_newton_lds_kernel<false, true, 768>;
+      kern = mat ? fem_newton_lds_kernel<false, true, 768, true> : fem_newton_lds_kernel<false, true, 768, false>;
       slot = 4;
     }
+    if (mat) slot += 6;
     // the env's state must fit next to the kernel's static __shared__; a pad that does not (e.g. 750 vertices on 768 threads) streams
-    static size_t avail[6][64] = {};
+    static size_t avail[12][64] = {};
     size_t limit = 0;
     ea = dynamic_lds_limit(reinterpret_cast<const void*>(kern), avail[slot], &limit);
     if (ea != hipSuccess) return fail_hip(ea, "hipFuncGetAttributes(fem_newton_lds_kernel)");
@@ -3195,7 +3342,7 @@ static int launch_newton(tacex_fem_ctx* c, double* x, const double* xt, const ui
     c->last_resident = 1;
     c->last_threads = nt;
     c->last_lds_mode = -1;
-    static size_t granted[6][64] = {};  // per kernel instantiation and device: the attribute is per kernel AND device
+    static size_t granted[12][64] = {};  // per kernel instantiation and device: the attribute is per kernel AND device
     ea = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), lds, granted[slot]);
     if (ea != hipSuccess) return fail_hip(ea, "hipFuncSetAttribute(fem_newton_lds_kernel)");
     // elastic preconditioner blocks of all envs at the state this launch starts from -> workspace ((V,16) per env)
@@ -3204,7 +3351,7 @@ static int launch_newton(tacex_fem_ctx* c, double* x, const double* xt, const ui
                        pcg_tol_rate, ls_max_iter, dx_dev, dx_tol, max_newton, step_info, fric ? xprev : nullptr,
                        (xprev && disp && c->dev.indenters) ? disp : nullptr, env_order,
                        (c->follow_indenter ? 1 : 0) | ((fric_lag_at_start || c->fric_lag_mode == 1) ? 2 : 0) | (c->fric_lag_mode == 1 ? 4 : 0),
-                       static_cast<double*>(ws));  // env blocks of the workspace: (V,16) elastic preconditioner blocks per env
+                       static_cast<double*>(ws), c->mat);  // env blocks of the workspace: (V,16) elastic preconditioner blocks per env
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? 0 : fail_hip(e, "fem_newton_lds_kernel");
   }
@@ -3213,23 +3360,24 @@ static int launch_newton(tacex_fem_ctx* c, double* x, const double* xt, const ui
   // x, p and the H.p accumulators in LDS when the summation order is free (atomic mode) and they fit next to the kernel's static
   // __shared__ (9 V doubles: ~2 200 vertices); all PCG vectors when 21 V doubles fit (~950 vertices); else global memory
   static const int stream_lds = getenv("TACEX_FEM_STREAM_LDS") ? atoi(getenv("TACEX_FEM_STREAM_LDS")) : 2;  // A/B hook: 0 none, 1 x / p / accumulators, 2 all PCG vectors
-  static size_t avail_s[64] = {};
+  static size_t avail_s[2][64] = {};
   size_t limit_s = 0;
-  ea = dynamic_lds_limit(reinterpret_cast<const void*>(fem_newton_kernel), avail_s, &limit_s);
+  auto kstream = mat ? fem_newton_kernel<true> : fem_newton_kernel<false>;
+  ea = dynamic_lds_limit(reinterpret_cast<const void*>(kstream), avail_s[mat ? 1 : 0], &limit_s);
   if (ea != hipSuccess) return fail_hip(ea, "hipFuncGetAttributes(fem_newton_kernel)");
   const bool lds_all = stream_lds != 1 && (size_t)21 * V * sizeof(double) <= limit_s;  // (TACEX_FEM_STREAM_LDS=1: x, p, accumulators only)
   const size_t lds_s = (size_t)(lds_all ? 21 : 9) * V * sizeof(double);
   const bool lds_sweep = stream_lds != 0 && atom && lds_s <= limit_s;
   if (lds_sweep) {
-    static size_t granted_s[64] = {};
-    const hipError_t es = ensure_dynamic_lds(reinterpret_cast<const void*>(fem_newton_kernel), lds_s, granted_s);
+    static size_t granted_s[2][64] = {};
+    const hipError_t es = ensure_dynamic_lds(reinterpret_cast<const void*>(kstream), lds_s, granted_s[mat ? 1 : 0]);
     if (es != hipSuccess) return fail_hip(es, "hipFuncSetAttribute(fem_newton_kernel)");
   }
   c->last_threads = 512;
   c->last_lds_mode = lds_sweep ? (lds_all ? 2 : 1) : 0;
-  hipLaunchKernelGGL(fem_newton_kernel, dim3(B), dim3(512), lds_sweep ? lds_s : 0, st, c->dev, x, xt, cons, aim, stats, static_cast<double*>(ws), pcg_max_iter,
+  hipLaunchKernelGGL(kstream, dim3(B), dim3(512), lds_sweep ? lds_s : 0, st, c->dev, x, xt, cons, aim, stats, static_cast<double*>(ws), pcg_max_iter,
                      pcg_tol_rate, ls_max_iter, dx_dev, dx_tol, step_info, stream_accumulate ? 1 : 0, fric ? xprev : nullptr, fric ? disp : nullptr,
-                     c->fric_lag_mode == 1 ? 1 : 0, lds_sweep ? (lds_all ? 2 : 1) : 0);
+                     c->fric_lag_mode == 1 ? 1 : 0, lds_sweep ? (lds_all ? 2 : 1) : 0, c->mat);
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? 0 : fail_hip(e, "fem_newton_kernel");
 }
@@ -3301,6 +3449,10 @@ int tacex_fem_set_affine_body(tacex_fem_ctx* c, int num_verts, const double* ver
                               double kappa, const double* pad_vertex_area_host, int num_pad_tris, const int32_t* pad_tris_host, double d_hat,
                               double stiffness, double ground_height, int enable_ground, int kinematic) {
   if (!c) { set_error("tacex_fem_set_affine_body: null context"); return 2; }
+  if (num_verts != 0 && c->mat.n > 0) {
+    set_error("tacex_fem_set_affine_body: not implemented for a scene with a material library (tacex_fem_set_material_library)");
+    return 2;
+  }
   bool synced = false;
   BallDev& bd = c->ball;
   fem_release(c, bd.Y, &synced); fem_release(c, bd.tri, &synced); fem_release(c, bd.area, &synced);
@@ -3495,11 +3647,11 @@ int tacex_fem_ball_step(tacex_fem_ctx* c, double* x, double* v, double* q, doubl
     static size_t granted_a[2][64] = {};
     const bool asm_atom = !c->deterministic;
     const size_t lds_a = ((size_t)3 * V + (asm_atom ? (size_t)15 * V : 0)) * sizeof(double);
-    auto ka = asm_atom ? fem_assemble_blocks_kernel<true> : fem_assemble_blocks_kernel<false>;
+    auto ka = asm_atom ? fem_assemble_blocks_kernel<true, false> : fem_assemble_blocks_kernel<false, false>;
     hipError_t ea = hipSetDevice(c->device);
     if (ea == hipSuccess) ea = ensure_dynamic_lds(reinterpret_cast<const void*>(ka), lds_a, granted_a[asm_atom ? 1 : 0]);
     if (ea != hipSuccess) return fail_hip(ea, "hipFuncSetAttribute(fem_assemble_blocks_kernel)");
-    hipLaunchKernelGGL(ka, dim3(B), dim3(512), lds_a, st, c->dev_nwt, x, blk, static_cast<const double*>(nullptr), 0.0);
+    hipLaunchKernelGGL(ka, dim3(B), dim3(512), lds_a, st, c->dev_nwt, x, blk, static_cast<const double*>(nullptr), 0.0, c->mat);
   }
   auto kern = ball_threads() == 256 ? fem_ball_newton_kernel<256> : fem_ball_newton_kernel<512>;
   hipLaunchKernelGGL(kern, dim3(B), dim3(ball_threads()), ball_lds_bytes(c->dev.V), st, c->dev, c->ball, x, xt, q, qt, cons, aim, static_cast<double*>(ws), pcg_max_iter,

@@ -11,7 +11,7 @@ import numpy as np
 import torch
 
 from .uipc_attachments import UipcIsaacAttachments, UipcIsaacAttachmentsCfg
-from .uipc_object import UipcObject, UipcObjectCfg, gelpad_box_mesh
+from .uipc_object import GelMaterialCfg, UipcObject, UipcObjectCfg, gelpad_box_mesh
 from .uipc_sim import UipcSim, UipcSimCfg
 
 
@@ -37,14 +37,18 @@ class FemGelpad:
     stepped with UipcSim.step (backward Euler: the whole Newton loop - matrix-free PCG, CCD filter, line search - in one HIP launch)."""
 
     def __init__(self, B, dev, max_newton_iter: int = 8, motion: str = "breathing", side_stream: bool = False, d_hat: float | None = None,
-                 cfg: UipcSimCfg | None = None, friction_lag: str | None = None, mesh: tuple[int, int, int] = (8, 10, 4)):
+                 cfg: UipcSimCfg | None = None, friction_lag: str | None = None, mesh: tuple[int, int, int] = (8, 10, 4),
+                 materials: list | None = None, material_ids=None, gel: GelMaterialCfg | None = None):
         """motion: "breathing" - the indenter presses in and retreats to the edge of the barrier zone every 21 steps; "rolling" - it
         stays on the pad like the ball of the reference's ball-rolling scenes: the depth varies between 0.3 and 0.8 of the env's
         maximum while the sphere slides sideways by up to +-0.5 mm (friction drags the surface along).  The half of the period in
         which the indenter RETREATS is the solver's harder regime: the pad follows it up the steeply nonlinear barrier.
         d_hat: width of the barrier zone; None = UipcSimCfg's default 1e-3 (uipc_sim.py:103-124 of the reference), 5e-4 = what the
         reference's own UIPC scenes set (ball_rolling_uipc.py:71-75, ball_rolling_tactile_rgb_uipc.py:220-224).
-        cfg: a UipcSimCfg to use instead of the defaults (tolerance studies in tests/test_fem_gpu.py)."""
+        cfg: a UipcSimCfg to use instead of the defaults (tolerance studies in tests/test_fem_gpu.py).
+        materials / material_ids: a gel material library and the material of every env (`UipcSim.set_materials`): mixed pads in one scene.
+        gel: ONE material for every env without a library - the gelpad object's `StableNeoHookeanCfg` / `mass_density` and the scene's
+        `contact.default_friction_ratio` are taken from it (the uniform scene an env of a library is compared with)."""
         assert motion in ("breathing", "rolling")
         self.motion = motion
         # side_stream: the scene driver and the FEM step run on a HIP stream of their own and `sim.step_done` marks their end, so that
@@ -62,8 +66,17 @@ class FemGelpad:
             cfg.contact.friction_lag = friction_lag
         self.d_hat = float(cfg.contact.d_hat)
         self.sim = UipcSim(cfg, num_envs=B)
-        self.gelpad = UipcObject(UipcObjectCfg(mesh_points=P, mesh_tets=T), self.sim)
+        ocfg = UipcObjectCfg(mesh_points=P, mesh_tets=T)
+        if gel is not None:
+            assert materials is None, "gel = one material for all envs, materials = a library: not both"
+            ocfg.constitution_cfg = UipcObjectCfg.StableNeoHookeanCfg(youngs_modulus=gel.youngs_modulus, poisson_rate=gel.poisson_rate)
+            ocfg.mass_density = gel.mass_density
+            if gel.friction_ratio is not None:
+                cfg.contact.default_friction_ratio = float(gel.friction_ratio)
+        self.gelpad = UipcObject(ocfg, self.sim)
         self.sim.setup_sim(constraint_strength_ratio=1000.0)  # benchmark env value (envs/ball_rolling_uipc.py:120-125)
+        if materials is not None:
+            self.sim.set_materials(materials, material_ids)
         self.num_tets, self.num_verts = len(T), len(P)
         size = P.max(0) - P.min(0)
         body = np.array([size[0] / 2, size[1] / 2, -0.001])  # the sensor case: a plate hugging the back face

@@ -82,6 +82,20 @@ class UipcObjectCfg:
     attachment_cfg: object = None
 
 
+@configclass
+class GelMaterialCfg:
+    """One gel of a material library (`UipcSim.set_materials`): the per-object fields of the reference - `StableNeoHookeanCfg` and
+    `mass_density` (uipc_object.py:54-92), same units and defaults - and the friction ratio of its contact element."""
+
+    youngs_modulus: float = 0.01
+    """in [MPa]"""
+    poisson_rate: float = 0.49
+    mass_density: float = 1e3
+    """in [kg/m^3]"""
+    friction_ratio: float | None = None
+    """None: `UipcSimCfg.contact.default_friction_ratio`; `contact.enable_friction = False` turns friction off for every material."""
+
+
 class UipcObject:
     """Holds the mesh + material of one deformable object replicated over all envs of a UipcSim."""
 

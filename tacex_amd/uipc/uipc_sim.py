@@ -178,6 +178,7 @@ class UipcSim:
         self._ws = torch.empty(lib.tacex_fem_workspace_bytes(h, B), dtype=torch.uint8, device=dev)
         self._g = torch.tensor(self.cfg.gravity, dtype=torch.float64, device=dev)
         self._body = None
+        self.materials = self.material_ids = None
         if body:
             self._setup_affine_body(body[0])
 
@@ -344,14 +345,67 @@ class UipcSim:
         self.indenter_mesh_ids.copy_(torch.from_numpy(ids))
 
     def _check_mesh_ids(self, mesh_ids, num_meshes) -> np.ndarray:
-        if mesh_ids is None:
+        return self._check_ids(mesh_ids, num_meshes, "mesh")
+
+    # -- gel material library: one material per env ------------------------------------------------------------------------------
+    materials = None
+    """The `GelMaterialCfg` list given to `set_materials` (None: no library, every env has the gelpad object's material)."""
+    material_ids = None
+    """(num_envs,) int32 device tensor the kernels read at every step (None without a library)."""
+
+    def set_materials(self, materials, ids=None):
+        """A LIBRARY of gel materials, one chosen per env: `materials` a list of `GelMaterialCfg`, `ids` (num_envs,) ints (None: every env
+        material 0).  An env of material k computes what a scene whose gelpad has `StableNeoHookeanCfg` / `mass_density` of material k
+        and `contact.default_friction_ratio` = its friction ratio computes - bit for bit with `linear_system.deterministic`
+        (`tacex_fem_set_material_library`; the coarse inverse of the preconditioner is built per material, `refresh_preconditioner`).
+        `self.material_ids` is the device tensor the kernels read: a task re-draws gels at a reset by writing it in place (or
+        `set_material_ids`, which validates) before `reset(env_ids)`.  An id changed WITHOUT a reset takes effect at the next step;
+        what the env carries over (friction lag, previous positions) then stems from its previous material.  An id outside the library
+        found on the device makes that env step with material 0 and flags it (`check_step()["bad_material_id_envs"]`).
+        None / [] removes the library."""
+        if self._handle is None:
+            raise RuntimeError("set_materials: call setup_sim() first (the library is built for the scene's mesh)")
+        if getattr(self, "_body", None) is not None and materials:
+            raise NotImplementedError("a material library is not implemented for a scene with an affine body (csrc/fem_ball.h)")
+        if not materials:
+            _lib.check(self._lib.tacex_fem_set_material_library(self._handle, 0, 0, 0, 0, 0), "tacex_fem_set_material_library")
+            _lib.check(self._lib.tacex_fem_set_material_ids(self._handle, 0), "tacex_fem_set_material_ids")
+            self.materials = self.material_ids = None
+            self._precond_dirty = True
+            return
+        mats = list(materials)
+        c = self.cfg.contact
+        fr = [0.0 if not c.enable_friction else float(c.default_friction_ratio if m.friction_ratio is None else m.friction_ratio) for m in mats]
+        for k, (m, f) in enumerate(zip(mats, fr)):
+            if not (m.youngs_modulus > 0.0) or not (-1.0 < m.poisson_rate < 0.5) or not (m.mass_density > 0.0) or not (f >= 0.0):
+                raise ValueError(f"set_materials: material {k} needs youngs_modulus > 0, -1 < poisson_rate < 0.5, mass_density > 0, friction_ratio >= 0")
+        host_ids = self._check_ids(ids, len(mats), "material")
+        E = np.array([m.youngs_modulus * 1e6 for m in mats], np.float64)  # MPa -> Pa, as setup_sim
+        nu = np.array([m.poisson_rate for m in mats], np.float64)
+        rho = np.array([m.mass_density for m in mats], np.float64)
+        f = np.array(fr, np.float64)
+        _lib.check(self._lib.tacex_fem_set_material_library(self._handle, len(mats), E.ctypes.data, nu.ctypes.data, rho.ctypes.data, f.ctypes.data),
+                   "tacex_fem_set_material_library")
+        self.materials = mats
+        self.material_ids = torch.from_numpy(host_ids).to(self.device)
+        _lib.check(self._lib.tacex_fem_set_material_ids(self._handle, _lib.ptr(self.material_ids)), "tacex_fem_set_material_ids")
+        self._precond_dirty = True  # one coarse inverse per material
+
+    def set_material_ids(self, ids):
+        """Writes new per-env material ids into `self.material_ids` (in stream order; checked on the host against the library)."""
+        if self.materials is None:
+            raise RuntimeError("set_material_ids: no material library (set_materials)")
+        self.material_ids.copy_(torch.from_numpy(self._check_ids(ids, len(self.materials), "material")))
+
+    def _check_ids(self, ids, count, what) -> np.ndarray:
+        if ids is None:
             return np.zeros(self.num_envs, np.int32)
-        ids = mesh_ids.detach().cpu().numpy() if isinstance(mesh_ids, torch.Tensor) else np.asarray(mesh_ids)
+        ids = ids.detach().cpu().numpy() if isinstance(ids, torch.Tensor) else np.asarray(ids)
         ids = ids.reshape(-1)
         if ids.shape != (self.num_envs,):
-            raise ValueError(f"mesh ids: need {self.num_envs} (one per env), got {ids.shape[0]}")
-        if not np.issubdtype(ids.dtype, np.integer) or (len(ids) and (ids.min() < 0 or ids.max() >= num_meshes)):
-            raise ValueError(f"mesh ids must be integers in [0, {num_meshes})")
+            raise ValueError(f"{what} ids: need {self.num_envs} (one per env), got {ids.shape[0]}")
+        if not np.issubdtype(ids.dtype, np.integer) or (len(ids) and (ids.min() < 0 or ids.max() >= count)):
+            raise ValueError(f"{what} ids must be integers in [0, {count})")
         return np.ascontiguousarray(ids, np.int32)
 
     def _mesh_gaps(self, x, ind):
@@ -528,8 +582,21 @@ class UipcSim:
         if nc > 64:
             raise ValueError(f"coarse grid {dims} has {nc} nodes (the kernel takes <= 64)")
         rest = torch.from_numpy(np.ascontiguousarray(P))[None].to(self.device)
-        _, _, h = self.element_terms(rest, energy=False, gradient=False)
-        He = h[0].cpu().numpy().reshape(12, 12, len(T)).transpose(2, 0, 1)
+        mats = self.materials
+        if mats is None:
+            _, _, h = self.element_terms(rest, energy=False, gradient=False)
+            He = h[0].cpu().numpy().reshape(12, 12, len(T)).transpose(2, 0, 1)
+        else:
+            # rest Hessians of EVERY material: one call of K envs at the rest state, env k reading material k through a K-element id
+            # array (the steps' own array is bound again right after)
+            kid = torch.arange(len(mats), dtype=torch.int32, device=self.device)
+            _lib.check(self._lib.tacex_fem_set_material_ids(self._handle, _lib.ptr(kid)), "tacex_fem_set_material_ids")
+            try:
+                _, _, h = self.element_terms(rest.repeat(len(mats), 1, 1).contiguous(), energy=False, gradient=False)
+                Hk = h.cpu().numpy()  # (synchronises: kid may go)
+            finally:
+                _lib.check(self._lib.tacex_fem_set_material_ids(self._handle, _lib.ptr(self.material_ids)), "tacex_fem_set_material_ids")
+            He = Hk[0].reshape(12, 12, len(T)).transpose(2, 0, 1)
         Dm = np.stack([P[T[:, 1]] - P[T[:, 0]], P[T[:, 2]] - P[T[:, 0]], P[T[:, 3]] - P[T[:, 0]]], -1)
         det = np.linalg.det(Dm)
         T = T.copy()
@@ -538,11 +605,26 @@ class UipcSim:
         mass = np.zeros(len(P))
         np.add.at(mass, T.reshape(-1), np.repeat(obj.cfg.mass_density * vol / 4.0, 4))
         cons = self.is_constrained[0].cpu().numpy().astype(np.float64)
+        if mats is not None:  # (material 0's tables also serve as the scene's: the same function and inputs a uniform scene of it uses)
+            mass = np.zeros(len(P))
+            np.add.at(mass, T.reshape(-1), np.repeat(mats[0].mass_density * vol / 4.0, 4))
         aci = np.ascontiguousarray(coarse_operator_inverse(He, T, mass, cons, self._strength, self.cfg.dt, node, w, nc))
         node, w = np.ascontiguousarray(node, np.int32), np.ascontiguousarray(w, np.float64)
         _lib.check(self._lib.tacex_fem_set_coarse_space(self._handle, nc, node.ctypes.data, w.ctypes.data, aci.ctypes.data),
                    "tacex_fem_set_coarse_space")
         self.coarse_space = (node, w, aci)  # what the library was given (tests hand the same tables to the oracle)
+        self.material_coarse_inverses = None
+        if mats is not None:
+            acis = [aci]
+            for k in range(1, len(mats)):
+                mass_k = np.zeros(len(P))
+                np.add.at(mass_k, T.reshape(-1), np.repeat(mats[k].mass_density * vol / 4.0, 4))
+                He_k = Hk[k].reshape(12, 12, len(T)).transpose(2, 0, 1)
+                acis.append(coarse_operator_inverse(He_k, T, mass_k, cons, self._strength, self.cfg.dt, node, w, nc))
+            acis = np.ascontiguousarray(np.stack(acis), np.float64)
+            _lib.check(self._lib.tacex_fem_set_material_coarse_inverses(self._handle, len(mats), acis.ctypes.data),
+                       "tacex_fem_set_material_coarse_inverses")
+            self.material_coarse_inverses = acis
 
     def _set_chains(self):
         ch = self.cfg.linear_system.vertex_chains
@@ -690,14 +772,16 @@ class UipcSim:
         documents the contract) and that vertex gets no restoring force; flag 2 = a line search found no decrease.  Informational:
         4 = the env dropped the coarse correction for the rest of the step, 8 = it met negative curvature and finished the step with
         the PSD-safe Hessian (csrc/fem_kernels.hip, kFemFlagCoarseOff / kFemFlagPsdSafe); 32 = its kind-4 row named a mesh id outside
-        the library (`set_indenter_meshes`): the env ran the step without an indenter ("bad_mesh_id_envs")."""
+        the library (`set_indenter_meshes`): the env ran the step without an indenter ("bad_mesh_id_envs"); 64 = its material id lay
+        outside the material library (`set_materials`): the env stepped with material 0 ("bad_material_id_envs")."""
         self.wait_for_step()  # a step enqueued on a side stream (FemGelpad(side_stream=True)): `.cpu()` only drains the CURRENT stream
         si = self.step_info.cpu().numpy()
         flags = si[:, 2].astype(np.int64)
         out = {"newton_iters": si[:, 0].astype(np.int64), "max_d": si[:, 1], "penetrating_envs": np.nonzero(flags & 1)[0],
                "line_search_failed_envs": np.nonzero(flags & 2)[0], "pcg_iters": si[:, 3].astype(np.int64),
                "coarse_dropped_envs": np.nonzero(flags & 4)[0], "psd_safe_envs": np.nonzero(flags & 8)[0],
-               "pair_list_overflow_envs": np.nonzero(flags & 16)[0], "bad_mesh_id_envs": np.nonzero(flags & 32)[0]}  # (affine-body scenes: a candidate list of csrc/fem_ball.h overflowed)
+               "pair_list_overflow_envs": np.nonzero(flags & 16)[0], "bad_mesh_id_envs": np.nonzero(flags & 32)[0],
+               "bad_material_id_envs": np.nonzero(flags & 64)[0]}  # (affine-body scenes: a candidate list of csrc/fem_ball.h overflowed)
         if raise_on_penetration and len(out["penetrating_envs"]):
             raise RuntimeError(f"gelpad penetrated by its indenter in envs {out['penetrating_envs'][:8].tolist()}: the indenter moved by "
                                "more than the contact gap between two steps (see UipcSim.set_contact_indenters)")
