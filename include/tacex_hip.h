@@ -32,7 +32,7 @@ extern "C" {
 #endif
 
 #define TACEX_MAX_LEVELS 8
-#define TACEX_ABI_VERSION 19
+#define TACEX_ABI_VERSION 20
 
 typedef struct tacex_taxim_ctx tacex_taxim_ctx;
 typedef struct tacex_fots_ctx tacex_fots_ctx;
@@ -674,6 +674,43 @@ int tacex_fem_marker_flow(const double* x_dev, const int64_t* surf_ids_dev, cons
                           const int32_t* tri_dev, const double* weight_dev, double fx, double fy, double cx, double cy,
                           const double* init_uv_dev, const int64_t* select_dev, double normalize_div, double* curr_uv_dev, double* flow_dev,
                           float* flow_f32_dev, int num_envs, int num_verts, int num_markers, int num_selected, void* stream);
+
+/* gen_marker_flow with the whole randomisation interface of VT:354-413 (random grid, lost tracking, noise, random subset) for a batch in
+ * ONE launch, every env on a marker pattern and a random stream of its own: a MARKER PATTERN LIBRARY.
+ *   Library (built once by the caller): num_patterns = P >= 1 patterns, pattern k = the k-th draw of the marker grid with its triangles and
+ *   barycentric weights: lib_tri_dev (P,Mmax,3) int32 SURFACE-local vertex ids, lib_weight_dev (P,Mmax,3) f64, lib_count_dev (P) int32;
+ *   rows >= count[k] are padding and never read.  max_markers = Mmax <= 1024 (one env's markers are staged in LDS).
+ *   pattern_ids_dev (B) int32, read at every launch (a task re-draws an env's pattern by writing it in place); an id outside [0, P) reads
+ *   pattern 0.  draws_dev (B) uint32: the env's draw number t; the kernel uses it and stores t + 1.  Writing it back reproduces a draw.
+ *   Per env e with k = pattern_ids[e], t = draws[e]:
+ *   1. every marker m < count[k]: initial (u, v) from ref_surf_cam_dev (B,Vs,3; the reference surface in the camera frame) with the
+ *      arithmetic of tacex_fem_marker_uv, current (u, v) from x_dev with the arithmetic of tacex_fem_marker_flow - bit-equal to both;
+ *   2. in-image mask on the env's own initial projection: 5 < u < image_height and 5 < v < image_width (sic: the reference's axis swap);
+ *   3. lost tracking: m survives iff U > lose_probability;
+ *   4. noise: sigma * N added to init u, init v, current u, current v of every survivor (four independent normals), before normalisation;
+ *   5. selection among the n survivors, K = num_selected: n >= K: the survivor whose (key, m) pair has rank r < K in ascending order goes
+ *      to slot r (a uniform K-subset in random order); 0 < n < K: the survivors in marker order, padded by repeating the last; n = 0: zeros;
+ *      then values / normalize_div - 1 if normalize_div > 0, the zero case included;
+ *   6. outputs: flow_dev (B,2,K,2) f64 and / or flow_f32_dev (B,2,K,2) f32 (at least one); curr_uv_dev (B,Mmax,2) f64 [nullable]: all
+ *      current projections, noise-free, rows >= count zero; num_tracked_dev (B) int32 [nullable] = n;
+ *   7. draws[e] = t + 1.
+ *   Random numbers: Philox4x32-10 (tacex_philox4x32), key (seed & 0xffffffff, seed >> 32), counter (m, stream, e, t).
+ *     stream 0: word 0 -> U, word 1 -> subset key;  stream 1: words (0,1) -> Box-Muller pair for (init u, init v), (2,3) -> (current u, v).
+ *     uniform of a word w = (w + 0.5) * 2^-32 in f64; Box-Muller of (a, b) = sqrt(-2 ln a) cos(2 pi b), sqrt(-2 ln a) sin(2 pi b) in f64.
+ *   The draws of an env depend on (seed, e, t, m) alone - not on B, the other envs or the launch shape; a sharded job gives every rank
+ *   its own seed.
+ * Returns 2 before any HIP call for NULL arguments, P < 1, Mmax outside [1, 1024], lose_probability outside [0, 1], negative sigma. */
+int tacex_fem_marker_flow_library(const double* x_dev, const int64_t* surf_ids_dev, const double* cam_pos_dev, const double* cam_rot_inv_dev,
+                                  const double* ref_surf_cam_dev, const int32_t* lib_tri_dev, const double* lib_weight_dev,
+                                  const int32_t* lib_count_dev, int num_patterns, int max_markers, const int32_t* pattern_ids_dev,
+                                  uint32_t* draws_dev, uint64_t seed, double fx, double fy, double cx, double cy, double lose_probability,
+                                  double sigma, int image_height, int image_width, double normalize_div, double* curr_uv_dev,
+                                  double* flow_dev, float* flow_f32_dev, int32_t* num_tracked_dev, int num_envs, int num_verts,
+                                  int num_surf_verts, int num_selected, void* stream);
+
+/* Philox4x32-10 (Random123 constants and round function) on the HOST: the function the marker kernel calls, so that a CPU test pins the
+ * generator.  ctr (4), key (2) -> out (4) uint32. */
+int tacex_philox4x32(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]);
 
 #ifdef __cplusplus
 }

@@ -11,7 +11,7 @@ from pathlib import Path
 from ._build import LIB, build_library
 
 MAX_LEVELS = 8
-ABI_VERSION = 19  # TACEX_ABI_VERSION of include/tacex_hip.h; bumped whenever a signature or struct layout changes
+ABI_VERSION = 20  # TACEX_ABI_VERSION of include/tacex_hip.h; bumped whenever a signature or struct layout changes
 FLAG_NO_SHIFT = 1
 FLAG_HAVE_FRAME_MIN = 2
 FLAG_WITH_SHADOW = 4
@@ -167,6 +167,9 @@ SIGNATURES = {
     "tacex_fem_set_attachment_targets": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "tacex_fem_marker_uv": (_i, [_vp, _vp, _vp, _d, _d, _d, _d, _vp, _i, _i, _i, _vp]),
     "tacex_fem_marker_flow": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _d, _d, _d, _d, _vp, _vp, _d, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "tacex_fem_marker_flow_library": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, C.c_uint64, _d, _d, _d, _d, _d, _d, _i, _i, _d,
+                                           _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "tacex_philox4x32": (_i, [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
 }
 
 _lib = None

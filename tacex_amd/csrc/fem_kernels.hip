@@ -29,6 +29,7 @@
 
 #include "tacex_hip.h"
 #include "tacex_internal.h"
+#include "tacex_philox.h"
 
 namespace tacex {
 
@@ -2587,6 +2588,156 @@ __global__ __launch_bounds__(256) void fem_marker_flow_kernel(const double* __re
   }
 }
 
+// gen_marker_flow with the reference's whole randomisation interface (VT:354-413: random grid, lost tracking, noise, random subset) for a
+// batch, in ONE launch and with every env on a marker pattern and a random stream of its own.  A library of P marker patterns (grid draws of
+// gen_marker_grid + gen_marker_weight, built once on the host) lies on the device; env e follows pattern k = pattern_ids[e] (an id outside
+// [0, P) reads pattern 0) and takes draw number t = draws[e].  One workgroup per env:
+//   1. every marker m < count[k]: initial (u, v) from the reference surface (fem_marker_uv_kernel's arithmetic) and current (u, v) from the
+//      FEM state (fem_marker_flow_kernel's arithmetic);
+//   2. in-image mask on the env's OWN initial projection, 5 < u < H and 5 < v < W (sic, VT:382-387);
+//   3. lost tracking: m survives iff U > lose_prob;  4. sigma * N added to the four values of a survivor (four independent normals);
+//   5. n survivors: n >= K: the survivor whose (key, m) has rank r < K goes to slot r (a uniform K-subset in random order); 0 < n < K: the
+//      survivors in marker order, padded with the last; n == 0: zeros;  then / norm_div - 1 if norm_div > 0, the zero case included;
+//   6. draws[e] = t + 1.
+// Random numbers: Philox4x32-10, key (seed lo, seed hi), counter (m, stream, e, t): stream 0 word 0 -> U, word 1 -> subset key; stream 1
+// words (0,1) -> Box-Muller pair for the initial (u, v), words (2,3) -> for the current (u, v).  Nothing depends on B or the launch shape.
+// LDS: 40 B per marker - the survivor's four values by marker id, and the compact (marker-ordered) survivor list with its keys.
+__global__ __launch_bounds__(256) void fem_marker_flow_library_kernel(
+    const double* __restrict__ xg, const long long* __restrict__ surf_ids, const double* __restrict__ cam_pos, const double* __restrict__ cam_rot_inv,
+    const double* __restrict__ ref_cam, const int* __restrict__ lib_tri, const double* __restrict__ lib_wgt, const int* __restrict__ lib_count,
+    int P, int Mmax, const int* __restrict__ pattern_ids, unsigned int* __restrict__ draws, unsigned int seed_lo, unsigned int seed_hi, double fx,
+    double fy, double cx, double cy, double lose_prob, double sigma, double img_h, double img_w, double norm_div, double* __restrict__ curr_uv,
+    double* __restrict__ flow, float* __restrict__ flow32, int* __restrict__ num_tracked, int V, int Vs, int K) {
+  extern __shared__ double mlib_smem[];
+  double* s_val = mlib_smem;                                              // (Mmax,4) init u, init v, current u, current v (noise added)
+  unsigned int* s_key = reinterpret_cast<unsigned int*>(s_val + (size_t)Mmax * 4);  // (Mmax) subset key of the p-th survivor
+  int* s_list = reinterpret_cast<int*>(s_key + Mmax);                      // (Mmax) marker id of the p-th survivor
+  __shared__ int s_cnt[16];                                               // survivors per (pass, wave)
+  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  int pat = pattern_ids[b];
+  if (pat < 0 || pat >= P) pat = 0;
+  int M = lib_count[pat];
+  M = M < 0 ? 0 : (M > Mmax ? Mmax : M);
+  const int* tri = lib_tri + (size_t)pat * Mmax * 3;
+  const double* wgt = lib_wgt + (size_t)pat * Mmax * 3;
+  const unsigned int t = draws[b];
+  const unsigned int key[2] = {seed_lo, seed_hi};
+  const double* x = xg + (size_t)b * V * 3;
+  const double* cp = cam_pos + (size_t)b * 3;
+  const double* R = cam_rot_inv + (size_t)b * 9;
+  const double* p = ref_cam + (size_t)b * Vs * 3;
+  bool keep[4];
+  unsigned int skey[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int mi = tid + j * 256;
+    keep[j] = false;
+    skey[j] = 0;
+    if (mi < M) {
+      int tv[3];
+#pragma unroll
+      for (int k = 0; k < 3; ++k) {
+        const int v = tri[mi * 3 + k];
+        tv[k] = v < 0 ? 0 : (v >= Vs ? Vs - 1 : v);
+      }
+      // initial projection: fem_marker_uv_kernel
+      double q0[3] = {0, 0, 0};
+#pragma unroll
+      for (int k = 0; k < 3; ++k) {
+        const int v = tv[k];
+        const double w = wgt[mi * 3 + k];
+        q0[0] += w * p[v * 3 + 0]; q0[1] += w * p[v * 3 + 1]; q0[2] += w * p[v * 3 + 2];
+      }
+      double iu = fx * q0[0] / q0[2] + cx, iv = fy * q0[1] / q0[2] + cy;
+      // current projection: fem_marker_flow_kernel
+      double q[3] = {0.0, 0.0, 0.0};
+#pragma unroll
+      for (int k = 0; k < 3; ++k) {
+        const long long v = surf_ids[tv[k]];
+        const double w = wgt[mi * 3 + k];
+        const double d0 = x[v * 3] - cp[0], d1 = x[v * 3 + 1] - cp[1], d2 = x[v * 3 + 2] - cp[2];
+#pragma unroll
+        for (int i = 0; i < 3; ++i) q[i] += w * (R[i * 3] * d0 + R[i * 3 + 1] * d1 + R[i * 3 + 2] * d2);
+      }
+      double u = fx * q[0] / q[2] + cx, vv = fy * q[1] / q[2] + cy;
+      if (curr_uv) { curr_uv[((size_t)b * Mmax + mi) * 2] = u; curr_uv[((size_t)b * Mmax + mi) * 2 + 1] = vv; }
+      const unsigned int c0[4] = {(unsigned int)mi, 0u, (unsigned int)b, t};
+      unsigned int r0[4];
+      philox4x32_10(c0, key, r0);
+      keep[j] = iu > 5.0 && iu < img_h && iv > 5.0 && iv < img_w && philox_uniform(r0[0]) > lose_prob;
+      skey[j] = r0[1];
+      if (keep[j] && sigma > 0.0) {
+        const unsigned int c1[4] = {(unsigned int)mi, 1u, (unsigned int)b, t};
+        unsigned int r1[4];
+        philox4x32_10(c1, key, r1);
+        const double kTwoPi = 6.283185307179586;
+        const double ra = sqrt(-2.0 * log(philox_uniform(r1[0]))), ta = kTwoPi * philox_uniform(r1[1]);
+        const double rb = sqrt(-2.0 * log(philox_uniform(r1[2]))), tb = kTwoPi * philox_uniform(r1[3]);
+        const double n0 = ra * cos(ta), n1 = ra * sin(ta), n2 = rb * cos(tb), n3 = rb * sin(tb);
+        // (products rounded on their own, then added: what the NumPy restatement computes)
+        iu = __dadd_rn(iu, __dmul_rn(sigma, n0)); iv = __dadd_rn(iv, __dmul_rn(sigma, n1));
+        u = __dadd_rn(u, __dmul_rn(sigma, n2)); vv = __dadd_rn(vv, __dmul_rn(sigma, n3));
+      }
+      s_val[mi * 4] = iu; s_val[mi * 4 + 1] = iv; s_val[mi * 4 + 2] = u; s_val[mi * 4 + 3] = vv;
+    } else if (mi < Mmax && curr_uv) {
+      curr_uv[((size_t)b * Mmax + mi) * 2] = 0.0; curr_uv[((size_t)b * Mmax + mi) * 2 + 1] = 0.0;
+    }
+  }
+  // survivor compaction in marker order: a workgroup prefix sum over (pass, wave) ballots
+  unsigned long long bal[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    bal[j] = __ballot(keep[j]);
+    if (lane == 0) s_cnt[j * 4 + wave] = __popcll(bal[j]);
+  }
+  __syncthreads();
+  int n = 0;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) n += s_cnt[i];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    if (keep[j]) {
+      int pos = __popcll(bal[j] & ((1ull << lane) - 1ull));
+      for (int i = 0; i < j * 4 + wave; ++i) pos += s_cnt[i];
+      s_list[pos] = tid + j * 256;
+      s_key[pos] = skey[j];
+    }
+  }
+  __syncthreads();
+  if (tid == 0) {
+    draws[b] = t + 1u;
+    if (num_tracked) num_tracked[b] = n;
+  }
+  double* fl = flow ? flow + (size_t)b * 4 * K : nullptr;
+  float* fl32 = flow32 ? flow32 + (size_t)b * 4 * K : nullptr;
+  auto put = [&](int slot, const double* v4) {  // v4: init u, init v, current u, current v; nullptr: zeros
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      double val = v4 ? v4[c] : 0.0;
+      if (norm_div > 0.0) val = val / norm_div - 1.0;
+      const size_t o = ((size_t)(c >> 1) * K + slot) * 2 + (c & 1);
+      if (fl) fl[o] = val;
+      if (fl32) fl32[o] = (float)val;
+    }
+  };
+  if (n >= K) {
+    for (int ps = tid; ps < n; ps += 256) {
+      const unsigned int kp = s_key[ps];
+      int r = 0;
+      for (int qs = 0; qs < n; ++qs) {
+        const unsigned int kq = s_key[qs];
+        r += (kq < kp || (kq == kp && qs < ps)) ? 1 : 0;  // (survivors are listed in marker order: qs < ps is m_q < m_p)
+      }
+      if (r < K) put(r, s_val + (size_t)s_list[ps] * 4);
+    }
+  } else if (n > 0) {
+    const double* last = s_val + (size_t)s_list[n - 1] * 4;
+    for (int s = tid; s < K; s += 256) put(s, s < n ? s_val + (size_t)s_list[s] * 4 : last);
+  } else {
+    for (int s = tid; s < K; s += 256) put(s, nullptr);
+  }
+}
+
 }  // namespace tacex
 
 using namespace tacex;
@@ -3738,6 +3889,39 @@ int tacex_fem_marker_flow(const double* x, const int64_t* surf_ids, const double
                      reinterpret_cast<const long long*>(select), normalize_div, curr_uv, flow, flow_f32, V, M, K);
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? 0 : fail_hip(e, "fem_marker_flow_kernel");
+}
+
+int tacex_fem_marker_flow_library(const double* x, const int64_t* surf_ids, const double* cam_pos, const double* cam_rot_inv,
+                                  const double* ref_surf_cam, const int32_t* lib_tri, const double* lib_wgt, const int32_t* lib_count,
+                                  int P, int Mmax, const int32_t* pattern_ids, uint32_t* draws, uint64_t seed, double fx, double fy, double cx,
+                                  double cy, double lose_prob, double sigma, int img_h, int img_w, double normalize_div, double* curr_uv,
+                                  double* flow, float* flow_f32, int32_t* num_tracked, int B, int V, int Vs, int K, void* stream) {
+  if (!x || !surf_ids || !cam_pos || !cam_rot_inv || !ref_surf_cam || !lib_tri || !lib_wgt || !lib_count || !pattern_ids || !draws ||
+      (!flow && !flow_f32)) {
+    set_error("tacex_fem_marker_flow_library: null argument");
+    return 2;
+  }
+  if (P < 1) { set_error("tacex_fem_marker_flow_library: %d patterns (a library holds at least one)", P); return 2; }
+  if (Mmax < 1 || Mmax > 1024) {
+    set_error("tacex_fem_marker_flow_library: %d markers per pattern (1 to 1024: one env's markers are staged in LDS)", Mmax);
+    return 2;
+  }
+  if (!(lose_prob >= 0.0 && lose_prob <= 1.0)) { set_error("tacex_fem_marker_flow_library: lose-tracking probability %g outside [0, 1]", lose_prob); return 2; }
+  if (!(sigma >= 0.0)) { set_error("tacex_fem_marker_flow_library: negative noise sigma %g", sigma); return 2; }
+  if (B <= 0 || K <= 0) return 0;
+  if (V <= 0 || Vs <= 0) { set_error("tacex_fem_marker_flow_library: %d vertices, %d surface vertices", V, Vs); return 2; }
+  hipLaunchKernelGGL(fem_marker_flow_library_kernel, dim3(B), dim3(256), (size_t)Mmax * 40, (hipStream_t)stream, x,
+                     reinterpret_cast<const long long*>(surf_ids), cam_pos, cam_rot_inv, ref_surf_cam, lib_tri, lib_wgt, lib_count, P, Mmax,
+                     pattern_ids, draws, (unsigned int)(seed & 0xffffffffull), (unsigned int)(seed >> 32), fx, fy, cx, cy, lose_prob, sigma,
+                     (double)img_h, (double)img_w, normalize_div, curr_uv, flow, flow_f32, num_tracked, V, Vs, K);
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? 0 : fail_hip(e, "fem_marker_flow_library_kernel");
+}
+
+int tacex_philox4x32(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]) {
+  if (!ctr || !key || !out) { set_error("tacex_philox4x32: null argument"); return 2; }
+  philox4x32_10(ctr, key, out);  // the function fem_marker_flow_library_kernel calls, compiled for the host
+  return 0;
 }
 
 }  // extern "C"

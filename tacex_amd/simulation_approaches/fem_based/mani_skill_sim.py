@@ -42,11 +42,13 @@ class ManiSkillSimulator(GelSightSimulator):
             marker_translation_range=self.cfg.marker_translation_range, marker_pos_shift_range=self.cfg.marker_pos_shift_range,
             marker_random_noise=self.cfg.marker_random_noise,
             marker_lose_tracking_probability=self.cfg.marker_lose_tracking_probability, normalize=self.cfg.normalize,
-            num_markers=self.cfg.marker_params.num_markers, camera_params=self.cfg.camera_params)
+            num_markers=self.cfg.marker_params.num_markers, camera_params=self.cfg.camera_params,
+            marker_patterns=self.cfg.marker_patterns, seed=self.cfg.marker_seed)
         self.marker_data = torch.zeros((self._num_envs, 2, self.cfg.marker_params.num_markers, 2), device=self._device)
 
     def marker_motion_simulation(self):
-        # static marker grid (the shipped cfgs): one launch from the FEM state straight into marker_data; otherwise the general path
+        # static marker grid (the shipped cfgs) or a marker pattern library: one launch from the FEM state straight into marker_data;
+        # otherwise the general path
         if self.marker_data.dtype == torch.float32 and self.marker_motion_sim.gen_marker_flow_fused(out_f32=self.marker_data) is not None:
             return self.marker_data
         self.marker_data[:] = self.marker_motion_sim.gen_marker_flow().to(self.marker_data.dtype)

@@ -16,6 +16,11 @@ class ManiSkillSimulatorCfg(GelSightSimulatorCfg):
     marker_pos_shift_range: tuple = (0.0, 0.0)
     marker_random_noise: float = 0.0
     marker_lose_tracking_probability: float = 0.0
+    marker_patterns: int = 0
+    """> 0: a library of that many marker patterns drawn from the ranges above at construction; every env follows the pattern its entry of
+    `marker_motion_sim.pattern_ids` names, and lost tracking / noise / the random subset are drawn per env on the device (one launch)."""
+    marker_seed: int = 0
+    """Seed of the pattern draws and of the device's random stream (a sharded job gives every rank its own)."""
     normalize: bool = False
     marker_flow_size: int = 128
     camera_params: tuple = (340, 325, 160, 125, 0.0)

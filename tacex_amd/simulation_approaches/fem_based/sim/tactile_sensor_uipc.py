@@ -9,6 +9,10 @@ project with a pinhole camera (VT:331-352) and mask / pad to `num_markers` (VT:3
 Here the grid + weights are host-side set-up (computed once while the random ranges are degenerate - the default - and
 re-drawn per call otherwise, like the reference), and the per-step part - barycentric points + projection for ALL envs -
 is one HIP launch (`tacex_fem_marker_uv`).
+
+With `marker_patterns = P > 0` the randomisation runs on the device instead (a MARKER PATTERN LIBRARY): P grids + weights are
+drawn once at construction, every env follows the pattern its entry of `pattern_ids` names, and lost tracking, noise and the random subset
+are drawn per env and per call by the kernel itself (`tacex_fem_marker_flow_library`, Philox4x32-10) - one launch per call, no host RNG.
 """
 from __future__ import annotations
 
@@ -92,6 +96,59 @@ def gen_marker_weight(marker_pts_xy: np.ndarray, surface_pts: np.ndarray, triang
     return idx, wgt
 
 
+MAX_PATTERN_MARKERS = 1024  # tacex_fem_marker_flow_library stages one env's markers in LDS
+
+
+class MarkerPatternLibrary:
+    """P marker patterns: `tri` (P,Mmax,3) int32 surface-local vertex ids, `wgt` (P,Mmax,3) float64 barycentric weights, `count` (P,) int32
+    markers per pattern (rows >= count[k] are padding).  NumPy arrays from `build_marker_patterns`; `.to(device)` gives torch tensors."""
+
+    def __init__(self, tri, wgt, count):
+        self.tri, self.wgt, self.count = tri, wgt, count
+        self.num_patterns, self.max_markers = int(tri.shape[0]), int(tri.shape[1])
+
+    def to(self, device) -> "MarkerPatternLibrary":
+        return MarkerPatternLibrary(*(torch.as_tensor(a).to(device).contiguous() for a in (self.tri, self.wgt, self.count)))
+
+
+def build_marker_patterns(num_patterns: int, surface_pts: np.ndarray, triangles: np.ndarray, marker_interval_range=(2.0625, 2.0625),
+                          marker_rotation_range=0.0, marker_translation_range=(0.0, 0.0), marker_pos_shift_range=(0.0, 0.0),
+                          rng=None) -> MarkerPatternLibrary:
+    """Pattern k = the k-th draw of `gen_marker_grid(ranges, rng)` followed by `gen_marker_weight(grid, surface_pts, triangles)`: all draws
+    from the one `rng`, in pattern order, the way `VisionTactileSensorUIPC._setup` draws a grid per call.  Host work, done once."""
+    if int(num_patterns) != num_patterns or num_patterns < 1:
+        raise ValueError(f"a marker pattern library holds at least one pattern, got {num_patterns}")
+    rng = np.random if rng is None else rng
+    pats = []
+    for k in range(int(num_patterns)):
+        grid = gen_marker_grid(marker_interval_range, marker_rotation_range, marker_translation_range, marker_pos_shift_range, rng)
+        idx, wgt = gen_marker_weight(grid, surface_pts, triangles)
+        if idx.shape[0] > MAX_PATTERN_MARKERS:
+            raise ValueError(f"marker pattern {k} has {idx.shape[0]} markers over the surface; the pattern library takes at most "
+                             f"{MAX_PATTERN_MARKERS} per pattern (the kernel stages one env's markers in LDS): widen marker_interval_range")
+        pats.append((idx, wgt))
+    mmax = max(1, max(i.shape[0] for i, _ in pats))
+    tri = np.zeros((len(pats), mmax, 3), dtype=np.int32)
+    w = np.zeros((len(pats), mmax, 3), dtype=np.float64)
+    for k, (i, g) in enumerate(pats):
+        tri[k, :i.shape[0]], w[k, :i.shape[0]] = i, g
+    return MarkerPatternLibrary(tri, w, np.array([i.shape[0] for i, _ in pats], dtype=np.int32))
+
+
+def check_pattern_ids(ids, num_envs: int, num_patterns: int) -> np.ndarray:
+    """(num_envs,) int32 pattern ids, validated on the host: integers in [0, num_patterns).  None: arange(num_envs) % num_patterns."""
+    if ids is None:
+        return (np.arange(num_envs) % num_patterns).astype(np.int32)
+    if isinstance(ids, torch.Tensor):
+        ids = ids.detach().cpu().numpy()
+    a = np.asarray(ids)
+    if a.shape != (num_envs,) or not np.issubdtype(a.dtype, np.integer):
+        raise ValueError(f"pattern_ids must be {num_envs} integers (one per env), got shape {a.shape} dtype {a.dtype}")
+    if a.size and (a.min() < 0 or a.max() >= num_patterns):
+        raise ValueError(f"pattern_ids outside the library of {num_patterns} patterns: min {a.min()}, max {a.max()}")
+    return a.astype(np.int32)
+
+
 def quat_to_matrix(q: torch.Tensor) -> torch.Tensor:
     """(…,4) wxyz unit quaternion -> (…,3,3)."""
     w, x, y, z = q.unbind(-1)
@@ -106,7 +163,7 @@ class VisionTactileSensorUIPC:
                  tactile_img_width=320, tactile_img_height=240, marker_interval_range=(2.0625, 2.0625),
                  marker_rotation_range=0.0, marker_translation_range=(0.0, 0.0), marker_pos_shift_range=(0.0, 0.0),
                  marker_random_noise=0.0, marker_lose_tracking_probability=0.0, normalize=False, num_markers=128,
-                 camera_params=(340, 325, 160, 125, 0.0), seed: int = 0, **kwargs):
+                 camera_params=(340, 325, 160, 125, 0.0), seed: int = 0, marker_patterns: int = 0, **kwargs):
         self.gelpad_obj = uipc_gelpad
         self.uipc_sim = uipc_sim
         self.tactile_img_width, self.tactile_img_height = tactile_img_width, tactile_img_height
@@ -141,6 +198,51 @@ class VisionTactileSensorUIPC:
         self._cached = None
         self._static_flow = None
         self._lib = _lib.load_library()
+        # marker pattern library: the randomisation on the device, per env (module docstring)
+        self.patterns = None
+        self.pattern_ids = self.marker_draws = self.num_tracked = None
+        if marker_patterns:
+            if not 0.0 <= marker_lose_tracking_probability <= 1.0 or marker_random_noise < 0.0:
+                raise ValueError("marker_lose_tracking_probability must lie in [0, 1] and marker_random_noise must not be negative")
+            surf0 = self.init_surface_vertices_camera[0].cpu().numpy()  # same mesh in every env
+            self.patterns = build_marker_patterns(marker_patterns, surf0, self.surf_triangles, marker_interval_range, marker_rotation_range,
+                                                  marker_translation_range, marker_pos_shift_range, self._rng).to(dev)
+            self.marker_seed = int(seed) & 0xFFFFFFFFFFFFFFFF  # Philox key; a sharded job gives every rank its own
+            self.pattern_ids = torch.from_numpy(check_pattern_ids(None, B, self.patterns.num_patterns)).to(dev)
+            self.marker_draws = torch.zeros(B, dtype=torch.int32, device=dev)  # (B,) uint32 draw counters (bit pattern), bumped by the kernel
+            self.num_tracked = torch.zeros(B, dtype=torch.int32, device=dev)
+
+    def set_pattern_ids(self, ids):
+        """Give every env the pattern `ids[e]`; validated on the host (ValueError outside the library).  A task may also write
+        `pattern_ids` in place on the device - the kernel reads it at every launch and treats an id outside the library as pattern 0."""
+        if self.patterns is None:
+            raise RuntimeError("set_pattern_ids needs a marker pattern library (marker_patterns > 0)")
+        ids = check_pattern_ids(ids, self.pattern_ids.shape[0], self.patterns.num_patterns)
+        self.pattern_ids.copy_(torch.from_numpy(ids), non_blocking=False)
+
+    def _gen_marker_flow_library(self, out_f32: torch.Tensor | None = None) -> torch.Tensor:
+        """One `tacex_fem_marker_flow_library` launch on the FEM state: (B,2,num_markers,2) float64, or `out_f32` filled."""
+        self.uipc_sim.wait_for_step()
+        x, lib = self.uipc_sim.x, self.patterns
+        B, V, K = x.shape[0], x.shape[1], self.num_markers
+        ref = self._ref_surface if self._ref_surface.is_contiguous() else self._ref_surface.contiguous()
+        curr_uv = torch.empty((B, lib.max_markers, 2), dtype=torch.float64, device=self.device)  # (a fresh tensor per call: callers may keep the last)
+        flow = None
+        if out_f32 is None:
+            flow = torch.empty((B, 2, K, 2), dtype=torch.float64, device=self.device)
+        elif out_f32.dtype != torch.float32 or not out_f32.is_contiguous() or tuple(out_f32.shape) != (B, 2, K, 2):
+            raise ValueError("gen_marker_flow_fused: out_f32 must be a contiguous float32 (B, 2, num_markers, 2) tensor")
+        with torch.cuda.device(self.device):
+            rc = self._lib.tacex_fem_marker_flow_library(
+                _lib.ptr(x), _lib.ptr(self._surf_ids64), _lib.ptr(self.cam_pos_w), _lib.ptr(self.cam_rot_inv), _lib.ptr(ref), _lib.ptr(lib.tri),
+                _lib.ptr(lib.wgt), _lib.ptr(lib.count), lib.num_patterns, lib.max_markers, _lib.ptr(self.pattern_ids), _lib.ptr(self.marker_draws),
+                self.marker_seed, self.fx, self.fy, self.cx, self.cy, float(self.marker_lose_tracking_probability), float(self.marker_random_noise),
+                int(self.tactile_img_height), int(self.tactile_img_width), float(self.tactile_img_width / 2) if self.normalize else 0.0,
+                _lib.ptr(curr_uv), _lib.ptr(flow) if flow is not None else None, _lib.ptr(out_f32) if out_f32 is not None else None,
+                _lib.ptr(self.num_tracked), B, V, ref.shape[1], K, _lib.current_stream_handle(self.device))
+        _lib.check(rc, "tacex_fem_marker_flow_library")
+        self.curr_marker_uv = curr_uv
+        return flow if out_f32 is None else out_f32
 
     # -- frames (VT:142-187) -----------------------------------------------------------------------------
     def get_surface_vertices_world(self) -> torch.Tensor:
@@ -241,7 +343,10 @@ class VisionTactileSensorUIPC:
     def gen_marker_flow_fused(self, out_f32: torch.Tensor | None = None) -> torch.Tensor | None:
         """gen_marker_flow for a static marker grid with enough in-image markers, as ONE launch on the FEM state (`tacex_fem_marker_flow`):
         returns the (B,2,num_markers,2) float64 flow - or, with `out_f32` (B,2,num_markers,2) float32 contiguous, writes that and returns it.
-        None when this path does not apply (random grid, no marker in the image): the caller takes gen_marker_flow()."""
+        None when this path does not apply (random grid, no marker in the image): the caller takes gen_marker_flow().
+        With a marker pattern library: always its one launch (`tacex_fem_marker_flow_library`)."""
+        if self.patterns is not None:
+            return self._gen_marker_flow_library(out_f32)
         if not self._static:
             return None
         tri, wgt = self._setup()
