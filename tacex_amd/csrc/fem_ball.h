@@ -50,26 +50,16 @@ struct BallDev {
                       // caller moves q between steps, the pad sees it through the pairs (both ways) and their friction
 };
 
-constexpr int kBallMaxPairs = 4096;   // listed candidate pairs per env and Newton iteration
-constexpr int kBallMaxActive = 1024;  // pairs inside d_hat at the iteration's state
-constexpr int kBallRec = 14;          // doubles per active record
 constexpr int kBallMaxCand = 512;     // candidate pad vertices / pad triangles / ball vertices per env
 constexpr double kBallReach = 2.0;    // additive CCD on pairs closer than kBallReach * d_hat
 constexpr double kBallKeep = 0.1;     // ... which may keep this fraction of their gap
-constexpr int kBallMaxFric = 1024;    // lagged friction contacts per env and time step (pairs + ground)
 constexpr int kBallFlagOverflow = 16; // step_info flag: a candidate / pair list overflowed (the scene is outside what this slice handles)
 
-// workspace of one env (doubles): ground curvature V | xb 3nv | xbc 3nv | dxb 3nv | ball triangle spheres 4nt | pair list (ints)
-//   kBallMaxPairs / 2 | active records | friction records + their Hessians.  (Everything per-vertex lives in LDS.)
+// (kBallMaxPairs, kBallMaxActive, kBallRec, kBallMaxFric and the env's workspace block, ball_ws_doubles: fem_layout.h)
 // dynamic LDS: x (V,3) | p (V + 4,3) | H.p accumulators = H.p (V,3) | z (V,3) | r (V + 4,3) | d (V + 4,3) (doubles) || chain factors (V,15)
 // (floats) || chain successor / predecessor (V each, u16): every vector of the PCG loop, 104 KB at 495 vertices
 __host__ __device__ inline size_t ball_lds_bytes(int V) {
   return ((((size_t)18 * V + 36) * sizeof(double) + (size_t)15 * V * sizeof(float) + (size_t)2 * V * sizeof(unsigned short)) + 15) & ~(size_t)15;
-}
-__host__ __device__ inline size_t ball_ws_doubles(int V, int T, int nv, int nt) {
-  (void)T;
-  return (size_t)V + (size_t)9 * nv + (size_t)4 * nt + kBallMaxPairs / 2 + (size_t)kBallMaxActive * kBallRec +
-         (size_t)kBallMaxFric * (kBallRec + 6);  // lagged friction records + their Hessians at the iteration's state
 }
 
 // closest point of triangle (a, b, c) to p: barycentric coordinates, distance, unit vector from the closest point to p

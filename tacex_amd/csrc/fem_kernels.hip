@@ -27,6 +27,7 @@
 #include <utility>
 #include <vector>
 
+#include "fem_layout.h"
 #include "tacex_hip.h"
 #include "tacex_internal.h"
 #include "tacex_philox.h"
@@ -770,9 +771,7 @@ __global__ __launch_bounds__(512) void fem_gradient_kernel(FemDev m, const doubl
 }
 
 // ---- K17b: one projected-Newton iteration per env, everything inside one workgroup -----------------------------
-// workspace per env (doubles): ge 12T | tet cache 12T (F 9, a, b, c) | hv 12T | g,r,z,p,d,Hp,xc 7*3V | Dinv 9V | contact 5V | friction lag 4V | friction blocks 6V; behind the B env
-// blocks: x_prev (B,V,3) and the per-env max |d| of tacex_fem_step
-__host__ __device__ inline size_t newton_ws_doubles(int V, int T) { return (size_t)36 * T + (size_t)45 * V; }  // (+ 10 V: friction lag | Hessian blocks)
+// (workspace per env: newton_ws_doubles, fem_layout.h)
 
 __device__ __forceinline__ bool inv3_spd(const double A[9], double Ai[9]) {
   // Cholesky test + inverse via adjugate
@@ -2744,8 +2743,13 @@ using namespace tacex;
 
 struct tacex_fem_ctx {
   int device = 0;
-  FemDev dev{};
-  FemDev dev_nwt{};  // same mesh with the tets renumbered for fem_newton_lds_kernel (see tacex_fem_create)
+  FemDev dev{};  // THE parameter block: the natural tet tables and everything the setters write
+  // the same tets renumbered for fem_newton_lds_kernel and fem_assemble_blocks_kernel (see tacex_fem_create); tet_rec and tet_blk exist
+  // in this numbering only (null in dev)
+  struct {
+    const int* tets = nullptr; const double* dminv = nullptr; const double* vol = nullptr; const int* vt_idx = nullptr;
+    const double* tet_rec = nullptr; const double* tet_blk = nullptr;
+  } nwt;
   FemMat mat{};      // the gel material library (tacex_fem_set_material_library); one copy: every launch hands it over
   // Friction slides relative to the indenter's displacement since the previous tacex_fem_step.  The previous positions (B,3) live
   // in the caller's workspace (no allocation in a compute call); the context remembers WHICH workspace and env count they were
@@ -2766,7 +2770,7 @@ struct tacex_fem_ctx {
   tacex::BallDev ball{};     // the env's free affine body + ground (tacex_fem_set_affine_body); nv == 0: none
   const void* ball_last_ws = nullptr;  // workspace / env count whose "q at the end of the previous step" rows are valid (kinematic bodies)
   int ball_last_B = 0;
-  // what tacex_fem_set_material_library needs to build a material's mass table the way tacex_fem_create built the scene's
+  // what tacex_fem_set_material_library needs to build a material's mass table (lumped_mass)
   std::vector<int> tets_host;    // (4,T) SoA, re-oriented
   std::vector<double> vol_host;  // (T)
   double fric_scene = 0.0;       // the ratio tacex_fem_set_friction gave (FemDev::fric_mu is the library's largest while a library is set)
@@ -2776,6 +2780,50 @@ struct tacex_fem_ctx {
 // Tables a setter REPLACES (coarse space, chains, indenter mesh, vertex areas) are freed once nothing can read them any more:
 // the setters are host-synchronous set-up calls, so they drain the device first (a caller who refreshed the
 // preconditioner every step grew the device memory without bound).
+// what the CU-resident Newton kernel and the block assembly get: dev with the tet tables in their numbering
+static FemDev newton_dev(const tacex_fem_ctx* c) {
+  FemDev d = c->dev;
+  d.tets = c->nwt.tets; d.dminv = c->nwt.dminv; d.vol = c->nwt.vol; d.vt_idx = c->nwt.vt_idx;
+  d.tet_rec = c->nwt.tet_rec; d.tet_blk = c->nwt.tet_blk;
+  return d;
+}
+
+// The LDS bookkeeping of ONE kernel instantiation, per device: what a workgroup can get next to the kernel's static __shared__
+// (dynamic_lds_limit) and what has been granted so far (ensure_dynamic_lds).  route<kernel>() is the only way to a kernel that takes
+// dynamic LDS, so a kernel and its tables cannot be paired wrongly.
+struct LdsTables { size_t avail[64] = {}, granted[64] = {}; };
+template <typename K>
+struct Route {
+  K kern = nullptr;
+  LdsTables* lds = nullptr;
+  const void* id() const { return reinterpret_cast<const void*>(kern); }
+};
+template <auto KERN>
+static Route<decltype(KERN)> route() {
+  static LdsTables t;
+  return {KERN, &t};
+}
+
+// Stable Neo-Hookean constants of a gel (Smith et al. 2018, eq. 14 with the rest-stable reparametrisation): the ONE place they are
+// computed, so an env of a library material computes bit for bit what a scene created with that material computes
+struct GelConstants { double mu, lam, alpha, psi_rest; };
+static GelConstants gel_constants(double youngs, double poisson) {
+  const double mu_l = youngs / (2.0 * (1.0 + poisson));
+  const double lam_l = youngs * poisson / ((1.0 + poisson) * (1.0 - 2.0 * poisson));
+  GelConstants g;
+  g.mu = 4.0 / 3.0 * mu_l;
+  g.lam = lam_l + 5.0 / 6.0 * mu_l;
+  g.alpha = 1.0 + 0.75 * g.mu / g.lam;
+  g.psi_rest = 0.5 * g.lam * (1.0 - g.alpha) * (1.0 - g.alpha) - 0.5 * g.mu * log(4.0);
+  return g;
+}
+
+// lumped mass per vertex, added INTO mass (V, zeroed by the caller): a quarter of every incident tet's, tets in order (fixed summation order)
+static void lumped_mass(double density, const std::vector<int>& tets_soa, const std::vector<double>& vol, int T, double* mass) {
+  for (int t = 0; t < T; ++t)
+    for (int k = 0; k < 4; ++k) mass[tets_soa[(size_t)k * T + t]] += density * vol[t] / 4.0;
+}
+
 template <typename T>
 static void fem_release(tacex_fem_ctx* c, const T*& ptr, bool* synced) {
   if (!ptr) return;
@@ -2873,8 +2921,8 @@ int tacex_fem_create(int device_id, const tacex_fem_params* p, tacex_fem_ctx** o
     for (int k = 0; k < 9; ++k) dminv[(size_t)k * T + t] = inv[k];
     for (int k = 0; k < 4; ++k) tets[(size_t)k * T + t] = v[k];
     vol[t] = det / 6.0;
-    for (int k = 0; k < 4; ++k) mass[v[k]] += p->density * vol[t] / 4.0;
   }
+  lumped_mass(p->density, tets, vol, T, mass.data());
   std::vector<int> off(V + 1, 0), idx((size_t)4 * T);
   for (int t = 0; t < T; ++t)
     for (int k = 0; k < 4; ++k) off[tets[(size_t)k * T + t] + 1]++;
@@ -2935,17 +2983,12 @@ int tacex_fem_create(int device_id, const tacex_fem_params* p, tacex_fem_ctx** o
       memcpy(base + 4608 + ln * 8, &vol2[n], 8);
       for (int k = 0; k < 4; ++k) memcpy(base + 5120 + k * 256 + ln * 4, &tets2[(size_t)k * T + n], 4);
     }
-    c->dev_nwt = d;
-    rc = fem_upload(c, blk2, &c->dev_nwt.tet_blk) | fem_upload(c, tets2, &c->dev_nwt.tets) | fem_upload(c, dminv2, &c->dev_nwt.dminv) | fem_upload(c, vol2, &c->dev_nwt.vol) |
-         fem_upload(c, idx2, &c->dev_nwt.vt_idx) | fem_upload(c, rec2, &c->dev_nwt.tet_rec);
+    rc |= fem_upload(c, blk2, &c->nwt.tet_blk) | fem_upload(c, tets2, &c->nwt.tets) | fem_upload(c, dminv2, &c->nwt.dminv) | fem_upload(c, vol2, &c->nwt.vol) |
+          fem_upload(c, idx2, &c->nwt.vt_idx) | fem_upload(c, rec2, &c->nwt.tet_rec);
   }
   if (rc) { tacex_fem_destroy(c); return rc; }
-  const double mu_l = p->youngs / (2.0 * (1.0 + p->poisson));
-  const double lam_l = p->youngs * p->poisson / ((1.0 + p->poisson) * (1.0 - 2.0 * p->poisson));
-  d.mu = 4.0 / 3.0 * mu_l;
-  d.lam = lam_l + 5.0 / 6.0 * mu_l;
-  d.alpha = 1.0 + 0.75 * d.mu / d.lam;
-  d.psi_rest = 0.5 * d.lam * (1.0 - d.alpha) * (1.0 - d.alpha) - 0.5 * d.mu * log(4.0);
+  const GelConstants g = gel_constants(p->youngs, p->poisson);
+  d.mu = g.mu; d.lam = g.lam; d.alpha = g.alpha; d.psi_rest = g.psi_rest;
   d.dt = p->dt;
   d.strength = p->constraint_strength_ratio;
   {
@@ -2953,10 +2996,7 @@ int tacex_fem_create(int device_id, const tacex_fem_params* p, tacex_fem_ctx** o
     for (int v = 1; v < V; ++v)
       for (int i = 0; i < 3; ++i) { lo[i] = fmin(lo[i], X[v * 3 + i]); hi[i] = fmax(hi[i], X[v * 3 + i]); }
     d.step_cap = sqrt((hi[0] - lo[0]) * (hi[0] - lo[0]) + (hi[1] - lo[1]) * (hi[1] - lo[1]) + (hi[2] - lo[2]) * (hi[2] - lo[2]));
-    c->dev_nwt.step_cap = d.step_cap;
   }
-  c->dev_nwt.mu = d.mu; c->dev_nwt.lam = d.lam; c->dev_nwt.alpha = d.alpha; c->dev_nwt.psi_rest = d.psi_rest;
-  c->dev_nwt.dt = d.dt; c->dev_nwt.strength = d.strength;
   *out = c;
   return 0;
 }
@@ -2970,9 +3010,7 @@ void tacex_fem_destroy(tacex_fem_ctx* c) {
 
 size_t tacex_fem_workspace_bytes(const tacex_fem_ctx* c, int B) {
   if (!c || B <= 0) return 0;
-  // env blocks | x_prev (B,V,3) | max |d| (B) | indenter displacement (B,3) | previous indenter position (B,3)
-  // ... | env launch order (B int32, rounded up to doubles)
-  return ((size_t)B * newton_ws_doubles(c->dev.V, c->dev.T) + (size_t)B * 3 * c->dev.V + (size_t)7 * B + 8 + ((size_t)B + 1) / 2) * sizeof(double);
+  return StepLayout(c->dev.V, c->dev.T, B).total * sizeof(double);
 }
 
 int tacex_fem_element_terms(tacex_fem_ctx* c, const double* x, double* energy, double* grad, double* hess,
@@ -3022,17 +3060,17 @@ int tacex_fem_set_contact(tacex_fem_ctx* c, const double* vertex_area_host, doub
     if (int rc = fem_upload(c, a, &d)) return rc;
     bool synced = false;
     fem_release(c, c->dev.area, &synced);
-    c->dev.area = d; c->dev_nwt.area = d;
+    c->dev.area = d;
   }
   if (indenters_dev) {
     if (!c->dev.area) { set_error("tacex_fem_set_contact: vertex areas were never given"); return 2; }
     if (!(d_hat > 0.0) || !(stiffness > 0.0)) { set_error("tacex_fem_set_contact: need d_hat > 0 and stiffness > 0"); return 2; }
   }
-  c->dev.dhat = c->dev_nwt.dhat = d_hat;
-  c->dev.kappa = c->dev_nwt.kappa = stiffness;
+  c->dev.dhat = d_hat;
+  c->dev.kappa = stiffness;
   if (!indenters_dev || !c->dev.indenters) { c->ind_prev_ws = nullptr; c->ind_prev_B = 0; }  // contact off, or enabled for the first time:
                                                                                              // the next step sees no indenter motion
-  c->dev.indenters = c->dev_nwt.indenters = indenters_dev;
+  c->dev.indenters = indenters_dev;
   return 0;
 }
 
@@ -3065,8 +3103,8 @@ int tacex_fem_set_friction(tacex_fem_ctx* c, double friction_ratio, double eps_v
     return 2;
   }
   c->fric_scene = friction_ratio;
-  if (c->mat.n == 0) c->dev.fric_mu = c->dev_nwt.fric_mu = friction_ratio;  // (with a material library: its largest ratio, set there)
-  c->dev.fric_eps = c->dev_nwt.fric_eps = eps_velocity * c->dev.dt;
+  if (c->mat.n == 0) c->dev.fric_mu = friction_ratio;  // (with a material library: its largest ratio, set there)
+  c->dev.fric_eps = eps_velocity * c->dev.dt;
   return 0;
 }
 
@@ -3202,15 +3240,12 @@ static int set_indenter_library(tacex_fem_ctx* c, const char* who, int num_meshe
     bool synced = false;
     fem_release(c, d.im_lib, &synced); fem_release(c, d.im_off, &synced);
     d.im_nt = d.im_nm = 0;
-    c->dev_nwt.im_lib = nullptr; c->dev_nwt.im_off = nullptr; c->dev_nwt.im_nt = c->dev_nwt.im_nm = 0;
   }
   if (num_meshes > 0) {
     if (int rc = fem_upload(c, lib, &d.im_lib) | fem_upload(c, off, &d.im_off)) return rc;
     d.im_nt = (int)nt;
     d.im_nm = num_meshes;
   }
-  FemDev& n2 = c->dev_nwt;
-  n2.im_nt = d.im_nt; n2.im_nm = d.im_nm; n2.im_lib = d.im_lib; n2.im_off = d.im_off;
   return 0;
 }
 
@@ -3220,7 +3255,7 @@ int tacex_fem_set_indenter_mesh(tacex_fem_ctx* c, int num_verts, const double* v
   if (num_tris != 0 && (num_verts < 3 || num_tris < 1 || !verts_host || !tris_host)) { set_error("tacex_fem_set_indenter_mesh: bad arguments"); return 2; }
   const int32_t nv = num_verts, nt = num_tris;
   const int rc = set_indenter_library(c, "tacex_fem_set_indenter_mesh", num_tris == 0 ? 0 : 1, &nv, verts_host, &nt, tris_host);
-  if (rc == 0) c->dev.im_ids = c->dev_nwt.im_ids = nullptr;
+  if (rc == 0) c->dev.im_ids = nullptr;
   return rc;
 }
 
@@ -3232,7 +3267,7 @@ int tacex_fem_set_indenter_mesh_library(tacex_fem_ctx* c, int num_meshes, const 
 
 int tacex_fem_set_indenter_mesh_ids(tacex_fem_ctx* c, const int32_t* ids_dev) {
   if (!c) { set_error("tacex_fem_set_indenter_mesh_ids: null context"); return 2; }
-  c->dev.im_ids = c->dev_nwt.im_ids = ids_dev;
+  c->dev.im_ids = ids_dev;
   return 0;
 }
 
@@ -3257,37 +3292,27 @@ int tacex_fem_set_material_library(tacex_fem_ctx* c, int num_materials, const do
       set_error("tacex_fem_set_material_library: material %d needs youngs > 0, -1 < poisson < 0.5, density > 0, friction_ratio >= 0", k);
       return 2;
     }
-    // the expressions and the summation order of tacex_fem_create: an env of material k computes bit for bit what a scene created
-    // with that material computes
     double* rec = lib.data() + stride * k;
-    const double mu_l = youngs[k] / (2.0 * (1.0 + poisson[k]));
-    const double lam_l = youngs[k] * poisson[k] / ((1.0 + poisson[k]) * (1.0 - 2.0 * poisson[k]));
-    const double mu = 4.0 / 3.0 * mu_l;
-    const double lam = lam_l + 5.0 / 6.0 * mu_l;
-    const double alpha = 1.0 + 0.75 * mu / lam;
-    rec[0] = mu; rec[1] = lam; rec[2] = alpha;
-    rec[3] = 0.5 * lam * (1.0 - alpha) * (1.0 - alpha) - 0.5 * mu * log(4.0);
+    const GelConstants g = gel_constants(youngs[k], poisson[k]);
+    rec[0] = g.mu; rec[1] = g.lam; rec[2] = g.alpha; rec[3] = g.psi_rest;
     rec[4] = friction_ratio[k];
-    double* mass = rec + kMatHead;
-    for (int t = 0; t < T; ++t)
-      for (int j = 0; j < 4; ++j) mass[c->tets_host[(size_t)j * T + t]] += density[k] * c->vol_host[t] / 4.0;
+    lumped_mass(density[k], c->tets_host, c->vol_host, T, rec + kMatHead);
     fmax_ = fmax(fmax_, friction_ratio[k]);
   }
   hipError_t e = hipSetDevice(c->device);
   if (e != hipSuccess) return fail_hip(e, "hipSetDevice");
   FemDev& d = c->dev;
-  FemDev& n2 = c->dev_nwt;
   {
     // (the per-material coarse inverses belong to the library they were built for: they go with it)
     bool synced = false;
     fem_release(c, c->mat.lib, &synced); fem_release(c, c->mat.ac, &synced);
     c->mat.n = 0;
-    d.fric_mu = n2.fric_mu = c->fric_scene;
+    d.fric_mu = c->fric_scene;
   }
   if (num_materials > 0) {
     if (int rc = fem_upload(c, lib, &c->mat.lib)) return rc;
     c->mat.n = num_materials;
-    d.fric_mu = n2.fric_mu = fmax_;  // sizes the friction state of the Newton kernels; an env's own ratio comes from its material
+    d.fric_mu = fmax_;  // sizes the friction state of the Newton kernels; an env's own ratio comes from its material
   }
   return 0;
 }
@@ -3318,13 +3343,11 @@ int tacex_fem_set_material_coarse_inverses(tacex_fem_ctx* c, int num_materials, 
 int tacex_fem_set_chains(tacex_fem_ctx* c, int num_chains, const int32_t* chain_offsets_host, const int32_t* chain_vertices_host) {
   if (!c) { set_error("tacex_fem_set_chains: null context"); return 2; }
   FemDev& d = c->dev;
-  FemDev& n2 = c->dev_nwt;
   auto drop_chains = [&]() {
     bool synced = false;
     (void)hipSetDevice(c->device);
     fem_release(c, d.ch_head, &synced); fem_release(c, d.ch_next, &synced); fem_release(c, d.ch_prev, &synced);
-    d.nch = n2.nch = 0;
-    n2.ch_head = nullptr; n2.ch_next = nullptr; n2.ch_prev = nullptr;
+    d.nch = 0;
   };
   if (num_chains == 0) {  // every vertex its own chain: 3x3 block Jacobi
     drop_chains();
@@ -3353,7 +3376,6 @@ int tacex_fem_set_chains(tacex_fem_ctx* c, int num_chains, const int32_t* chain_
   drop_chains();
   if (int rc = fem_upload(c, head, &d.ch_head) | fem_upload(c, nxt, &d.ch_next) | fem_upload(c, prv, &d.ch_prev)) return rc;
   d.nch = (int)head.size();
-  n2.nch = d.nch; n2.ch_head = d.ch_head; n2.ch_next = d.ch_next; n2.ch_prev = d.ch_prev;
   return 0;
 }
 
@@ -3367,9 +3389,7 @@ int tacex_fem_set_coarse_space(tacex_fem_ctx* c, int num_coarse, const int32_t* 
     fem_release(c, d0.cv_node, &synced); fem_release(c, d0.cv_w, &synced); fem_release(c, d0.cn_off, &synced);
     fem_release(c, d0.cn_vtx, &synced); fem_release(c, d0.cn_w, &synced); fem_release(c, d0.ac_inv, &synced);
     fem_release(c, c->mat.ac, &synced);  // (the per-material inverses were built for the space that goes: tacex_fem_set_material_coarse_inverses again)
-    FemDev& n0 = c->dev_nwt;
-    n0.cv_node = nullptr; n0.cv_w = nullptr; n0.cn_off = nullptr; n0.cn_vtx = nullptr; n0.cn_w = nullptr; n0.ac_inv = nullptr;
-    d0.nc = n0.nc = 0;
+    d0.nc = 0;
   };
   if (num_coarse == 0) {  // block Jacobi alone
     drop_coarse();
@@ -3405,8 +3425,6 @@ int tacex_fem_set_coarse_space(tacex_fem_ctx* c, int num_coarse, const int32_t* 
                fem_upload(c, cw, &d.cn_w) | fem_upload(c, ai, &d.ac_inv))
     return rc;
   d.nc = nc;
-  FemDev& n2 = c->dev_nwt;
-  n2.nc = nc; n2.cv_node = d.cv_node; n2.cv_w = d.cv_w; n2.cn_off = d.cn_off; n2.cn_vtx = d.cn_vtx; n2.cn_w = d.cn_w; n2.ac_inv = d.ac_inv;
   return 0;
 }
 
@@ -3417,26 +3435,26 @@ int tacex_fem_set_newton_early_exit(tacex_fem_ctx* c, double* dx_dev, double dx_
   return 0;
 }
 
-// one launch of the Newton kernel: up to max_newton iterations per env inside the CU-resident kernel, one iteration of the
-// streaming fallback (mesh with more vertices than a workgroup has threads; TACEX_FEM_NEWTON_LDS=0)
-// elastic preconditioner blocks of all envs at x -> the env blocks of the workspace ((V,16) per env); dx_dev / dx_tol: envs already converged are skipped
-static int launch_assemble(tacex_fem_ctx* c, const double* x, void* ws, int B, const double* dx_dev, double dx_tol, hipStream_t st, bool atom) {
-  static size_t granted_a[4][64] = {};
+// elastic preconditioner blocks of all envs at x -> blk (B,V,16); dx_dev / dx_tol: envs already converged are skipped.  THE launch of
+// fem_assemble_blocks_kernel: tacex_fem_ball_step comes here too (its blk region, no dx, tolerance 0)
+static int launch_assemble(tacex_fem_ctx* c, const double* x, double* blk, int B, const double* dx_dev, double dx_tol, hipStream_t st, bool atom) {
   // TACEX_FEM_ASSEMBLE: 1 = tet-centric with LDS atomics, 0 = vertex-centric in a fixed order (A/B hook; default: follows the atomics switch)
   static const int asm_env = getenv("TACEX_FEM_ASSEMBLE") ? atoi(getenv("TACEX_FEM_ASSEMBLE")) : -1;
   const bool asm_atom = asm_env < 0 ? atom : (asm_env != 0 && !c->deterministic);
   const int V = c->dev.V;
   const size_t lds_a = ((size_t)3 * V + (asm_atom ? (size_t)15 * V : 0)) * sizeof(double);
   const bool mat = c->mat.n > 0;
-  auto ka = asm_atom ? (mat ? fem_assemble_blocks_kernel<true, true> : fem_assemble_blocks_kernel<true, false>)
-                     : (mat ? fem_assemble_blocks_kernel<false, true> : fem_assemble_blocks_kernel<false, false>);
-  hipError_t ea = ensure_dynamic_lds(reinterpret_cast<const void*>(ka), lds_a, granted_a[(asm_atom ? 1 : 0) + (mat ? 2 : 0)]);
+  const auto ra = asm_atom ? (mat ? route<fem_assemble_blocks_kernel<true, true>>() : route<fem_assemble_blocks_kernel<true, false>>())
+                           : (mat ? route<fem_assemble_blocks_kernel<false, true>>() : route<fem_assemble_blocks_kernel<false, false>>());
+  hipError_t ea = ensure_dynamic_lds(ra.id(), lds_a, ra.lds->granted);
   if (ea != hipSuccess) return fail_hip(ea, "hipFuncSetAttribute(fem_assemble_blocks_kernel)");
-  hipLaunchKernelGGL(ka, dim3(B), dim3(512), lds_a, st, c->dev_nwt, x, static_cast<double*>(ws), dx_dev, dx_tol, c->mat);
+  hipLaunchKernelGGL(ra.kern, dim3(B), dim3(512), lds_a, st, newton_dev(c), x, blk, dx_dev, dx_tol, c->mat);
   ea = hipGetLastError();
   return ea == hipSuccess ? 0 : fail_hip(ea, "fem_assemble_blocks_kernel");
 }
 
+// one launch of the Newton kernel: up to max_newton iterations per env inside the CU-resident kernel, one iteration of the
+// streaming fallback (mesh with more vertices than a workgroup has threads; TACEX_FEM_NEWTON_LDS=0)
 static int launch_newton(tacex_fem_ctx* c, double* x, const double* xt, const uint8_t* cons, const double* aim, double* stats, void* ws,
                          int B, int pcg_max_iter, double pcg_tol_rate, int ls_max_iter, double* dx_dev, double dx_tol, int max_newton,
                          double* step_info, hipStream_t st, bool* resident, const double* xprev = nullptr, const double* disp = nullptr,
@@ -3461,44 +3479,36 @@ static int launch_newton(tacex_fem_ctx* c, double* x, const double* xt, const ui
   hipError_t ea = hipSetDevice(c->device);  // (the LDS limits and opt-ins below are per device)
   if (ea != hipSuccess) return fail_hip(ea, "hipSetDevice");
   const bool mat = c->mat.n > 0;  // the material-library instantiations only when a library has been set
-  using kern_t = decltype(&fem_newton_lds_kernel<false, true, 512, false>);
-  kern_t kern = nullptr;
-  int slot = 0;
+  Route<decltype(&fem_newton_lds_kernel<false, true, 512, false>)> rk;  // (kern == nullptr: the streaming kernel below)
   if (use_lds && V <= 768 && (nt <= 512 ? 4 * c->dev.T < 65535 : (atom && !mesh))) {
     if (nt == 256) {
-      kern = mat ? fem_newton_lds_kernel<false, true, 256, true> : fem_newton_lds_kernel<false, true, 256, false>;
-      slot = 5;
+      rk = mat ? route<fem_newton_lds_kernel<false, true, 256, true>>() : route<fem_newton_lds_kernel<false, true, 256, false>>();
     } else if (nt == 512) {
       if (mat)
-        kern = mesh ? (atom ? fem_newton_lds_kernel<true, true, 512, true> : fem_newton_lds_kernel<true, false, 512, true>)
-                    : (atom ? fem_newton_lds_kernel<false, true, 512, true> : fem_newton_lds_kernel<false, false, 512, true>);
+        rk = mesh ? (atom ? route<fem_newton_lds_kernel<true, true, 512, true>>() : route<fem_newton_lds_kernel<true, false, 512, true>>())
+                  : (atom ? route<fem_newton_lds_kernel<false, true, 512, true>>() : route<fem_newton_lds_kernel<false, false, 512, true>>());
       else
-        kern = mesh ? (atom ? fem_newton_lds_kernel<true, true, 512, false> : fem_newton_lds_kernel<true, false, 512, false>)
-                    : (atom ? fem_newton_lds_kernel<false, true, 512, false> : fem_newton_lds_kernel<false, false, 512, false>);
-      slot = (mesh ? 1 : 0) + (atom ? 2 : 0);
+        rk = mesh ? (atom ? route<fem_newton_lds_kernel<true, true, 512, false>>() : route<fem_newton_lds_kernel<true, false, 512, false>>())
+                  : (atom ? route<fem_newton_lds_kernel<false, true, 512, false>>() : route<fem_newton_lds_kernel<false, false, 512, false>>());
     } else {
-      kern = mat ? fem_newton_lds_kernel<false, true, 768, true> : fem_newton_lds_kernel<false, true, 768, false>;
-      slot = 4;
+      rk = mat ? route<fem_newton_lds_kernel<false, true, 768, true>>() : route<fem_newton_lds_kernel<false, true, 768, false>>();
     }
-    if (mat) slot += 6;
     // the env's state must fit next to the kernel's static __shared__; a pad that does not (e.g. 750 vertices on 768 threads) streams
-    static size_t avail[12][64] = {};
     size_t limit = 0;
-    ea = dynamic_lds_limit(reinterpret_cast<const void*>(kern), avail[slot], &limit);
+    ea = dynamic_lds_limit(rk.id(), rk.lds->avail, &limit);
     if (ea != hipSuccess) return fail_hip(ea, "hipFuncGetAttributes(fem_newton_lds_kernel)");
-    if (lds > limit) kern = nullptr;
+    if (lds > limit) rk = {};
   }
-  if (kern) {
+  if (rk.kern) {
     if (resident) *resident = true;
     c->last_resident = 1;
     c->last_threads = nt;
     c->last_lds_mode = -1;
-    static size_t granted[12][64] = {};  // per kernel instantiation and device: the attribute is per kernel AND device
-    ea = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), lds, granted[slot]);
+    ea = ensure_dynamic_lds(rk.id(), lds, rk.lds->granted);
     if (ea != hipSuccess) return fail_hip(ea, "hipFuncSetAttribute(fem_newton_lds_kernel)");
     // elastic preconditioner blocks of all envs at the state this launch starts from -> workspace ((V,16) per env)
-    if (int rc = launch_assemble(c, x, ws, B, dx_dev, dx_tol, st, atom)) return rc;
-    hipLaunchKernelGGL(kern, dim3(B), dim3(nt), lds, st, c->dev_nwt, x, xt, cons, aim, stats, pcg_max_iter,
+    if (int rc = launch_assemble(c, x, static_cast<double*>(ws), B, dx_dev, dx_tol, st, atom)) return rc;
+    hipLaunchKernelGGL(rk.kern, dim3(B), dim3(nt), lds, st, newton_dev(c), x, xt, cons, aim, stats, pcg_max_iter,
                        pcg_tol_rate, ls_max_iter, dx_dev, dx_tol, max_newton, step_info, fric ? xprev : nullptr,
                        (xprev && disp && c->dev.indenters) ? disp : nullptr, env_order,
                        (c->follow_indenter ? 1 : 0) | ((fric_lag_at_start || c->fric_lag_mode == 1) ? 2 : 0) | (c->fric_lag_mode == 1 ? 4 : 0),
@@ -3511,22 +3521,20 @@ static int launch_newton(tacex_fem_ctx* c, double* x, const double* xt, const ui
   // x, p and the H.p accumulators in LDS when the summation order is free (atomic mode) and they fit next to the kernel's static
   // __shared__ (9 V doubles: ~2 200 vertices); all PCG vectors when 21 V doubles fit (~950 vertices); else global memory
   static const int stream_lds = getenv("TACEX_FEM_STREAM_LDS") ? atoi(getenv("TACEX_FEM_STREAM_LDS")) : 2;  // A/B hook: 0 none, 1 x / p / accumulators, 2 all PCG vectors
-  static size_t avail_s[2][64] = {};
   size_t limit_s = 0;
-  auto kstream = mat ? fem_newton_kernel<true> : fem_newton_kernel<false>;
-  ea = dynamic_lds_limit(reinterpret_cast<const void*>(kstream), avail_s[mat ? 1 : 0], &limit_s);
+  const auto rs = mat ? route<fem_newton_kernel<true>>() : route<fem_newton_kernel<false>>();
+  ea = dynamic_lds_limit(rs.id(), rs.lds->avail, &limit_s);
   if (ea != hipSuccess) return fail_hip(ea, "hipFuncGetAttributes(fem_newton_kernel)");
   const bool lds_all = stream_lds != 1 && (size_t)21 * V * sizeof(double) <= limit_s;  // (TACEX_FEM_STREAM_LDS=1: x, p, accumulators only)
   const size_t lds_s = (size_t)(lds_all ? 21 : 9) * V * sizeof(double);
   const bool lds_sweep = stream_lds != 0 && atom && lds_s <= limit_s;
   if (lds_sweep) {
-    static size_t granted_s[2][64] = {};
-    const hipError_t es = ensure_dynamic_lds(reinterpret_cast<const void*>(kstream), lds_s, granted_s[mat ? 1 : 0]);
+    const hipError_t es = ensure_dynamic_lds(rs.id(), lds_s, rs.lds->granted);
     if (es != hipSuccess) return fail_hip(es, "hipFuncSetAttribute(fem_newton_kernel)");
   }
   c->last_threads = 512;
   c->last_lds_mode = lds_sweep ? (lds_all ? 2 : 1) : 0;
-  hipLaunchKernelGGL(kstream, dim3(B), dim3(512), lds_sweep ? lds_s : 0, st, c->dev, x, xt, cons, aim, stats, static_cast<double*>(ws), pcg_max_iter,
+  hipLaunchKernelGGL(rs.kern, dim3(B), dim3(512), lds_sweep ? lds_s : 0, st, c->dev, x, xt, cons, aim, stats, static_cast<double*>(ws), pcg_max_iter,
                      pcg_tol_rate, ls_max_iter, dx_dev, dx_tol, step_info, stream_accumulate ? 1 : 0, fric ? xprev : nullptr, fric ? disp : nullptr,
                      c->fric_lag_mode == 1 ? 1 : 0, lds_sweep ? (lds_all ? 2 : 1) : 0, c->mat);
   hipError_t e = hipGetLastError();
@@ -3557,10 +3565,12 @@ int tacex_fem_step(tacex_fem_ctx* c, double* x, double* v, double* xt, const uin
   hipStream_t st = (hipStream_t)stream;
   const int V = c->dev.V;
   const size_t n3 = (size_t)B * V * 3;
-  double* xprev = static_cast<double*>(ws) + (size_t)B * newton_ws_doubles(V, c->dev.T);
-  double* dx = xprev + n3;  // (B,) max |d| per env: the device-side convergence state of this time step
-  double* disp = dx + B;    // (B,3) indenter displacement since the previous step | (B,3) indenter position of the previous step
-  double* ind_prev = disp + (size_t)3 * B;
+  const StepLayout lay(V, c->dev.T, B);
+  double* const base = static_cast<double*>(ws);
+  double* xprev = base + lay.x_prev;
+  double* dx = base + lay.dx;      // (B,) max |d| per env: the device-side convergence state of this time step
+  double* disp = base + lay.disp;  // (B,3) indenter displacement since the previous step | (B,3) indenter position of the previous step
+  double* ind_prev = base + lay.ind_prev;
   const double* ind = c->dev.indenters;
   const double dt = c->dev.dt, tol = velocity_tol * dt;
   hipLaunchKernelGGL(fem_predict_kernel, dim3((unsigned)((n3 + 255) / 256)), dim3(256), 0, st, x, v, xt, xprev, dx, n3, B, dt, gravity[0],
@@ -3571,7 +3581,7 @@ int tacex_fem_step(tacex_fem_ctx* c, double* x, double* v, double* xt, const uin
   static const int use_order = getenv("TACEX_FEM_ORDER") ? atoi(getenv("TACEX_FEM_ORDER")) : 1;
   int* env_order = nullptr;
   if (use_order && B > 1) {
-    env_order = reinterpret_cast<int*>(ind_prev + (size_t)3 * B + 1);  // behind the (B,3) previous indenter positions (tacex_fem_workspace_bytes)
+    env_order = reinterpret_cast<int*>(base + lay.env_order);
     hipLaunchKernelGGL(fem_env_order_kernel, dim3(1), dim3(1024), 0, st, step_info, B, env_order);
     e = hipGetLastError();
     if (e != hipSuccess) return fail_hip(e, "fem_env_order_kernel");
@@ -3685,12 +3695,11 @@ int tacex_fem_set_edge_edge(tacex_fem_ctx* c, int enable) {
   return 0;
 }
 
+static BallLayout ball_layout(const tacex_fem_ctx* c, int B) { return BallLayout(c->dev.V, c->dev.T, c->ball.nv, c->ball.nt, B); }
+
 size_t tacex_fem_ball_workspace_bytes(const tacex_fem_ctx* c, int B) {
   if (!c || B <= 0 || c->ball.nv == 0) return 0;
-  // env blocks | x_prev (B,V,3) | q_prev (B,12) | x~ (B,V,3) | q~ (B,12) | q at the end of the previous step (B,12) | env launch order (B int32)
-  // | elastic preconditioner blocks (B,V,16)
-  return ((size_t)B * ball_ws_doubles(c->dev.V, c->dev.T, c->ball.nv, c->ball.nt) + (size_t)B * 6 * c->dev.V + (size_t)B * 36 + 8 + ((size_t)B + 1) / 2 + 2 +
-          (size_t)B * 16 * c->dev.V) * sizeof(double);
+  return ball_layout(c, B).total * sizeof(double);
 }
 
 int tacex_fem_ball_moments(const tacex_fem_ctx* c, double moments_out[16], double* kappa_vol_out) {
@@ -3711,19 +3720,17 @@ static int ball_threads() {
 // up to 696 vertices; 697 at 256 threads) is refused with this message before anything is launched.
 static int ball_lds_ok(tacex_fem_ctx* c, const char* who) {
   const size_t lds = ball_lds_bytes(c->dev.V);
-  const int k = ball_threads() == 256 ? 0 : 1;
-  const void* kern = k == 0 ? reinterpret_cast<const void*>(fem_ball_newton_kernel<256>) : reinterpret_cast<const void*>(fem_ball_newton_kernel<512>);
-  static size_t avail[2][64] = {}, granted[2][64] = {};
+  const auto rb = ball_threads() == 256 ? route<fem_ball_newton_kernel<256>>() : route<fem_ball_newton_kernel<512>>();
   hipError_t e = hipSetDevice(c->device);
   size_t limit = 0;
-  if (e == hipSuccess) e = dynamic_lds_limit(kern, avail[k], &limit);
+  if (e == hipSuccess) e = dynamic_lds_limit(rb.id(), rb.lds->avail, &limit);
   if (e != hipSuccess) return fail_hip(e, "hipFuncGetAttributes(fem_ball_newton_kernel)");
   if (lds > limit) {
     set_error("%s: pad of %d vertices (x, p, accumulators and chain factors of one env must fit a CU's 160 KB of LDS: %zu B next to the kernel's "
               "%zu B of static LDS)", who, c->dev.V, lds, (size_t)160 * 1024 - limit);
     return 2;
   }
-  e = ensure_dynamic_lds(kern, lds, granted[k]);
+  e = ensure_dynamic_lds(rb.id(), lds, rb.lds->granted);
   return e == hipSuccess ? 0 : fail_hip(e, "hipFuncSetAttribute(fem_ball_newton_kernel)");
 }
 
@@ -3751,10 +3758,7 @@ int tacex_fem_ball_terms(tacex_fem_ctx* c, const double* x, const double* xt, co
 }
 
 // the (B,12) rows "q at the end of the previous step" of a ball workspace (see tacex_fem_ball_step)
-static double* ball_qlast(const tacex_fem_ctx* c, void* ws, int B) {
-  const size_t n3 = (size_t)B * c->dev.V * 3;
-  return static_cast<double*>(ws) + (size_t)B * ball_ws_doubles(c->dev.V, c->dev.T, c->ball.nv, c->ball.nt) + 2 * n3 + (size_t)B * 24;
-}
+static double* ball_qlast(const tacex_fem_ctx* c, void* ws, int B) { return static_cast<double*>(ws) + ball_layout(c, B).q_last; }
 
 int tacex_fem_ball_step(tacex_fem_ctx* c, double* x, double* v, double* q, double* qv, const uint8_t* cons, const double* aim, double* step_info,
                         void* ws, int B, const double gravity[3], int max_newton, double velocity_tol, double transrate_tol, int pcg_max_iter,
@@ -3773,13 +3777,15 @@ int tacex_fem_ball_step(tacex_fem_ctx* c, double* x, double* v, double* q, doubl
   hipStream_t st = (hipStream_t)stream;
   const int V = c->dev.V;
   const size_t n3 = (size_t)B * V * 3;
-  double* xprev = static_cast<double*>(ws) + (size_t)B * ball_ws_doubles(V, c->dev.T, c->ball.nv, c->ball.nt);
-  double* qprev = xprev + n3;
-  double* xt = qprev + (size_t)B * 12;
-  double* qt = xt + n3;
+  const BallLayout lay = ball_layout(c, B);
+  double* const base = static_cast<double*>(ws);
+  double* xprev = base + lay.x_prev;
+  double* qprev = base + lay.q_prev;
+  double* xt = base + lay.xt;
+  double* qt = base + lay.qt;
   // A KINEMATIC body is moved by the caller between steps: friction then slides relative to where the body stood at the END of the previous
   // step (kept here; the first step with this workspace sees no body motion), like the analytic indenters' displacement in tacex_fem_step
-  double* qlast = ball_qlast(c, ws, B);
+  double* qlast = base + lay.q_last;
   const bool have_last = c->ball.kinematic && c->ball_last_ws == ws && c->ball_last_B == B;
   const double dt = c->dev.dt;
   hipLaunchKernelGGL(fem_predict_kernel, dim3((unsigned)((n3 + 255) / 256)), dim3(256), 0, st, x, v, xt, xprev, static_cast<double*>(nullptr), n3, B, dt,
@@ -3789,21 +3795,12 @@ int tacex_fem_ball_step(tacex_fem_ctx* c, double* x, double* v, double* q, doubl
   int* env_order = nullptr;
   static const int use_order = getenv("TACEX_FEM_ORDER") ? atoi(getenv("TACEX_FEM_ORDER")) : 1;
   if (use_order && B > 256) {  // (step_info still holds the previous step's counts; a first step sorts zeros = index order)
-    env_order = reinterpret_cast<int*>(qlast + (size_t)B * 12 + 1);
+    env_order = reinterpret_cast<int*>(base + lay.env_order);
     hipLaunchKernelGGL(fem_env_order_kernel, dim3(1), dim3(1024), 0, st, step_info, B, env_order);
   }
   // elastic preconditioner blocks D | E of every env at the state the step starts from (what fem_newton_lds_kernel's launch does too)
-  double* blk = reinterpret_cast<double*>(reinterpret_cast<char*>(qlast + (size_t)B * 12) + (((size_t)B + 1) / 2 + 2) * sizeof(double));
-  {
-    static size_t granted_a[2][64] = {};
-    const bool asm_atom = !c->deterministic;
-    const size_t lds_a = ((size_t)3 * V + (asm_atom ? (size_t)15 * V : 0)) * sizeof(double);
-    auto ka = asm_atom ? fem_assemble_blocks_kernel<true, false> : fem_assemble_blocks_kernel<false, false>;
-    hipError_t ea = hipSetDevice(c->device);
-    if (ea == hipSuccess) ea = ensure_dynamic_lds(reinterpret_cast<const void*>(ka), lds_a, granted_a[asm_atom ? 1 : 0]);
-    if (ea != hipSuccess) return fail_hip(ea, "hipFuncSetAttribute(fem_assemble_blocks_kernel)");
-    hipLaunchKernelGGL(ka, dim3(B), dim3(512), lds_a, st, c->dev_nwt, x, blk, static_cast<const double*>(nullptr), 0.0, c->mat);
-  }
+  double* blk = base + lay.blk;
+  if (int rc = launch_assemble(c, x, blk, B, nullptr, 0.0, st, !c->deterministic)) return rc;  // (the device is current: ball_lds_ok)
   auto kern = ball_threads() == 256 ? fem_ball_newton_kernel<256> : fem_ball_newton_kernel<512>;
   hipLaunchKernelGGL(kern, dim3(B), dim3(ball_threads()), ball_lds_bytes(c->dev.V), st, c->dev, c->ball, x, xt, q, qt, cons, aim, static_cast<double*>(ws), pcg_max_iter,
                      pcg_tol_rate, ls_max_iter, max_newton, velocity_tol * dt, transrate_tol * dt, step_info, (ball_coarse_off ? 2 : 0) | ((c->ls_refine & 15) << 8),
@@ -3830,7 +3827,7 @@ int tacex_fem_reset_envs(tacex_fem_ctx* c, const int32_t* env_ids, int num_reset
   // env count means the next step has no previous positions at all
   double* ind_prev = nullptr;
   if (ws && c->dev.indenters && c->ind_prev_ws == ws && c->ind_prev_B == B)
-    ind_prev = static_cast<double*>(ws) + (size_t)B * newton_ws_doubles(V, c->dev.T) + (size_t)B * V * 3 + B + (size_t)3 * B;
+    ind_prev = static_cast<double*>(ws) + StepLayout(V, c->dev.T, B).ind_prev;
   hipLaunchKernelGGL(fem_reset_envs_kernel, dim3(num_reset), dim3(256), 0, (hipStream_t)stream, env_ids, positions, c->rest, x, v, step_info,
                      ind_prev, V, B);
   hipError_t e = hipGetLastError();
