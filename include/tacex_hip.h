@@ -248,7 +248,7 @@ int tacex_taxim_set_fots_partials(tacex_taxim_ctx* ctx, void* partials_dev, int 
  * antialiased bilinear down-sample of the RGB frame (torchvision resize semantics, as tasks feed 32x32x3 to the policy:
  * tacex_tasks/.../ball_rolling_tactile_rgb.py:303,318).  Where the fused tail kernel exists the horizontal half of the
  * filter is accumulated while the frame is still in LDS (the full-resolution frame is never re-read), otherwise it falls
- * back to the two-pass resize.  obs_scratch_dev: B * (max(H * obs_w, obs_h * W) + obs_h * obs_w) * 3 floats.
+ * back to the two-pass resize.  obs_scratch_dev: obs_scratch_floats (csrc/taxim_layout.h) = B * (max(H * obs_w, obs_h * W) + obs_h * obs_w) * 3.
  * obs_out_dev is float32, or uint8 with TACEX_FLAG_OBS_U8 (the image a CNN policy consumes; a quarter of the bytes in the
  * per-step observation all-gather). */
 int tacex_taxim_render_obs(tacex_taxim_ctx* ctx, const float* hm_mm_dev, const float* press_dev, float* frame_min_dev,

@@ -12,6 +12,7 @@
 
 #include "tacex_hip.h"
 #include "tacex_internal.h"
+#include "taxim_layout.h"
 
 namespace tacex {
 
@@ -79,7 +80,7 @@ struct tacex_taxim_ctx {
     float* hm = nullptr; float* fmin = nullptr; float* indent = nullptr; uint8_t* cam_u8 = nullptr; int* rows = nullptr;
     int B = 0;
   } depth_pass;
-  // second stream of the band levels (pipeline_impl: odd chunks of a pass run beside the even ones), created on first use
+  // second stream of the band levels (run_band_levels: odd chunks of a pass run beside the even ones), created on first use
   static constexpr int kMaxLvlStreams = 4;
   hipStream_t lvl_stream[kMaxLvlStreams - 1] = {}; hipStream_t lvl_caller = nullptr; hipEvent_t lvl_fork = nullptr, lvl_join[kMaxLvlStreams - 1] = {}, order_evt = nullptr;
   std::vector<void*> allocs;
@@ -248,8 +249,6 @@ void tacex_taxim_destroy(tacex_taxim_ctx* c) {
   for (void* p : c->allocs) (void)hipFree(p);
   delete c;
 }
-
-static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 // Triangle-filter taps of torchvision's antialiased bilinear resize (GelSightSensor's 32 x 32 policy observation),
 // one axis: the same fp32 expressions as resize_v_kernel / the oracle's resize_bilinear_aa.
@@ -447,9 +446,7 @@ int tacex_taxim_set_shadow(tacex_taxim_ctx* c, const tacex_shadow_params* p) {
 }
 
 size_t tacex_taxim_shadow_workspace_bytes(const tacex_taxim_ctx* c, int B) {
-  if (!c || B <= 0) return 0;
-  const size_t img = align_up((size_t)B * c->H * c->W * sizeof(float), 256);
-  return 12 * img;  // deformed gel 1, mask 1 (u8, one image slot), gdir 1, raw 3, shadow 3, tmp 3
+  return (c && B > 0) ? ShadowLayout(c->H, c->W, B).total : 0;
 }
 
 int tacex_taxim_shadow_rays(tacex_taxim_ctx* c, const float* z, const uint8_t* mask, const float* gdir, float* shadow_min, int B,
@@ -462,16 +459,7 @@ int tacex_taxim_shadow_rays(tacex_taxim_ctx* c, const float* z, const uint8_t* m
 }
 
 size_t tacex_taxim_workspace_bytes(const tacex_taxim_ctx* c, int B) {
-  if (!c || B <= 0) return 0;
-  const size_t img = align_up((size_t)B * c->H * c->W * sizeof(float), 256);
-  const size_t vec = align_up((size_t)B * sizeof(float), 256);
-  return 3 * img + 3 * vec + align_up((size_t)B * 4 * sizeof(int), 256);  // Z ping, Z pong, generic-path temp; shift_a, shift_b, pdepth; contact rows / columns
-}
-// where the library keeps the contact row ranges it computes itself (behind everything a chunk of <= B frames lays out)
-static int* workspace_rows(const tacex_taxim_ctx* c, void* ws, int B) {
-  const size_t img = align_up((size_t)B * c->H * c->W * sizeof(float), 256);
-  const size_t vec = align_up((size_t)B * sizeof(float), 256);
-  return reinterpret_cast<int*>(static_cast<char*>(ws) + 3 * img + 3 * vec);
+  return (c && B > 0) ? PassLayout(c->H, c->W, B).total : 0;
 }
 
 int tacex_taxim_set_profiling(tacex_taxim_ctx* c, int enabled) {
@@ -525,20 +513,15 @@ struct StageTimer {
 
 }  // extern "C"
 
-// frames [b0, b0 + nb) of a depth -> height map pass (GS:581-593 + TS:115-131 + contact row / column ranges)
-static int depth_pass_range(const tacex_taxim_ctx::DepthPass& d, int b0, int nb, int H, int W, hipStream_t st) {
-  const size_t o = (size_t)b0 * H * W;
-  uint8_t* u8 = d.cam_u8 ? d.cam_u8 + o : nullptr;
-  float* ind = d.indent ? d.indent + b0 : nullptr;
+// the d.B frames of a depth -> height map pass (GS:581-593 + TS:115-131 + contact row / column ranges)
+static int run_depth_pass(const tacex_taxim_ctx::DepthPass& d, int H, int W, hipStream_t st) {
   if (d.rows && frame_rows_supported(H, W)) {
-    HIP_TRY(run_frame_rows(d.depth + o, true, d.hm + o, d.fmin + b0, ind, u8, nullptr, d.rows + 4 * b0, nb, H, W, d.near_mm, d.far_m, d.far_mm,
-                           d.gelpad_h, d.gelpad_dmin, st),
-            "frame_rows_kernel<depth>");
+    HIP_TRY(run_frame_rows(d.depth, true, d.hm, d.fmin, d.indent, d.cam_u8, nullptr, d.rows, d.B, H, W, d.near_mm, d.far_m, d.far_mm, d.gelpad_h,
+                           d.gelpad_dmin, st), "frame_rows_kernel<depth>");
     return 0;
   }
-  if (d.rows) HIP_TRY(run_fill_rows(d.rows + 4 * b0, nb, H, W, st), "fill_rows_kernel");
-  HIP_TRY(run_frame_min(d.depth + o, true, d.hm + o, d.fmin + b0, ind, u8, nb, H * W, d.near_mm, d.far_m, d.far_mm, d.gelpad_h, d.gelpad_dmin, st),
-          "frame_min_kernel<depth>");
+  if (d.rows) HIP_TRY(run_fill_rows(d.rows, d.B, H, W, st), "fill_rows_kernel");
+  HIP_TRY(run_frame_min(d.depth, true, d.hm, d.fmin, d.indent, d.cam_u8, d.B, H * W, d.near_mm, d.far_m, d.far_mm, d.gelpad_h, d.gelpad_dmin, st), "frame_min_kernel<depth>");
   return 0;
 }
 
@@ -563,7 +546,7 @@ int tacex_height_map_from_depth(const float* depth_m, double near_m, double far_
   if (int rc = fill_depth_pass(&d, "tacex_height_map_from_depth", depth_m, near_m, far_m, gelpad_h, gelpad_dmin, hm_mm, frame_min, indent_mm,
                                cam_u8, frame_rows, B)) return rc;
   if (B <= 0) return 0;
-  return depth_pass_range(d, 0, B, H, W, (hipStream_t)stream);
+  return run_depth_pass(d, H, W, (hipStream_t)stream);
 }
 
 int tacex_taxim_defer_height_map_from_depth(tacex_taxim_ctx* c, const float* depth_m, double near_m, double far_m, float gelpad_h,
@@ -581,7 +564,7 @@ int tacex_taxim_flush_deferred(tacex_taxim_ctx* c, void* stream) {
   if (!c) { set_error("tacex_taxim_flush_deferred: null context"); return 2; }
   if (!c->depth_pass.armed) return 0;
   c->depth_pass.armed = false;
-  return depth_pass_range(c->depth_pass, 0, c->depth_pass.B, c->H, c->W, (hipStream_t)stream);
+  return run_depth_pass(c->depth_pass, c->H, c->W, (hipStream_t)stream);
 }
 
 int tacex_height_map_from_indenters(const float* indenters, float pixmm, float gel_top_mm, float far_clip_mm, float gelpad_h,
@@ -613,19 +596,52 @@ int tacex_indentation_depth(const float* hm_mm, float gelpad_h, float gelpad_dmi
   return 0;
 }
 
-static int pipeline_chunk(tacex_taxim_ctx* c, const float* hm, const float* press, float* frame_min, float* rgb,
-                          float* z_out, uint8_t* mask_out, void* ws, int B, unsigned flags, hipStream_t st,
-                          float* obs_h, void* obs, int obs_hh, int obs_w, FotsReduce* fots_part, int frame0,
-                          const int* rows = nullptr, const tacex_taxim_ctx::DepthPass* dp = nullptr);
+// One pass of the pipeline: what an entry point was asked for (make_pass + the outputs it wants) and what pipeline_impl adds to it.
+struct Pass {
+  int H = 0, W = 0;
+  const float* hm = nullptr; const float* press = nullptr; float* frame_min = nullptr;  // inputs (frame_min: scratch / in)
+  float* rgb = nullptr; float* z_out = nullptr; uint8_t* mask_out = nullptr;            // outputs, each nullable
+  void* obs = nullptr; float* obs_scratch = nullptr; int oh = 0, ow = 0; bool u8 = false;  // policy observation (the scratch belongs to the pass, not to a frame)
+  void* ws = nullptr; int B = 0; unsigned flags = 0; hipStream_t stream = nullptr;
+  FotsReduce* fots_part = nullptr;   // per-wave FOTS contact statistics of the fused tails, nullable
+  int frame0 = -1;                   // first frame's slot in the context's marker-pixel buffers (-1: they do not hold the batch)
+  const int* rows = nullptr;         // contact row / column ranges (zero-band skipping), nullable
+  tacex_taxim_ctx::DepthPass depth;  // armed: the deferred depth pass that produces hm / frame_min / press, still to run
+  // frames [b0, b0 + n): the one place that knows the per-frame stride of each buffer
+  Pass slice(int b0, int n) const {
+    const size_t npix = (size_t)H * W;
+    Pass q = *this;
+    q.B = n; q.hm += b0 * npix; q.frame_min += b0;
+    if (press) q.press += b0;
+    if (rgb) q.rgb += b0 * npix * 3;
+    if (z_out) q.z_out += b0 * npix;
+    if (mask_out) q.mask_out += b0 * npix;
+    if (obs) q.obs = static_cast<char*>(obs) + (size_t)b0 * oh * ow * 3 * (u8 ? 1 : 4);
+    if (fots_part) q.fots_part += (size_t)b0 * tail_tiles_per_frame(H, W) * kTailWavesPerTile;
+    if (frame0 >= 0) q.frame0 += b0;
+    if (rows) q.rows += 4 * b0;
+    if (depth.armed) {
+      tacex_taxim_ctx::DepthPass& d = q.depth;
+      d.depth += b0 * npix; d.hm += b0 * npix; d.fmin += b0; d.B = n;
+      if (d.indent) d.indent += b0;
+      if (d.cam_u8) d.cam_u8 += b0 * npix;
+      if (d.rows) d.rows += 4 * b0;
+    }
+    return q;
+  }
+};
+static Pass make_pass(const tacex_taxim_ctx* c, const float* hm, const float* press, float* frame_min, void* ws, int B, unsigned flags, void* stream) {
+  Pass p; p.H = c->H; p.W = c->W; p.hm = hm; p.press = press; p.frame_min = frame_min; p.ws = ws; p.B = B; p.flags = flags; p.stream = (hipStream_t)stream;
+  return p;
+}
 
-// The extra streams the band levels of a pass alternate on (TWO CHUNKS IN FLIGHT, pipeline_chunk) come from ONE pool per device,
-// created at first use and kept for the life of the process.  A stream per CONTEXT (round 4) made what a context measured depend on
+// The extra streams the band levels of a pass alternate on (TWO CHUNKS IN FLIGHT, plan_band_levels) come from ONE pool per device,
+// created at first use and kept for the life of the process.  A stream per CONTEXT made what a context measured depend on
 // how many streams the process had created before it: HIP deals streams onto a handful of hardware queues round-robin, and a
 // context whose level stream lands on the queue of the caller's stream runs its "two chunks in flight" one after the other
 // (bench.py sweep, 640x480: 110 K frames/s as the 17th rig of a process against 128 K on its own; profiles/r05_experiments.md section 7).
-// Round 6: the pool is keyed by (device, caller stream) - contexts driven on DIFFERENT caller streams (bench --sensor-streams, multi-threaded
-// hosts) get different side streams, so one context's fork wait does not serialise the other's chunks; all contexts on one caller stream
-// (every test, the bench default) still share lane 0, which is what made measurements independent of context creation order.
+// The pool is keyed by (device, caller stream): contexts driven on DIFFERENT caller streams (bench --sensor-streams, multi-threaded hosts)
+// get different side streams, so one context's fork wait does not serialise the other's chunks; all contexts on one caller stream share lane 0.
 static hipError_t level_stream(int device, hipStream_t caller, int q, hipStream_t* out) {
   constexpr int kLanes = 4;
   static std::mutex mu;
@@ -678,8 +694,9 @@ static int chunk_frames(const tacex_taxim_ctx* c, int B) {
 
 // Frames per launch of the band levels inside one pass that ends in the streaming tail (TACEX_LEVEL_CHUNK_FRAMES overrides,
 // 0 = the whole pass): 3 buffers x 4 B/px per frame against the 256 MB Infinity Cache.
+static int level_chunk_env() { static const int env = getenv("TACEX_LEVEL_CHUNK_FRAMES") ? atoi(getenv("TACEX_LEVEL_CHUNK_FRAMES")) : -1; return env; }
 static int level_chunk_frames(const tacex_taxim_ctx* c, int B) {
-  static const int env = getenv("TACEX_LEVEL_CHUNK_FRAMES") ? atoi(getenv("TACEX_LEVEL_CHUNK_FRAMES")) : -1;
+  const int env = level_chunk_env();
   if (env == 0) return B;
   if (env > 0) return env < B ? env : B;
   const size_t per_frame = (size_t)3 * c->H * c->W * sizeof(float);
@@ -691,114 +708,29 @@ static int level_chunk_frames(const tacex_taxim_ctx* c, int B) {
 
 int tacex_taxim_chunk_frames(const tacex_taxim_ctx* c, int B) { return (c && B > 0) ? chunk_frames(c, B) : 0; }
 
-static int pipeline_impl(tacex_taxim_ctx* c, const float* hm, const float* press, float* frame_min, float* rgb,
-                         float* z_out, uint8_t* mask_out, void* ws, int B, unsigned flags, hipStream_t st,
-                         float* obs_h = nullptr, void* obs = nullptr, int obs_hh = 0, int obs_w = 0) {
-  const int cf = chunk_frames(c, B);
-  // A deferred depth -> height map pass (tacex_taxim_defer_height_map_from_depth) that produces exactly this call's inputs runs inside
-  // the pass, chunk by chunk (pipeline_chunk); one that does not is run in full first - it was promised no later than this call.
-  tacex_taxim_ctx::DepthPass dpl;
-  const tacex_taxim_ctx::DepthPass* dp = nullptr;
-  if (c->depth_pass.armed) {
-    c->depth_pass.armed = false;
-    dpl = c->depth_pass;
-    const bool fits = dpl.B == B && dpl.hm == hm && dpl.fmin == frame_min && dpl.indent == press && press &&
-                      (flags & TACEX_FLAG_HAVE_FRAME_MIN) && !(flags & TACEX_FLAG_NO_SHIFT) &&
-                      (!(flags & TACEX_FLAG_HAVE_FRAME_ROWS) || dpl.rows == c->frame_rows);
-    if (fits) dp = &dpl;
-    else if (int rc = depth_pass_range(dpl, 0, dpl.B, c->H, c->W, st)) return rc;
-  }
-  FotsReduce* fp = (c->fots_part && B <= c->fots_cap) ? c->fots_part : nullptr;
-  const size_t fper = tail_tiles_per_frame(c->H, c->W) * kTailWavesPerTile;
-  // Contact row ranges (zero-band skipping of the band levels, TACEX_BAND_SKIP=0 disables): from the caller's buffer when the
-  // minimum came with them, else from the library's own minimum pass (kept behind the chunk layouts of the workspace)
-  static const bool band_skip = !(getenv("TACEX_BAND_SKIP") && atoi(getenv("TACEX_BAND_SKIP")) == 0);
-  const bool can_rows = band_skip && press && !(flags & TACEX_FLAG_NO_SHIFT) && frame_rows_supported(c->H, c->W);
-  const int* rows = nullptr;
-  if (flags & TACEX_FLAG_HAVE_FRAME_MIN) {
-    if (can_rows && (flags & TACEX_FLAG_HAVE_FRAME_ROWS) && c->frame_rows && B <= c->frame_rows_cap) rows = c->frame_rows;
-  } else {  // one reduction pass over the whole shard
-    StageTimer t(c, st, 0);
-    if (can_rows) {
-      int* wr = workspace_rows(c, ws, B);
-      HIP_TRY(run_frame_rows(hm, false, nullptr, frame_min, nullptr, nullptr, press, wr, B, c->H, c->W, 0.f, 0.f, 0.f, 0.f, 0.f, st),
-              "frame_rows_kernel");
-      rows = wr;
-    } else {
-      HIP_TRY(run_frame_min(hm, false, nullptr, frame_min, nullptr, nullptr, B, c->H * c->W, 0.f, 0.f, 0.f, 0.f, 0.f, st),
-              "frame_min_kernel");
-    }
-    flags |= TACEX_FLAG_HAVE_FRAME_MIN;
-  }
-  if (cf >= B)
-    return pipeline_chunk(c, hm, press, frame_min, rgb, z_out, mask_out, ws, B, flags, st, obs_h, obs, obs_hh, obs_w, fp,
-                          B <= c->fots_pix_cap ? 0 : -1, rows, dp);
-  const size_t npix = (size_t)c->H * c->W;
-  for (int b0 = 0; b0 < B; b0 += cf) {
-    const int n = B - b0 < cf ? B - b0 : cf;
-    tacex_taxim_ctx::DepthPass dpc;
-    if (dp) {  // the chunk's share of the deferred pass
-      dpc = *dp;
-      dpc.depth += b0 * npix; dpc.hm += b0 * npix; dpc.fmin += b0; dpc.indent += b0; dpc.B = n;
-      if (dpc.cam_u8) dpc.cam_u8 += b0 * npix;
-      if (dpc.rows) dpc.rows += 4 * b0;
-    }
-    int rc = pipeline_chunk(c, hm + b0 * npix, press ? press + b0 : nullptr, frame_min + b0, rgb ? rgb + b0 * npix * 3 : nullptr,
-                            z_out ? z_out + b0 * npix : nullptr, mask_out ? mask_out + b0 * npix : nullptr, ws, n,
-                            flags, st, obs_h,
-                            obs ? static_cast<char*>(obs) + (size_t)b0 * obs_hh * obs_w * 3 * ((flags & TACEX_FLAG_OBS_U8) ? 1 : 4) : nullptr,
-                            obs_hh, obs_w, fp ? fp + (size_t)b0 * fper : nullptr, B <= c->fots_pix_cap ? b0 : -1,
-                            rows ? rows + 4 * b0 : nullptr, dp ? &dpc : nullptr);
-    if (rc) return rc;
-  }
-  return 0;
-}
-
 // two-pass antialiased down-sample of the finished frame (scratch = [resize temp | float observation when the caller wants uint8])
-static int resize_obs(tacex_taxim_ctx* c, const float* rgb, float* scratch, void* obs, bool u8, int oh, int ow, int B, hipStream_t st) {
-  const size_t tmp_floats = (size_t)B * (size_t)(c->H * ow > oh * c->W ? c->H * ow : oh * c->W) * 3;
-  float* dst = u8 ? scratch + tmp_floats : static_cast<float*>(obs);
-  HIP_TRY(run_resize_aa(rgb, c->H, c->W, dst, oh, ow, B, 3, scratch, st), "resize_aa (observation)");
-  if (u8) HIP_TRY(run_obs_to_u8(dst, static_cast<uint8_t*>(obs), (size_t)B * oh * ow * 3, st), "obs_to_u8_kernel");
+static int resize_obs(tacex_taxim_ctx* c, const Pass& p) {
+  float* dst = p.u8 ? p.obs_scratch + obs_resize_floats(c->H, c->W, p.oh, p.ow, p.B) : static_cast<float*>(p.obs);
+  HIP_TRY(run_resize_aa(p.rgb, c->H, c->W, dst, p.oh, p.ow, p.B, 3, p.obs_scratch, p.stream), "resize_aa (observation)");
+  if (p.u8) HIP_TRY(run_obs_to_u8(dst, static_cast<uint8_t*>(p.obs), (size_t)p.B * p.oh * p.ow * 3, p.stream), "obs_to_u8_kernel");
   return 0;
 }
 
-static int pipeline_chunk(tacex_taxim_ctx* c, const float* hm, const float* press, float* frame_min, float* rgb,
-                          float* z_out, uint8_t* mask_out, void* ws, int B, unsigned flags, hipStream_t st,
-                          float* obs_h, void* obs, int obs_hh, int obs_w, FotsReduce* fots_part, int frame0,
-                          const int* rows, const tacex_taxim_ctx::DepthPass* dp) {
-  const bool obs_u8 = (flags & TACEX_FLAG_OBS_U8) != 0;
-  const size_t img = align_up((size_t)B * c->H * c->W * sizeof(float), 256);
-  const size_t vec = align_up((size_t)B * sizeof(float), 256);
-  char* w = static_cast<char*>(ws);
-  float* zbuf[2] = {reinterpret_cast<float*>(w), reinterpret_cast<float*>(w + img)};
-  float* tmp = reinterpret_cast<float*>(w + 2 * img);
-  const float* sa = reinterpret_cast<float*>(w + 3 * img);
-  const float* sb = reinterpret_cast<float*>(w + 3 * img + vec);
-  const float* pd = reinterpret_cast<float*>(w + 3 * img + 2 * vec);
-  const bool no_shift = (flags & TACEX_FLAG_NO_SHIFT) != 0;
-  if (!(flags & TACEX_FLAG_HAVE_FRAME_MIN)) {
-    StageTimer t(c, st, 0);
-    HIP_TRY(run_frame_min(hm, false, nullptr, frame_min, nullptr, nullptr, B, c->H * c->W, 0.f, 0.f, 0.f, 0.f, 0.f, st),
-            "frame_min_kernel");
-  }
-  if (no_shift) {  // S = hm, P = -min(hm): zeros / negated minima need their own (B,) arrays
-    HIP_TRY(run_press_depth(frame_min, press, const_cast<float*>(sa), const_cast<float*>(sb), const_cast<float*>(pd), B, 1, st),
-            "press_depth_kernel");
-  } else {
-    // S = (hm - min) - press (TT:441) and P = -min(S) = -((min - min) - press) = press (TT:449): the per-frame scalars
-    // the kernels read ARE the frame-min and press arrays - no (B,)-sized helper launch (~5 us of a ~600 us step)
-    sa = frame_min; sb = press; pd = press;
-  }
-  const int n_fused = c->use_tail ? c->n_fused : 0;
-  const int n_band = c->n_levels - n_fused;
-  const float* src = nullptr;
-  const bool stream_tail = n_fused > 0 && c->use_stream && rgb && !z_out && !mask_out &&
-                           stream_supported(n_fused, c->levels[c->n_levels - n_fused].kw, c->H, c->W);
+// What the pieces of one pass share: Z ping / pong and the scratch image of the two-pass (generic) blur; the (B,) shift_a, shift_b and press
+// depth the kernels read; trailing levels of the fused tail and band levels ahead of them; the rows by which the band levels spread the
+// non-zero range of their output beyond the contact rows.
+struct PassState { float* z[2]; float* tmp; const float *sa, *sb, *pd; int n_fused, n_band, band_grow; bool stream_tail; };
+
+// How the band levels of a pass are launched: frames per launch of a level; streams the chunks alternate on (1 = the caller's alone);
+// depth_interleaved: the pass's deferred depth pass runs chunk by chunk on the chunk's stream (false: none, or in full ahead of the levels);
+// order_early: the item order of the streaming tail is issued beside the levels.
+struct LevelPlan { int frames, streams, n_chunks; bool depth_interleaved, order_early; };
+
+static LevelPlan plan_band_levels(const tacex_taxim_ctx* c, const Pass& p, const PassState& s) {
+  LevelPlan lp{};
   // Band levels ahead of a streaming tail run over sub-ranges of the pass (level_chunk_frames): the tail wants >= 2048 strips
   // per launch, the band kernels want their three frame-sized buffers (height map, Z ping, Z pong) in the Infinity Cache.
-  int lcf = stream_tail ? level_chunk_frames(c, B) : B;
-  const size_t npix = (size_t)c->H * c->W;
+  lp.frames = s.stream_tail ? level_chunk_frames(c, p.B) : p.B;
   // TWO CHUNKS IN FLIGHT: the chunks of a pass are independent until the tail, and a band-level launch of 128-256 frames spends
   // ~14 us of its 40-77 us ramping up and draining (k = 61: 45.5 us for 128 frames, 76.9 for 256).  Chunks therefore run round-robin on the
   // caller's stream and on streams of the context's own - at a chunk size divided by the stream count, so that the frames in flight (and
@@ -809,78 +741,79 @@ static int pipeline_chunk(tacex_taxim_ctx* c, const float* hm, const float* pres
   // (a pass of fewer than three chunks gains 1.4 % - 512 frames of 320x240 - and loses it again when the caller overlaps the pass with
   //  other work of its own, the FEM step of C4: there the extra stream only adds contention.  Three and more: 2.7 % at 1024 frames of
   //  320x240, 8.5 % at 640x480.)
-  bool dual = stream_tail && lvl_streams > 1 && !c->profiling && n_band > 0 && lcf < B && (B + lcf - 1) / lcf >= 3;
-  for (int l = 0; dual && l < n_band; ++l)
+  bool dual = s.stream_tail && lvl_streams > 1 && !c->profiling && s.n_band > 0 && lp.frames < p.B && (p.B + lp.frames - 1) / lp.frames >= 3;
+  for (int l = 0; dual && l < s.n_band; ++l)
     dual = blur_level_single_kernel(c->levels[l], l == 0, c->H, c->W);
+  lp.streams = dual ? lvl_streams : 1;
+  if (dual && level_chunk_env() < 0) lp.frames = (lp.frames + lvl_streams - 1) / lvl_streams;  // (an explicit chunk size is taken as given)
+  lp.n_chunks = (p.B + lp.frames - 1) / lp.frames;
+  // A deferred depth pass is interleaved with the band levels only where that pays: chunks alternating on two streams, and chunks of
+  // >= 128 frames (the pass runs one workgroup per frame).  Measured (profiles/r05_experiments.md section 15): 320x240 in 128-frame chunks
+  // +3.2 % on C3; 640x480 in its 32-frame chunks -11 %, in units of 128-1024 frames -0.5..-4 %.  Otherwise: in full, ahead of the levels.
+  static const int depth_min_frames = getenv("TACEX_DEPTH_INTERLEAVE_MIN_FRAMES") ? atoi(getenv("TACEX_DEPTH_INTERLEAVE_MIN_FRAMES")) : 128;
+  lp.depth_interleaved = p.depth.armed && dual && lp.frames >= depth_min_frames;
+  // ITEM ORDER OF THE TAIL, EARLY: stream_order_kernel needs the contact rows only.  On the two-streams path it is issued beside the band
+  // levels - right behind the fork when the caller brought the rows, behind the last two depth passes when they are this pass's own
+  // (deferred) - instead of between the levels' join and the tail (9.5 us + the join's ~12 us of queue turnaround on the critical path,
+  // profiles/r05_experiments.md section 22).  TACEX_STREAM_ORDER_EARLY=0: between the join and the tail.
+  static const int order_early_env = getenv("TACEX_STREAM_ORDER_EARLY") ? atoi(getenv("TACEX_STREAM_ORDER_EARLY")) : 1;
+  lp.order_early = order_early_env != 0 && s.stream_tail && dual && lvl_streams == 2 && p.rows != nullptr && lp.n_chunks >= 3;
+  return lp;
+}
+
+// The band levels of a pass, chunk by chunk: fork onto the level streams, the deferred depth pass, the early item order, the join.
+// *out: what the last level wrote (nullptr without band levels); *order_done: the tail's item order has been issued.
+static int run_band_levels(tacex_taxim_ctx* c, const Pass& p, const PassState& s, const LevelPlan& lp, const float** out, bool* order_done) {
+  hipStream_t const st = p.stream;
+  const size_t npix = (size_t)c->H * c->W;
+  const bool dual = lp.streams > 1;
+  if (p.depth.armed && !lp.depth_interleaved)
+    if (int rc = run_depth_pass(p.depth, c->H, c->W, st)) return rc;
   if (dual) {
     if (!c->lvl_fork) HIP_TRY(hipEventCreateWithFlags(&c->lvl_fork, hipEventDisableTiming), "hipEventCreate");
-    for (int q = 0; q < lvl_streams - 1; ++q) {
+    for (int q = 0; q < lp.streams - 1; ++q) {
       if (!c->lvl_stream[q] || c->lvl_caller != st)
         if (hipError_t es = level_stream(c->device, st, q, &c->lvl_stream[q]); es != hipSuccess) return fail_hip(es, "hipStreamCreate(band levels)");
       if (!c->lvl_join[q]) HIP_TRY(hipEventCreateWithFlags(&c->lvl_join[q], hipEventDisableTiming), "hipEventCreate");
     }
     c->lvl_caller = st;
-    static const int env_lcf = getenv("TACEX_LEVEL_CHUNK_FRAMES") ? atoi(getenv("TACEX_LEVEL_CHUNK_FRAMES")) : -1;
-    if (env_lcf < 0) lcf = (lcf + lvl_streams - 1) / lvl_streams;
-  }
-  // A deferred depth pass is interleaved with the band levels only where that pays: chunks alternating on two streams, and chunks of
-  // >= 128 frames (the pass runs one workgroup per frame).  Measured (profiles/r05_experiments.md section 15): 320x240 in 128-frame chunks
-  // +3.2 % on C3; 640x480 in its 32-frame chunks -11 %, in units of 128-1024 frames -0.5..-4 %.  Otherwise: in full, ahead of the levels.
-  static const int depth_min_frames = getenv("TACEX_DEPTH_INTERLEAVE_MIN_FRAMES") ? atoi(getenv("TACEX_DEPTH_INTERLEAVE_MIN_FRAMES")) : 128;
-  if (dp && (!dual || lcf < depth_min_frames)) {
-    if (int rc = depth_pass_range(*dp, 0, B, c->H, c->W, st)) return rc;
-    dp = nullptr;
-  }
-  if (dual) {
     HIP_TRY(hipEventRecord(c->lvl_fork, st), "hipEventRecord");  // the pass's inputs (height map, shifts, rows) are ready behind this
-    for (int q = 0; q < lvl_streams - 1; ++q) HIP_TRY(hipStreamWaitEvent(c->lvl_stream[q], c->lvl_fork, 0), "hipStreamWaitEvent");
+    for (int q = 0; q < lp.streams - 1; ++q) HIP_TRY(hipStreamWaitEvent(c->lvl_stream[q], c->lvl_fork, 0), "hipStreamWaitEvent");
   }
-  hipStream_t const st_main = st;
-  // ITEM ORDER OF THE TAIL, EARLY: stream_order_kernel needs the contact rows only.  On the two-streams path it is issued beside the band
-  // levels - right behind the fork when the caller brought the rows, behind the last two depth passes when they are this pass's own
-  // (deferred) - instead of between the levels' join and the tail (9.5 us + the join's ~12 us of queue turnaround on the critical path,
-  // profiles/r05_experiments.md section 22).  TACEX_STREAM_ORDER_EARLY=0: as before.
-  static const int order_early_env = getenv("TACEX_STREAM_ORDER_EARLY") ? atoi(getenv("TACEX_STREAM_ORDER_EARLY")) : 1;
   const StreamPlan* tail_plan = nullptr;
-  bool order_done = false;
-  int band_grow_rows = 0;
-  for (int l = 0; l < n_band; ++l) band_grow_rows += (c->levels[l].kh - 1) / 2;
-  const int n_chunks = (B + lcf - 1) / lcf;
-  bool order_early = order_early_env != 0 && stream_tail && dual && lvl_streams == 2 && rows != nullptr && n_chunks >= 3;
+  bool order_early = lp.order_early;
   if (order_early) {
-    const bool want_obs_p = obs_h && obs;
-    if (int rc = stream_plan(c, n_fused, B, want_obs_p ? obs_hh : 0, want_obs_p ? obs_w : 0, &tail_plan)) return rc;
-    if (B * tail_plan->nstrips * tail_plan->nseg > c->stream_order_cap) order_early = false;
+    const bool want_obs = p.obs_scratch && p.obs;
+    if (int rc = stream_plan(c, s.n_fused, p.B, want_obs ? p.oh : 0, want_obs ? p.ow : 0, &tail_plan)) return rc;
+    if (p.B * tail_plan->nstrips * tail_plan->nseg > c->stream_order_cap) order_early = false;
   }
-  if (order_early && !dp) {  // rows from the caller: ready behind the fork; on the second stream, ahead of its first chunk
-    HIP_TRY(run_stream_order(c->levels, c->n_levels, n_fused, *tail_plan, B, c->H, rows, band_grow_rows, c->stream_order, c->lvl_stream[0], &order_done),
+  if (order_early && !lp.depth_interleaved)  // rows from the caller: ready behind the fork; on the second stream, ahead of its first chunk
+    HIP_TRY(run_stream_order(c->levels, c->n_levels, s.n_fused, *tail_plan, p.B, c->H, p.rows, s.band_grow, c->stream_order, c->lvl_stream[0], order_done),
             "stream_order_kernel");
-  }
-  int chunk_no = 0;
-  for (int b0 = 0; b0 < B; b0 += lcf, ++chunk_no) {
-    const int nb = B - b0 < lcf ? B - b0 : lcf;
-    const int lane_q = dual ? chunk_no % lvl_streams : 0;
-    hipStream_t st = lane_q > 0 ? c->lvl_stream[lane_q - 1] : st_main;  // (shadows the pass's stream inside the chunk)
-    if (dp) {  // this chunk's height maps, minima, indentation depths and contact ranges: on the chunk's stream, ahead of its levels
-      if (int rc = depth_pass_range(*dp, b0, nb, c->H, c->W, st)) return rc;
-      if (order_early && chunk_no == n_chunks - 2) {  // the last depth pass of THIS stream: the other stream's order launch waits for it
+  const float* src = nullptr;
+  for (int b0 = 0, chunk_no = 0; b0 < p.B; b0 += lp.frames, ++chunk_no) {
+    const Pass q = p.slice(b0, p.B - b0 < lp.frames ? p.B - b0 : lp.frames);
+    const int lane = dual ? chunk_no % lp.streams : 0;
+    hipStream_t const cst = lane > 0 ? c->lvl_stream[lane - 1] : st;  // the chunk's stream
+    if (lp.depth_interleaved) {  // this chunk's height maps, minima, indentation depths and contact ranges: on the chunk's stream, ahead of its levels
+      if (int rc = run_depth_pass(q.depth, c->H, c->W, cst)) return rc;
+      if (order_early && chunk_no == lp.n_chunks - 2) {  // the last depth pass of THIS stream: the other stream's order launch waits for it
         if (!c->order_evt) HIP_TRY(hipEventCreateWithFlags(&c->order_evt, hipEventDisableTiming), "hipEventCreate");
-        HIP_TRY(hipEventRecord(c->order_evt, st), "hipEventRecord");
-      } else if (order_early && chunk_no == n_chunks - 1) {  // every frame's rows are written once this one and the other stream's last are done
-        HIP_TRY(hipStreamWaitEvent(st, c->order_evt, 0), "hipStreamWaitEvent");
-        HIP_TRY(run_stream_order(c->levels, c->n_levels, n_fused, *tail_plan, B, c->H, rows, band_grow_rows, c->stream_order, st, &order_done),
+        HIP_TRY(hipEventRecord(c->order_evt, cst), "hipEventRecord");
+      } else if (order_early && chunk_no == lp.n_chunks - 1) {  // every frame's rows are written once this one and the other stream's last are done
+        HIP_TRY(hipStreamWaitEvent(cst, c->order_evt, 0), "hipStreamWaitEvent");
+        HIP_TRY(run_stream_order(c->levels, c->n_levels, s.n_fused, *tail_plan, p.B, c->H, p.rows, s.band_grow, c->stream_order, cst, order_done),
                 "stream_order_kernel");
       }
     }
     src = nullptr;
     int grow = 0, grow_x = 0;  // rows / columns by which the non-zero range of the level's input exceeds the contact rows / columns
-    for (int l = 0; l < n_band; ++l) {
+    for (int l = 0; l < s.n_band; ++l) {
       const bool last = l == c->n_levels - 1;
-      float* dst = (last && z_out) ? z_out : zbuf[l & 1];
-      StageTimer t(c, st, 1 + l);
-      HIP_TRY(run_blur_level(c->levels[l], src ? src + b0 * npix : nullptr, hm + b0 * npix, c->gel_dev, sa + b0, sb + b0, pd + b0,
-                             dst + b0 * npix, tmp, last && mask_out ? mask_out + b0 * npix : nullptr, nb,
-                             c->H, c->W, c->contact_scale, last ? 0 : 1, l == 0, st, rows ? rows + 4 * b0 : nullptr, grow, grow_x),
+      float* dst = (last && p.z_out) ? p.z_out : s.z[l & 1];
+      StageTimer t(c, cst, 1 + l);
+      HIP_TRY(run_blur_level(c->levels[l], src ? src + b0 * npix : nullptr, q.hm, c->gel_dev, s.sa + b0, s.sb + b0, s.pd + b0, dst + b0 * npix,
+                             s.tmp, last ? q.mask_out : nullptr, q.B, c->H, c->W, c->contact_scale, last ? 0 : 1, l == 0, cst, q.rows, grow, grow_x),
               "blur level");
       grow += (c->levels[l].kh - 1) / 2;
       grow_x += (c->levels[l].kw - 1) / 2;
@@ -888,70 +821,128 @@ static int pipeline_chunk(tacex_taxim_ctx* c, const float* hm, const float* pres
     }
   }
   if (dual) {  // the tail (and whatever the caller enqueues next) waits for the odd chunks
-    for (int q = 0; q < lvl_streams - 1; ++q) {
+    for (int q = 0; q < lp.streams - 1; ++q) {
       HIP_TRY(hipEventRecord(c->lvl_join[q], c->lvl_stream[q]), "hipEventRecord");
       HIP_TRY(hipStreamWaitEvent(st, c->lvl_join[q], 0), "hipStreamWaitEvent");
     }
   }
-  int band_grow = 0;  // rows by which the band levels spread the non-zero range of their output beyond the contact rows
-  for (int l = 0; l < n_band; ++l) band_grow += (c->levels[l].kh - 1) / 2;
-  if (stream_tail) {
-    // trailing small-kernel levels (+ restores), shading, observation and FOTS by-products: wave-autonomous streaming kernel
-    StageTimer t(c, st, c->n_levels + 2);
-    const bool want_obs = obs_h && obs;
-    const StreamPlan* plan = nullptr;
-    if (int rc = stream_plan(c, n_fused, B, want_obs ? obs_hh : 0, want_obs ? obs_w : 0, &plan)) return rc;
-    const size_t obs_scratch_floats = (size_t)B * (size_t)(c->H * obs_w > obs_hh * c->W ? c->H * obs_w : obs_hh * c->W) * 3;
-    const bool fuse_obs = want_obs && plan->obs_ready &&
-                          (size_t)B * plan->nstrips * plan->nseg * plan->obs_nrows * plan->obs_ncols * 3 <= obs_scratch_floats;
-    const bool pix = frame0 >= 0 && c->fots_pix_z && c->mk_x;
-    float* z_last = src == zbuf[0] ? zbuf[1] : zbuf[0];  // the level buffer the last band level did not write
-    const int n_items = B * plan->nstrips * plan->nseg;
-    HIP_TRY(run_stream_tail(c->levels, c->n_levels, n_fused, src, hm, c->gel_dev, sa, sb, pd, &c->shade, rgb, z_last, B, c->H, c->W,
-                            c->contact_scale, *plan, fuse_obs ? obs_h : nullptr, fots_part,
-                            (int)(tail_tiles_per_frame(c->H, c->W) * kTailWavesPerTile),
-                            pix ? c->fots_pix_z + (size_t)frame0 * c->fots_taps.n_markers : nullptr,
-                            pix ? c->fots_pix_m + (size_t)frame0 * c->fots_taps.n_markers : nullptr, st, rows, band_grow,
-                            n_items <= c->stream_order_cap ? c->stream_order : nullptr, order_done),
-            "taxim_stream_kernel");
-    if (fuse_obs) {
-      HIP_TRY(run_obs_finish_stream(obs_h, obs, obs_u8, *plan, B, st), "obs_finish_stream_kernel");
-    } else if (want_obs) {
-      if (int rc = resize_obs(c, rgb, obs_h, obs, obs_u8, obs_hh, obs_w, B, st)) return rc;
-    }
-    return 0;
+  *out = src;
+  return 0;
+}
+
+// trailing small-kernel levels (+ restores), shading, observation and FOTS by-products: wave-autonomous streaming kernel
+static int end_stream_tail(tacex_taxim_ctx* c, const Pass& p, const PassState& s, const float* src, bool order_done) {
+  StageTimer t(c, p.stream, c->n_levels + 2);
+  const bool want_obs = p.obs_scratch && p.obs;
+  const StreamPlan* plan = nullptr;
+  if (int rc = stream_plan(c, s.n_fused, p.B, want_obs ? p.oh : 0, want_obs ? p.ow : 0, &plan)) return rc;
+  const bool fuse_obs = want_obs && plan->obs_ready &&
+                        (size_t)p.B * plan->nstrips * plan->nseg * plan->obs_nrows * plan->obs_ncols * 3 <= obs_resize_floats(c->H, c->W, p.oh, p.ow, p.B);
+  const bool pix = p.frame0 >= 0 && c->fots_pix_z && c->mk_x;
+  float* z_last = src == s.z[0] ? s.z[1] : s.z[0];  // the level buffer the last band level did not write
+  const int n_items = p.B * plan->nstrips * plan->nseg;
+  HIP_TRY(run_stream_tail(c->levels, c->n_levels, s.n_fused, src, p.hm, c->gel_dev, s.sa, s.sb, s.pd, &c->shade, p.rgb, z_last, p.B, c->H, c->W,
+                          c->contact_scale, *plan, fuse_obs ? p.obs_scratch : nullptr, p.fots_part,
+                          (int)(tail_tiles_per_frame(c->H, c->W) * kTailWavesPerTile),
+                          pix ? c->fots_pix_z + (size_t)p.frame0 * c->fots_taps.n_markers : nullptr,
+                          pix ? c->fots_pix_m + (size_t)p.frame0 * c->fots_taps.n_markers : nullptr, p.stream, p.rows, s.band_grow,
+                          n_items <= c->stream_order_cap ? c->stream_order : nullptr, order_done),
+          "taxim_stream_kernel");
+  if (fuse_obs) HIP_TRY(run_obs_finish_stream(p.obs_scratch, p.obs, p.u8, *plan, p.B, p.stream), "obs_finish_stream_kernel");
+  else if (want_obs) return resize_obs(c, p);
+  return 0;
+}
+
+// trailing small-kernel levels (+ restores) and the shading in one LDS-tiled kernel
+static int end_tiled_tail(tacex_taxim_ctx* c, const Pass& p, const PassState& s, const float* src) {
+  StageTimer t(c, p.stream, c->n_levels + 2);
+  // fused observation: needs down-sampling factors >= 7.5 (y) / 8 (x) (cell-count bounds of the tile) and scratch room
+  bool fuse_obs = false;
+  int onry = 0, oncx = 0, oky = 0, okx = 0;
+  if (p.obs_scratch && p.obs && p.rgb) {
+    if (int rc = ensure_obs_tables(c, p.oh, p.ow)) return rc;
+    const int k0 = c->levels[c->n_levels - s.n_fused].kw;
+    fuse_obs = obs_fusable(c->obs_tab, c->H, c->W, s.n_fused, k0) && tail_obs_geom(s.n_fused, k0, &onry, &oncx, &oky, &okx) &&
+               obs_part_floats(c->H, c->W, p.B, onry, oncx) <= obs_resize_floats(c->H, c->W, p.oh, p.ow, p.B);
   }
-  if (n_fused > 0) {
-    // trailing small-kernel levels (+ restores) and the shading in one LDS-tiled kernel
-    StageTimer t(c, st, c->n_levels + 2);
-    // fused observation: needs down-sampling factors >= 7.5 (y) / 8 (x) (cell-count bounds of the tile) and scratch room
-    bool fuse_obs = false;
-    int onry = 0, oncx = 0, oky = 0, okx = 0;
-    if (obs_h && obs && rgb) {
-      if (int rc = ensure_obs_tables(c, obs_hh, obs_w)) return rc;
-      const int k0 = c->levels[c->n_levels - n_fused].kw;
-      fuse_obs = obs_fusable(c->obs_tab, c->H, c->W, n_fused, k0) && tail_obs_geom(n_fused, k0, &onry, &oncx, &oky, &okx) &&
-                 obs_part_floats(c->H, c->W, B, onry, oncx) <= (size_t)B * (size_t)(c->H * obs_w > obs_hh * c->W ? c->H * obs_w : obs_hh * c->W) * 3;
-    }
-    HIP_TRY(run_tail(c->levels, c->n_levels, n_fused, src, hm, c->gel_dev, sa, sb, pd, z_out, mask_out, &c->shade, rgb,
-                     fuse_obs ? obs_h : nullptr, fuse_obs ? &c->obs_tab : nullptr, fots_part,
-                     (frame0 >= 0 && c->fots_pix_z) ? &c->fots_taps : nullptr,
-                     (frame0 >= 0 && c->fots_pix_z) ? c->fots_pix_z + (size_t)frame0 * c->fots_taps.n_markers : nullptr,
-                     (frame0 >= 0 && c->fots_pix_m) ? c->fots_pix_m + (size_t)frame0 * c->fots_taps.n_markers : nullptr, B, c->H, c->W,
-                     c->contact_scale, st),
-            "taxim_tail_kernel");
-    if (fuse_obs) {
-      HIP_TRY(run_obs_finish(obs_h, obs, obs_u8, c->obs_tab, c->H, c->W, B, onry, oncx, st), "obs_finish_kernel");
-    } else if (obs && rgb) {  // no fusable geometry: plain two-pass down-sample of the finished frame (obs_h = scratch)
-      if (int rc = resize_obs(c, rgb, obs_h, obs, obs_u8, obs_hh, obs_w, B, st)) return rc;
-    }
-    return 0;
+  const bool pix = p.frame0 >= 0 && c->fots_pix_z;
+  HIP_TRY(run_tail(c->levels, c->n_levels, s.n_fused, src, p.hm, c->gel_dev, s.sa, s.sb, s.pd, p.z_out, p.mask_out, &c->shade, p.rgb,
+                   fuse_obs ? p.obs_scratch : nullptr, fuse_obs ? &c->obs_tab : nullptr, p.fots_part, pix ? &c->fots_taps : nullptr,
+                   pix ? c->fots_pix_z + (size_t)p.frame0 * c->fots_taps.n_markers : nullptr,
+                   (p.frame0 >= 0 && c->fots_pix_m) ? c->fots_pix_m + (size_t)p.frame0 * c->fots_taps.n_markers : nullptr, p.B, c->H, c->W,
+                   c->contact_scale, p.stream),
+          "taxim_tail_kernel");
+  if (fuse_obs) HIP_TRY(run_obs_finish(p.obs_scratch, p.obs, p.u8, c->obs_tab, c->H, c->W, p.B, onry, oncx, p.stream), "obs_finish_kernel");
+  else if (p.obs && p.rgb) return resize_obs(c, p);  // no fusable geometry: plain two-pass down-sample of the finished frame
+  return 0;
+}
+
+// no fused tail: the shading as a kernel of its own (nothing at all for a deform-only pass)
+static int end_shade(tacex_taxim_ctx* c, const Pass& p, const float* src) {
+  if (!p.rgb) return 0;
+  { StageTimer t(c, p.stream, c->n_levels + 1); HIP_TRY(run_shade(c->shade, src, p.rgb, nullptr, p.B, p.stream), "shade_kernel"); }
+  return p.obs ? resize_obs(c, p) : 0;
+}
+
+// One pass over p.B frames (pipeline_impl has left the per-frame minima in p.frame_min).
+static int pipeline_chunk(tacex_taxim_ctx* c, const Pass& p) {
+  const PassLayout L(c->H, c->W, p.B);
+  auto at = [&p](size_t off) { return reinterpret_cast<float*>(static_cast<char*>(p.ws) + off); };
+  PassState s{};
+  s.z[0] = at(L.z[0]); s.z[1] = at(L.z[1]); s.tmp = at(L.tmp);
+  if (p.flags & TACEX_FLAG_NO_SHIFT) {  // S = hm, P = -min(hm): zeros / negated minima need their own (B,) arrays
+    HIP_TRY(run_press_depth(p.frame_min, p.press, at(L.shift_a), at(L.shift_b), at(L.pdepth), p.B, 1, p.stream), "press_depth_kernel");
+    s.sa = at(L.shift_a); s.sb = at(L.shift_b); s.pd = at(L.pdepth);
+  } else {
+    // S = (hm - min) - press (TT:441) and P = -min(S) = -((min - min) - press) = press (TT:449): the per-frame scalars
+    // the kernels read ARE the frame-min and press arrays - no (B,)-sized helper launch (~5 us of a ~600 us step)
+    s.sa = p.frame_min; s.sb = p.press; s.pd = p.press;
   }
-  if (rgb) {
-    StageTimer t(c, st, c->n_levels + 1);
-    HIP_TRY(run_shade(c->shade, src, rgb, nullptr, B, st), "shade_kernel");
+  s.n_fused = c->use_tail ? c->n_fused : 0; s.n_band = c->n_levels - s.n_fused;
+  s.stream_tail = s.n_fused > 0 && c->use_stream && p.rgb && !p.z_out && !p.mask_out &&
+                  stream_supported(s.n_fused, c->levels[c->n_levels - s.n_fused].kw, c->H, c->W);
+  for (int l = 0; l < s.n_band; ++l) s.band_grow += (c->levels[l].kh - 1) / 2;
+  const float* src = nullptr; bool order_done = false;
+  if (int rc = run_band_levels(c, p, s, plan_band_levels(c, p, s), &src, &order_done)) return rc;
+  if (s.stream_tail) return end_stream_tail(c, p, s, src, order_done);
+  if (s.n_fused > 0) return end_tiled_tail(c, p, s, src);
+  return end_shade(c, p, src);
+}
+
+static int pipeline_impl(tacex_taxim_ctx* c, Pass p) {
+  const int cf = chunk_frames(c, p.B);
+  // A deferred depth -> height map pass (tacex_taxim_defer_height_map_from_depth) that produces exactly this call's inputs runs inside
+  // the pass, chunk by chunk (run_band_levels); one that does not is run in full first - it was promised no later than this call.
+  if (c->depth_pass.armed) {
+    c->depth_pass.armed = false;
+    const tacex_taxim_ctx::DepthPass& d = c->depth_pass;
+    const bool fits = d.B == p.B && d.hm == p.hm && d.fmin == p.frame_min && d.indent == p.press && p.press &&
+                      (p.flags & TACEX_FLAG_HAVE_FRAME_MIN) && !(p.flags & TACEX_FLAG_NO_SHIFT) &&
+                      (!(p.flags & TACEX_FLAG_HAVE_FRAME_ROWS) || d.rows == c->frame_rows);
+    if (fits) { p.depth = d; p.depth.armed = true; }
+    else if (int rc = run_depth_pass(d, c->H, c->W, p.stream)) return rc;
   }
-  if (obs && rgb) return resize_obs(c, rgb, obs_h, obs, obs_u8, obs_hh, obs_w, B, st);
+  if (c->fots_part && p.B <= c->fots_cap) p.fots_part = c->fots_part;
+  p.frame0 = p.B <= c->fots_pix_cap ? 0 : -1;
+  // Contact row ranges (zero-band skipping of the band levels, TACEX_BAND_SKIP=0 disables): from the caller's buffer when the
+  // minimum came with them, else from the library's own minimum pass (PassLayout::rows of the whole batch)
+  static const bool band_skip = !(getenv("TACEX_BAND_SKIP") && atoi(getenv("TACEX_BAND_SKIP")) == 0);
+  const bool can_rows = band_skip && p.press && !(p.flags & TACEX_FLAG_NO_SHIFT) && frame_rows_supported(c->H, c->W);
+  if (p.flags & TACEX_FLAG_HAVE_FRAME_MIN) {
+    if (can_rows && (p.flags & TACEX_FLAG_HAVE_FRAME_ROWS) && c->frame_rows && p.B <= c->frame_rows_cap) p.rows = c->frame_rows;
+  } else {  // one reduction pass over the whole shard
+    StageTimer t(c, p.stream, 0);
+    if (can_rows) {
+      int* wr = reinterpret_cast<int*>(static_cast<char*>(p.ws) + PassLayout(c->H, c->W, p.B).rows);
+      HIP_TRY(run_frame_rows(p.hm, false, nullptr, p.frame_min, nullptr, nullptr, p.press, wr, p.B, c->H, c->W, 0.f, 0.f, 0.f, 0.f, 0.f, p.stream), "frame_rows_kernel");
+      p.rows = wr;
+    } else {
+      HIP_TRY(run_frame_min(p.hm, false, nullptr, p.frame_min, nullptr, nullptr, p.B, c->H * c->W, 0.f, 0.f, 0.f, 0.f, 0.f, p.stream), "frame_min_kernel");
+    }
+    p.flags |= TACEX_FLAG_HAVE_FRAME_MIN;
+  }
+  for (int b0 = 0; b0 < p.B; b0 += cf)
+    if (int rc = pipeline_chunk(c, p.slice(b0, p.B - b0 < cf ? p.B - b0 : cf))) return rc;
   return 0;
 }
 
@@ -960,7 +951,9 @@ int tacex_taxim_deform(tacex_taxim_ctx* c, const float* hm, const float* press, 
   if (!c || !hm || !frame_min || !z_out || !ws) { set_error("tacex_taxim_deform: null argument"); return 2; }
   if (!press && !(flags & TACEX_FLAG_NO_SHIFT)) { set_error("tacex_taxim_deform: press_dev is null"); return 2; }
   if (B <= 0) return 0;
-  return pipeline_impl(c, hm, press, frame_min, nullptr, z_out, mask_out, ws, B, flags, (hipStream_t)stream);
+  Pass p = make_pass(c, hm, press, frame_min, ws, B, flags, stream);
+  p.z_out = z_out; p.mask_out = mask_out;
+  return pipeline_impl(c, p);
 }
 
 int tacex_taxim_shade(tacex_taxim_ctx* c, const float* z, float* rgb, uint8_t* idx_out, int B, void* stream) {
@@ -976,23 +969,22 @@ int tacex_taxim_render(tacex_taxim_ctx* c, const float* hm, const float* press, 
   if (!c || !hm || !frame_min || !rgb || !ws) { set_error("tacex_taxim_render: null argument"); return 2; }
   if (!press && !(flags & TACEX_FLAG_NO_SHIFT)) { set_error("tacex_taxim_render: press_dev is null"); return 2; }
   if (B <= 0) return 0;
+  Pass p = make_pass(c, hm, press, frame_min, ws, B, flags, stream);
   if (flags & TACEX_FLAG_WITH_SHADOW) {
     if (!c->shadow.ready) { set_error("tacex_taxim_render: TACEX_FLAG_WITH_SHADOW needs tacex_taxim_set_shadow first"); return 2; }
-    const size_t img = align_up((size_t)B * c->H * c->W * sizeof(float), 256);
-    char* sw = static_cast<char*>(ws) + tacex_taxim_workspace_bytes(c, B);
-    float* zb = z_out ? z_out : reinterpret_cast<float*>(sw);
-    uint8_t* mb = mask_out ? mask_out : reinterpret_cast<uint8_t*>(sw + img);
-    float* gdir = reinterpret_cast<float*>(sw + 2 * img);
-    float* raw = reinterpret_cast<float*>(sw + 3 * img);
-    float* shd = reinterpret_cast<float*>(sw + 6 * img);
-    float* tmp = reinterpret_cast<float*>(sw + 9 * img);
-    int rc = pipeline_impl(c, hm, press, frame_min, nullptr, zb, mb, ws, B, flags, (hipStream_t)stream);
-    if (rc) return rc;
+    const ShadowLayout S(c->H, c->W, B);
+    char* sw = static_cast<char*>(ws) + PassLayout(c->H, c->W, B).total;
+    auto at = [sw](size_t off) { return reinterpret_cast<float*>(sw + off); };
+    p.z_out = z_out ? z_out : at(S.z);
+    p.mask_out = mask_out ? mask_out : reinterpret_cast<uint8_t*>(sw + S.mask);
+    if (int rc = pipeline_impl(c, p)) return rc;
     StageTimer t(c, (hipStream_t)stream, c->n_levels + 1);
-    HIP_TRY(run_shadow(c->shadow, c->shade, zb, mb, c->gel_dev, rgb, raw, shd, gdir, tmp, B, (hipStream_t)stream), "shadow branch");
+    HIP_TRY(run_shadow(c->shadow, c->shade, p.z_out, p.mask_out, c->gel_dev, rgb, at(S.raw), at(S.shadow), at(S.gdir), at(S.tmp), B, (hipStream_t)stream),
+            "shadow branch");
     return 0;
   }
-  return pipeline_impl(c, hm, press, frame_min, rgb, z_out, mask_out, ws, B, flags, (hipStream_t)stream);
+  p.rgb = rgb; p.z_out = z_out; p.mask_out = mask_out;
+  return pipeline_impl(c, p);
 }
 
 int tacex_taxim_set_frame_rows(tacex_taxim_ctx* c, const int32_t* frame_rows, int capacity_frames) {
@@ -1066,12 +1058,14 @@ int tacex_taxim_render_obs(tacex_taxim_ctx* c, const float* hm, const float* pre
   if (obs_h <= 0 || obs_w <= 0 || obs_h > c->H || obs_w > c->W) { set_error("tacex_taxim_render_obs: bad observation size %dx%d", obs_w, obs_h); return 2; }
   if (!press && !(flags & TACEX_FLAG_NO_SHIFT)) { set_error("tacex_taxim_render_obs: press_dev is null"); return 2; }
   if (B <= 0) return 0;
+  Pass p = make_pass(c, hm, press, frame_min, ws, B, flags, stream);
+  p.rgb = rgb; p.z_out = z_out; p.mask_out = mask_out;
+  p.obs = obs_out; p.obs_scratch = obs_scratch; p.oh = obs_h; p.ow = obs_w; p.u8 = (flags & TACEX_FLAG_OBS_U8) != 0;
   if (flags & TACEX_FLAG_WITH_SHADOW) {  // the shadow branch re-blurs the finished frame: its observation is a plain two-pass resize
     if (int rc = tacex_taxim_render(c, hm, press, frame_min, rgb, z_out, mask_out, ws, B, flags & ~TACEX_FLAG_OBS_U8, stream)) return rc;
-    return resize_obs(c, rgb, obs_scratch, obs_out, (flags & TACEX_FLAG_OBS_U8) != 0, obs_h, obs_w, B, (hipStream_t)stream);
+    return resize_obs(c, p);
   }
-  return pipeline_impl(c, hm, press, frame_min, rgb, z_out, mask_out, ws, B, flags, (hipStream_t)stream, obs_scratch, obs_out,
-                       obs_h, obs_w);
+  return pipeline_impl(c, p);
 }
 
 /* test / ablation hook: 0 = run every level as its own kernel + separate shade, 1 = fused tail (default) */

@@ -1268,9 +1268,10 @@ int stream_segments(int B, int nstrips, int H, int warm, int per_simd) {
 // waves per SIMD the fused kernel of this level set is compiled for (sizes the segment count: a launch should bring a whole
 // number of resident rounds)
 int stream_waves_per_simd(int n_fused, int k0) { return stream_variant(n_fused, k0) == 2 ? TACEX_STREAM3_WAVES : 2; }
+// summed radii of a variant's levels (StreamCfg::sum_r of its instantiation: 9,5,3,5 / 9,5,9 / 5,3,5)
+static int variant_sum_r(int v) { return v == 0 ? 9 : (v == 1 ? 10 : 5); }
 int stream_warm_rows(int n_fused, int k0, bool levels_kernel) {
-  const int v = stream_variant(n_fused, k0);
-  const int sum_r = v == 0 ? 9 : (v == 1 ? 10 : 5);
+  const int sum_r = variant_sum_r(stream_variant(n_fused, k0));
   if (!stream_split()) return 2 * sum_r + 2;
   return levels_kernel ? 2 * sum_r : 2;
 }
@@ -1317,6 +1318,14 @@ static bool stream_sorted() {
   return sorted != 0;
 }
 
+// heaviest items first (see the kernel's "work distribution" note): the order of the B * nstrips * nseg items of a fused launch
+static hipError_t launch_stream_order(int v, const int* rows_ext, int ext_grow, int B, int nstrips, int nseg, int seg_rows, int H, int* order_buf,
+                                      hipStream_t st) {
+  hipLaunchKernelGGL(stream_order_kernel, dim3(1), dim3(1024), 0, st, rows_ext, B * nstrips * nseg, nstrips * nseg, nseg, seg_rows, H,
+                     ext_grow + variant_sum_r(v) + 1, order_buf);
+  return hipGetLastError();
+}
+
 // The item order of a fused streaming-tail launch, as a launch of its own: it depends on the contact rows alone, so the pipeline issues it
 // beside the band levels (as soon as the last depth pass has left the rows) instead of between the levels' join and the tail.
 // Returns hipSuccess and sets *launched when the order buffer will hold the launch's order.
@@ -1324,12 +1333,8 @@ hipError_t run_stream_order(const LevelDesc* lv, int n_levels, int n_fused, cons
                             int* order_buf, hipStream_t st, bool* launched) {
   *launched = false;
   if (stream_split() || !stream_sorted() || !order_buf || !lv[0].gel_zero || !rows_ext) return hipSuccess;
-  const int v = stream_variant(n_fused, lv[n_levels - n_fused].kw);
-  const int n_items = B * plan.nstrips * plan.nseg;
-  const int sum_r = v == 0 ? 9 : (v == 1 ? 10 : 5);
-  hipLaunchKernelGGL(stream_order_kernel, dim3(1), dim3(1024), 0, st, rows_ext, n_items, plan.nstrips * plan.nseg, plan.nseg, plan.seg_rows, H,
-                     ext_grow + sum_r + 1, order_buf);
-  const hipError_t e = hipGetLastError();
+  const hipError_t e = launch_stream_order(stream_variant(n_fused, lv[n_levels - n_fused].kw), rows_ext, ext_grow, B, plan.nstrips, plan.nseg,
+                                           plan.seg_rows, H, order_buf, st);
   *launched = e == hipSuccess;
   return e;
 }
@@ -1377,13 +1382,8 @@ hipError_t run_stream_tail(const LevelDesc* lv, int n_levels, int n_fused, const
   if (!stream_split()) {
     if (order_done) {
       sh.order = order_buf;  // (run_stream_order has been issued for this launch)
-    } else if (sorted && order_buf && gz && rows_ext) {  // heaviest items first (see the kernel's "work distribution" note)
-      const int n_items = B * sh.nstrips * sh.nseg;
-      const int sum_r = v == 0 ? 9 : (v == 1 ? 10 : 5);
-      hipLaunchKernelGGL(stream_order_kernel, dim3(1), dim3(1024), 0, st, rows_ext, n_items, sh.nstrips * sh.nseg, sh.nseg, sh.seg_rows, H,
-                         ext_grow + sum_r + 1, order_buf);
-      hipError_t e = hipGetLastError();
-      if (e != hipSuccess) return e;
+    } else if (sorted && order_buf && gz && rows_ext) {
+      if (hipError_t e = launch_stream_order(v, rows_ext, ext_grow, B, sh.nstrips, sh.nseg, sh.seg_rows, H, order_buf, st); e != hipSuccess) return e;
       sh.order = order_buf;
     }
     if (v == 0) return launch_stream<kStreamFused, 9, 5, 3, 5>(sh, gz, st);

@@ -271,6 +271,15 @@ def test_fused_tail_matches_unfused_levels(taxim, shape):
     same = (idf == idu).all(-1)
     assert same.float().mean().item() > 0.995
     assert ((rf - ru).abs()[same]).max().item() <= 2e-6
+    # the workspace sizes the C API reports, worked out here: three images and three (B,) vectors, each 256-byte aligned, and the (B, 4)
+    # int32 contact rows; the shadow branch's twelve images behind them
+    from tacex_amd import _lib
+
+    lib, handle = _lib.load_library(), taxim.context(shape).handle
+    for B in (1, 65):
+        img, vec, rows = (-(-n // 256) * 256 for n in (B * H * W * 4, B * 4, B * 16))
+        assert lib.tacex_taxim_workspace_bytes(handle, B) == 3 * img + 3 * vec + rows
+        assert lib.tacex_taxim_shadow_workspace_bytes(handle, B) == 12 * img
 
 
 def test_policy_observation_downsample_matches_torch(taxim):
