@@ -70,13 +70,13 @@ def box_tet_mesh(nx=6, ny=8, nz=3, size=(0.02075, 0.02525, 0.0045)):
     return P, np.array(tets, dtype=np.int32)
 
 
-# Backtracking beyond the configured cap (mirrors kLsRescue of csrc/fem_kernels.hip): when the capped line search finds no decrease
+# Backtracking beyond the configured cap (mirrors kLsRescue of csrc/fem_newton_lds.h): when the capped line search finds no decrease
 # the step is halved further, down to 2^-32, instead of leaving the env stuck - a Newton direction computed before a vertex enters
 # the barrier zone knows nothing of the barrier it runs into.
 LS_RESCUE = 32
 
 
-# Safeguard of the coarse correction (kCoarseTrust of csrc/fem_kernels.hip): the PCG's stopping test is in the M^-1 norm, and M^-1
+# Safeguard of the coarse correction (kCoarseTrust of csrc/fem_newton_lds.h): the PCG's stopping test is in the M^-1 norm, and M^-1
 # contains the REST-state coarse operator - blind to the barrier / friction stiffness of the current contacts.  Where the coarse
 # space holds nearly free modes (simple_axle held at its ends) the test passes with the residual's 2-norm above that of b; if it is
 # above COARSE_TRUST |b| at exit (no reduction at all), the coarse part is dropped for the rest of the time step and the iteration's solve starts over.

@@ -90,6 +90,10 @@ def _mllvm_supported(hipcc: str, flags: list, objdir: Path) -> bool:
 
 
 def _build_locked(dig: str, verbose: bool) -> Path:
+    srcs = [CSRC / s for s in SOURCES]
+    missing = [s.name for s in srcs if not s.exists()]
+    if missing:  # (a library linked without one of its units only fails later, on a missing symbol)
+        raise RuntimeError(f"missing HIP source(s) under {CSRC}: {', '.join(missing)}")
     hipcc = _hipcc()
     objdir = PKG / (f"build.{_TAG}" if _TAG else "build")
     objdir.mkdir(exist_ok=True)
@@ -100,7 +104,6 @@ def _build_locked(dig: str, verbose: bool) -> Path:
         file_flags["taxim_stream.hip"] = [f for f in file_flags["taxim_stream.hip"] if f not in sched]
         if verbose:
             print(f"hipcc does not know {' '.join(sched)}: building taxim_stream.hip without it")
-    srcs = [CSRC / s for s in SOURCES if (CSRC / s).exists()]
     procs = []
     for s in srcs:
         obj = objdir / (s.stem + ".o")

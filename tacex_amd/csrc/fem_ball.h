@@ -1,4 +1,4 @@
-// The reference's own UIPC scene on the GPU (second slice; included by fem_kernels.hip inside namespace tacex):
+// The reference's own UIPC scene on the GPU (second slice):
 // the gelpad (Stable Neo-Hookean tets, soft position constraints) + ONE FREE AFFINE-BODY BALL per env + the ground half-space, in IPC
 // contact through point-triangle pairs in both directions and edge-edge pairs.  Reference call sites: ball_rolling_uipc.py:71-92 (ground_height 0.001,
 // d_hat 5e-4, the ball as AffineBodyConstitutionCfg), uipc_object.py:62-74,456-466 (m_kappa 100 MPa, kinematic = False),
@@ -25,6 +25,11 @@
 // the step bound.  Pair candidates are rebuilt once per Newton iteration at reach 2.8 d_hat, which no pair
 // outside can cross into d_hat within one bounded step, so the line search's energies are exact.  (The CU-resident kernel of the
 // prescribed-indenter scenes keeps ALL per-vertex state in registers and is at its register limit: this scene got a kernel of its own.)
+
+#pragma once
+#include "fem_device.h"
+
+namespace tacex {
 
 struct BallDev {
   int nv = 0, nt = 0, npt = 0, nsv = 0;
@@ -421,37 +426,8 @@ __global__ __launch_bounds__(NT_, NT_ >= 512 ? TACEX_BALL_WG_PER_CU : 1) void fe
 #define PCG_TICK0() do { } while (0)
 #define PCG_TICK(k) do { } while (0)
 #endif
-  auto chain_solve = [&](int ch) {  // block-tridiagonal L D L^T solve along one vertex chain, in place in rsl (factors cf in LDS)
-    int v = m.ch_next ? m.ch_head[ch] : ch, last = v;
-    double y[3] = {rsl[v * 3], rsl[v * 3 + 1], rsl[v * 3 + 2]};
-    while (true) {
-      last = v;
-      const int n = cnx[v] == 0xffff ? -1 : (int)cnx[v];
-      if (n < 0) break;
-      const float* g = cf + v * 15 + 6;
-      const double y0 = y[0], y1 = y[1], y2 = y[2];
-#pragma unroll
-      for (int k = 0; k < 3; ++k) y[k] = rsl[n * 3 + k] - ((double)g[k] * y0 + (double)g[3 + k] * y1 + (double)g[6 + k] * y2);
-      rsl[n * 3] = y[0]; rsl[n * 3 + 1] = y[1]; rsl[n * 3 + 2] = y[2];
-      v = n;
-    }
-    v = last;
-    double zn[3] = {0, 0, 0};
-    while (true) {
-      const float* f = cf + v * 15;
-      const double y0 = rsl[v * 3], y1 = rsl[v * 3 + 1], y2 = rsl[v * 3 + 2];
-      double zz[3];
-      zz[0] = (double)f[0] * y0 + (double)f[1] * y1 + (double)f[2] * y2;
-      zz[1] = (double)f[1] * y0 + (double)f[3] * y1 + (double)f[4] * y2;
-      zz[2] = (double)f[2] * y0 + (double)f[4] * y1 + (double)f[5] * y2;
-#pragma unroll
-      for (int i = 0; i < 3; ++i) zz[i] -= (double)f[6 + i * 3] * zn[0] + (double)f[7 + i * 3] * zn[1] + (double)f[8 + i * 3] * zn[2];
-      rsl[v * 3] = zz[0]; rsl[v * 3 + 1] = zz[1]; rsl[v * 3 + 2] = zz[2];
-      zn[0] = zz[0]; zn[1] = zz[1]; zn[2] = zz[2];
-      const int pv = cpr[v] == 0xffff ? -1 : (int)cpr[v];
-      if (pv < 0) break;
-      v = pv;
-    }
+  auto solve_chain = [&](int ch) {  // block-tridiagonal L D L^T solve along one vertex chain, in place in rsl (factors cf in LDS)
+    chain_solve<true>(m.ch_next ? m.ch_head[ch] : ch, rsl, rsl, cf, cnx, cpr);
   };
   // z = M^-1 r (r in rL, z in rsl | zq); returns r . z.  Phases: (A) copy + restriction r_c = P^T r; (B) coarse solve on waves 0-5 WHILE waves 6-7
   // solve the chains; (C) the coarse solve's two halves; (D) prolongation + r . z.
@@ -462,20 +438,7 @@ __global__ __launch_bounds__(NT_, NT_ >= 512 ? TACEX_BALL_WG_PER_CU : 1) void fe
     for (int k = tid; k < 3 * V; k += NT) rsl[k] = rL[k];
     if (coarse) {  // restriction, node by node over the node's vertex list (G lanes per node, as coarse_correct(); the first cut added 12 000 LDS
                    // atomics onto 180 addresses per application)
-      int G = 1;
-      while (2 * G <= NT / m.nc && 2 * G <= 64) G *= 2;
-      const int node = tid / G, jn = tid - node * G;
-      double a0 = 0.0, a1 = 0.0, a2 = 0.0;
-      if (node < m.nc) {
-        const int e1 = m.cn_off[node + 1];
-        for (int e = m.cn_off[node] + jn; e < e1; e += G) {
-          const int v0 = m.cn_vtx[e];
-          const double w0 = m.cn_w[e];
-          a0 += w0 * rL[v0 * 3]; a1 += w0 * rL[v0 * 3 + 1]; a2 += w0 * rL[v0 * 3 + 2];
-        }
-      }
-      for (int o2 = G >> 1; o2 > 0; o2 >>= 1) { a0 += __shfl_xor(a0, o2, 64); a1 += __shfl_xor(a1, o2, 64); a2 += __shfl_xor(a2, o2, 64); }
-      if (node < m.nc && jn == 0) { crc[node * 3] = a0; crc[node * 3 + 1] = a1; crc[node * 3 + 2] = a2; }
+      restrict_to_coarse<false>(m, rL, crc, coarse_lanes_per_node(NT, m.nc), tid);
     }
     __syncthreads();
     PCG_TICK(3);
@@ -512,14 +475,14 @@ __global__ __launch_bounds__(NT_, NT_ >= 512 ? TACEX_BALL_WG_PER_CU : 1) void fe
           cpart[jp * 3 * kFemMaxCoarse + r] = (s0 + s1) + (s2 + s3);
         }
       } else {  // ... while the last two waves solve the chains
-        for (int ch = tid - MW * 64; ch < nch; ch += NT - MW * 64) chain_solve(ch);
+        for (int ch = tid - MW * 64; ch < nch; ch += NT - MW * 64) solve_chain(ch);
       }
       __syncthreads();
       for (int k = tid; k < nc3; k += NT) cyc[k] = cpart[k] + (HALVES > 1 ? cpart[3 * kFemMaxCoarse + k] : 0.0);
       __syncthreads();
       for (int k = tid; k < nc3; k += NT) part += crc[k] * cyc[k];
     } else {
-      for (int ch = tid; ch < nch; ch += NT) chain_solve(ch);
+      for (int ch = tid; ch < nch; ch += NT) solve_chain(ch);
       __syncthreads();
     }
     PCG_TICK(4);
@@ -1075,46 +1038,17 @@ __global__ __launch_bounds__(NT_, NT_ >= 512 ? TACEX_BALL_WG_PER_CU : 1) void fe
     // block part of the pad's preconditioner: block-tridiagonal LDL^T along the vertex chains of tacex_fem_set_chains (the columns of
     // vertices through the pad's thickness; a chain of one vertex = 3 x 3 block Jacobi) - S_0 = D_0, G_i = S_i^-1 E_i,
     // S_{i+1} = D_{i+1} - E_i^T G_i, the thread of a chain walks it (fem_newton_lds_kernel does the same); S^-1 | G as floats in LDS
-    for (int ch = tid; ch < nch; ch += NT) {
-      int v = m.ch_next ? m.ch_head[ch] : ch;
-      double S[9];
+    for (int ch = tid; ch < nch; ch += NT)
+      chain_factor(m.ch_next ? m.ch_head[ch] : ch,
+                   [&](int v, double (&Dv)[9]) __attribute__((always_inline)) {
 #pragma unroll
-      for (int k = 0; k < 9; ++k) S[k] = Dinv[(size_t)v * 9 + k];
-      while (true) {
-        double Si[9];
-        if (!inv3_spd(S, Si)) {
-          const double dm = fmax(S[0], fmax(S[4], S[8]));
-          const double im = 1.0 / (dm > 0.0 ? dm : 1.0);
-          Si[0] = im; Si[1] = 0; Si[2] = 0; Si[3] = 0; Si[4] = im; Si[5] = 0; Si[6] = 0; Si[7] = 0; Si[8] = im;
-        }
-        float* f = cf + v * 15;
-        f[0] = (float)Si[0]; f[1] = (float)Si[1]; f[2] = (float)Si[2]; f[3] = (float)Si[4]; f[4] = (float)Si[5]; f[5] = (float)Si[8];
-        const int n = cnx[v] == 0xffff ? -1 : (int)cnx[v];
-        if (n < 0 || !blk) {
-#pragma unroll
-          for (int k = 0; k < 9; ++k) f[6 + k] = 0.0f;
-          if (n < 0) break;
-#pragma unroll
-          for (int k = 0; k < 9; ++k) S[k] = Dinv[(size_t)n * 9 + k];
-          v = n;
-          continue;
-        }
-        const double* Ev = blk + (size_t)v * 16 + 6;
-        double G[9];
-#pragma unroll
-        for (int i = 0; i < 3; ++i)
-#pragma unroll
-          for (int k = 0; k < 3; ++k) G[i * 3 + k] = Si[i * 3 + 0] * Ev[k] + Si[i * 3 + 1] * Ev[3 + k] + Si[i * 3 + 2] * Ev[6 + k];
-#pragma unroll
-        for (int k = 0; k < 9; ++k) f[6 + k] = (float)G[k];
-#pragma unroll
-        for (int i = 0; i < 3; ++i)
-#pragma unroll
-          for (int k = 0; k < 3; ++k)
-            S[i * 3 + k] = Dinv[(size_t)n * 9 + i * 3 + k] - (Ev[i] * G[k] + Ev[3 + i] * G[3 + k] + Ev[6 + i] * G[6 + k]);
-        v = n;
-      }
-    }
+                     for (int k = 0; k < 9; ++k) Dv[k] = Dinv[(size_t)v * 9 + k];
+                   },
+                   [&](int v, const double*& Ev) __attribute__((always_inline)) {  // (no blk table: every vertex a chain of its own)
+                     if (!blk) return false;
+                     Ev = blk + (size_t)v * 16 + 6;
+                     return true;
+                   }, cf, cnx);
     __syncthreads();  // (the chains have read their blocks: r may take over the tail of their slot)
     for (int k = tid; k < 3 * VN; k += NT) { rL[k] = (bd.kinematic && k >= 3 * V) ? 0.0 : -vg[k]; dL[k] = 0.0; }  // (a fixed body: zero residual rows stay zero through the PCG)
     __syncthreads();
@@ -1150,12 +1084,12 @@ __global__ __launch_bounds__(NT_, NT_ >= 512 ? TACEX_BALL_WG_PER_CU : 1) void fe
         deformation_gradient(ps, v, Di, dF);
         apply_dP(m, s, dF, dP);
         shape_rows(Di, r);
-        const double sc = dt2 * m.vol[t];
+        double rows[12];
+        element_hp_rows(dP, r, dt2 * m.vol[t], rows);
 #pragma unroll
         for (int w4 = 0; w4 < 4; ++w4)
 #pragma unroll
-          for (int i = 0; i < 3; ++i)
-            atomicAdd(&acc[v[w4] * 3 + i], sc * (dP[i * 3 + 0] * r[w4 * 3 + 0] + dP[i * 3 + 1] * r[w4 * 3 + 1] + dP[i * 3 + 2] * r[w4 * 3 + 2]));
+          for (int i = 0; i < 3; ++i) atomicAdd(&acc[v[w4] * 3 + i], rows[w4 * 3 + i]);
       }
       __syncthreads();
       PCG_TICK(0);
@@ -1431,3 +1365,5 @@ __global__ __launch_bounds__(256) void fem_ball_velocity_kernel(const double* __
   const int k = blockIdx.x * blockDim.x + threadIdx.x;
   if (k < B * 12) qv[k] = (q[k] - qprev[k]) * inv_dt;
 }
+
+}  // namespace tacex

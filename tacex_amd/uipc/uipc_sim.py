@@ -771,7 +771,7 @@ class UipcSim:
         Newton iteration started - the caller moved the indenter by more than the gap between two steps (`set_contact_indenters`
         documents the contract) and that vertex gets no restoring force; flag 2 = a line search found no decrease.  Informational:
         4 = the env dropped the coarse correction for the rest of the step, 8 = it met negative curvature and finished the step with
-        the PSD-safe Hessian (csrc/fem_kernels.hip, kFemFlagCoarseOff / kFemFlagPsdSafe); 32 = its kind-4 row named a mesh id outside
+        the PSD-safe Hessian (csrc/fem_device.h, kFemFlagCoarseOff / kFemFlagPsdSafe); 32 = its kind-4 row named a mesh id outside
         the library (`set_indenter_meshes`): the env ran the step without an indenter ("bad_mesh_id_envs"); 64 = its material id lay
         outside the material library (`set_materials`): the env stepped with material 0 ("bad_material_id_envs")."""
         self.wait_for_step()  # a step enqueued on a side stream (FemGelpad(side_stream=True)): `.cpu()` only drains the CURRENT stream

@@ -511,7 +511,7 @@ def test_edge_snap_lowers_the_energy_and_lands_at_the_balance_depth():
 
 
 def test_psd_safe_hessian_is_positive_semidefinite_where_the_exact_one_is_not(meshes):
-    """PSD-safe mode (kFemFlagPsdSafe of csrc/fem_kernels.hip, `FemModel.psd_safe`): with |c_J| clamped to a / sqrt(2 Ic) per element the
+    """PSD-safe mode (kFemFlagPsdSafe of csrc/fem_device.h, `FemModel.psd_safe`): with |c_J| clamped to a / sqrt(2 Ic) per element the
     9x9 F-space Hessian a I + b f f^T + lam c c^T + c_J d2J/dF2 is PSD for ANY deformation gradient - also strongly compressed and
     inverted ones, where the exact Hessian has negative eigenvalues - and the bound it rests on holds: the spectral norm of d2J/dF2
     is below sqrt(2 Ic).  Hessian-vector products in that mode are those of the clamped element matrices."""

@@ -3,6 +3,7 @@ CPU by a stand-alone C++ program, tests/fem_layout_check.cpp: every offset and t
 before the layouts had a header of their own, region order, overlap, the end of the last region and alignment, for
 V in {4, 495, 2232} x T in {1, 1920} x B in {1, 2, 3, 512} (the odd B: the int32 env order rounded up to doubles) and, for the ball
 scene, (nv, nt) in {(4, 4), (42, 80)}.  The header is plain C++17: a host compiler builds it without HIP."""
+import re
 import shutil
 import subprocess
 
@@ -40,3 +41,13 @@ def test_no_workspace_arithmetic_outside_the_layout_header():
     host = src[src.index("struct tacex_fem_ctx"):]
     assert "newton_ws_doubles(" not in host and "ball_ws_doubles(" not in host
     assert "dev_nwt" not in src
+    # the kernel headers the translation unit includes (fem_ball.h is older than the split and indexes its env block in its kernel): one
+    # of them also holds host code - the LDS sizes of the CU-resident kernel - and that one stays clear of the block sizes as well
+    csrc = REPO / "tacex_amd" / "csrc"
+    headers = [h for h in re.findall(r'^#include "(fem_\w+\.h)"', src, flags=re.M) if h not in ("fem_layout.h", "fem_ball.h")]
+    assert len(headers) >= 6, headers
+    with_host_code = [h for h in headers if re.search(r"^(static|inline)\s|__host__", (csrc / h).read_text(), flags=re.M)]
+    assert "fem_newton_lds.h" in with_host_code, with_host_code
+    for h in with_host_code:
+        code = re.sub(r"//[^\n]*", "", (csrc / h).read_text())  # (comments may name the functions)
+        assert "newton_ws_doubles(" not in code and "ball_ws_doubles(" not in code, h

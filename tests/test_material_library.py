@@ -39,7 +39,7 @@ def test_header_binding_and_flag_agree_on_the_material_library():
     for name in ("tacex_fem_set_material_library", "tacex_fem_set_material_ids", "tacex_fem_set_material_coarse_inverses"):
         assert re.search(rf"\bint\s+{name}\s*\(", hdr), name
         assert hasattr(lib, name) and name not in _lib.MISSING_SYMBOLS
-    src = (REPO / "tacex_amd" / "csrc" / "fem_kernels.hip").read_text()
+    src = (REPO / "tacex_amd" / "csrc" / "fem_device.h").read_text()
     assert re.search(r"kFemFlagBadMaterial\s*=\s*64\b", src) and "flag 64" in hdr  # the next free bit after the mesh library's 32
 
 
