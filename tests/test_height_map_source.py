@@ -43,6 +43,56 @@ def test_oracle_matches_the_synthetic_generator():
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("shape", [(30, 40), (24, 32), (250, 320), (9, 4), (1100, 12)], ids=lambda s: f"{s[0]}x{s[1]}")
+def test_indenter_kernel_off_the_tuned_size(shape):
+    """`tacex_height_map_from_indenters` through the C ABI: every indenter kind, frames of less than one pass of the block (24x32, 30x40,
+    9x4: one float4 per row) and of several passes in which the incremental (x, y) wraps (250x320: 256 columns and 12 rows per pass;
+    1100x12: 4 columns and 341 rows).  The frame minimum is the minimum of the map the kernel wrote, the indentation the reference's
+    formula on that minimum - both exactly."""
+    from oracle.indenter_oracle import indenter_height_map, indentation_depth
+    from tacex_amd import _lib
+    from tacex_amd.utils.synthetic import PIXMM
+
+    lib = _lib.load_library()
+    H, W = shape
+    B = 7
+    desc = _desc_like_synthetic(B, H, W, 31 + H)
+    desc[:, 0] = torch.tensor([0.0, 1.0, 2.0, 3.0, -1.0, 2.0, 3.0])  # all five kinds
+    desc[5, 5] = 6.0  # pressed past the sensor case: the minimum lies below 24 mm and the indentation clamps to the pad height
+    want = indenter_height_map(desc.numpy(), H, W, PIXMM)
+    d = desc.cuda()
+    hm = torch.full(((B + 1) * H * W,), -7.0, device="cuda")  # one more frame than the call owns
+    fmin, ind = torch.full((B + 1,), -7.0, device="cuda"), torch.full((B + 1,), -7.0, device="cuda")
+    st = torch.cuda.current_stream().cuda_stream
+    _lib.check(lib.tacex_height_map_from_indenters(_lib.ptr(d), PIXMM, 28.5, 29.0, 0.0045, 0.024, _lib.ptr(hm), _lib.ptr(fmin), _lib.ptr(ind),
+                                                   B, H, W, st), "tacex_height_map_from_indenters")
+    got = hm.cpu().numpy()
+    assert (got[B * H * W:] == -7.0).all() and fmin[B].item() == -7.0 and ind[B].item() == -7.0
+    got = got[:B * H * W].reshape(B, H, W)
+    err = np.abs(got - want).reshape(B, -1).max(1)
+    print(shape, "max |hm - oracle| per env", err)
+    assert err.max() <= 2e-5  # float32 sqrt / sincos round-off
+    assert (got[4] == np.float32(29.0)).all() and (got[[0, 1, 2, 3, 5, 6]].reshape(6, -1).min(1) < 28.5).all()
+    m_o, ind_o = indentation_depth(got)
+    np.testing.assert_array_equal(fmin[:B].cpu().numpy(), m_o)
+    np.testing.assert_array_equal(ind[:B].cpu().numpy(), ind_o)
+    assert ind_o[4] == 0.0 and ind_o[5] == np.float32(4.5) and got[5].min() < 24.0
+    # without the indentation output
+    fmin2 = torch.full((B,), -7.0, device="cuda")
+    _lib.check(lib.tacex_height_map_from_indenters(_lib.ptr(d), PIXMM, 28.5, 29.0, 0.0045, 0.024, _lib.ptr(hm), _lib.ptr(fmin2), 0, B, H, W, st),
+               "tacex_height_map_from_indenters")
+    np.testing.assert_array_equal(fmin2.cpu().numpy(), m_o)
+    np.testing.assert_array_equal(hm.cpu().numpy()[:B * H * W].reshape(B, H, W), got)
+    # a width the float4 stores cannot cover is refused before anything is launched
+    hm.fill_(-7.0)
+    rc = lib.tacex_height_map_from_indenters(_lib.ptr(d), PIXMM, 28.5, 29.0, 0.0045, 0.024, _lib.ptr(hm), _lib.ptr(fmin), _lib.ptr(ind), B, H, W + 1, st)
+    assert rc == 2 and b"W % 4 == 0" in lib.tacex_last_error()
+    with pytest.raises(ValueError, match="W % 4 == 0"):
+        _lib.check(rc, "tacex_height_map_from_indenters")
+    assert (hm == -7.0).all().item()
+
+
+@pytest.mark.gpu
 def test_hip_source_vs_oracle_and_sensor_path(calib_dir):
     from oracle.indenter_oracle import indenter_height_map, indentation_depth
     from tacex_amd import GelSightSensor, GelSightSensorCfg, IndenterHeightMapSource
