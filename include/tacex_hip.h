@@ -148,6 +148,23 @@ int tacex_depth_from_deformed_mesh(const double* x_dev, int num_verts, const int
                                    float fx, float fy, float cx, float cy, float near_clip_m, float far_clip_m, float* depth_m_dev,
                                    int num_envs, int height, int width, void* stream);
 
+/* Height-map SOURCE for the affine body that presses into the pad (ball_rolling_uipc.py:71-139): the same depth image, rendered from the
+ * body's 12-unknown state - what the sensor camera sees of the object with the gel hidden, the input Taxim is built for
+ * (ManiSkill-ViTac gen_rgb_image, tactile_sensor_sapienipc.py:424-457).
+ *   rest_verts_dev (num_verts,3) f64 rest vertices X in the body frame, one table for all envs; tris_dev (T,3) int32 indices into it,
+ *   each < num_verts (not checked on the device); q_dev (B,4,3) f64 = (p, c1, c2, c3), c_k the columns of A (UipcSim.q, read in place):
+ *   world point per component w = ((p + X0 c1) + X1 c2) + X2 c3 in f64, separate multiplies and adds;
+ *   cam_pos_dev / cam_rot_inv_dev / intrinsics / clipping range / depth_m_dev (B,H,W) f32 out as in tacex_depth_from_deformed_mesh: from
+ *   the world point on it is that function's kernel (one shared body, a second vertex source), so the image is bit-equal to
+ *   tacex_depth_from_deformed_mesh on those world points.  Bodies of up to 2048 vertices are projected once per workgroup into LDS.
+ *   Image tiles that the part of the body's bounding sphere (radius |A|_2 max|X| about p) inside the clipping range cannot project onto
+ *   skip the vertices altogether (no fragment can lie there: same image).
+ * Returns 2 (no GPU call) on a null buffer, a count <= 0 or a clipping range that is not 0 <= near < far. */
+int tacex_depth_from_affine_body(const double* rest_verts_dev, int num_verts, const int32_t* tris_dev, int num_tris, const double* q_dev,
+                                 const double* cam_pos_dev, const double* cam_rot_inv_dev, float fx, float fy, float cx, float cy,
+                                 float near_clip_m, float far_clip_m, float* depth_m_dev, int num_envs, int height, int width,
+                                 void* stream);
+
 /* Height-map SOURCE from a mesh LIBRARY (ABI 17): the image of tacex_depth_from_mesh, with every env rendering its OWN mesh.
  *   verts_dev (V,3) f32 every mesh's object-frame vertices back to back; tris_dev (T,3) int32 every mesh's triangles back to back,
  *   indexing verts_dev (the concatenated table); mesh_tris_dev (num_meshes,2) int32: first triangle and triangle count of every mesh;

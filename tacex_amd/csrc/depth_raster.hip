@@ -227,33 +227,25 @@ constexpr int kDeformBlock = 256;
 constexpr int kDeformRows = kRasterTileH * kRasterTileW / kDeformBlock;  // pixels per thread (8)
 static_assert(kRasterTileW == 64 && kDeformBlock / 64 * kDeformRows == kRasterTileH, "a wave owns whole 64-pixel tile rows");
 
+//
+// Vertex SOURCE: where the float64 world point of rendered vertex `sv` of env `env` comes from is the kernel's template parameter - the
+// one thing the two entry points differ in.  Everything from the world point on (camera frame, rounding, projection, staging, tile skip,
+// setup rounds, raster) is the one copy below.
+//  - FemSurfaceVerts (tacex_depth_from_deformed_mesh): x[env][surf_ids[sv]], the FEM state.
+//  - AffineBodyVerts (tacex_depth_from_affine_body): the affine body's state q (B,4,3) = (p, c1, c2, c3), c_k the columns of A, read in
+//    place (UipcSim.q), applied to the rest vertex X (nv,3), one table for all envs: per component w = ((p + X0 c1) + X1 c2) + X2 c3 in
+//    float64, separate multiplies and adds (no FMA in this file).  The 12 unknowns are the same for the whole workgroup.
+// A source may also say that a tile can hold no fragment (`out_of_tile`, workgroup-uniform): its vertices are then not staged for that tile.
+// The pad's never does (its vertices are the bound); the body's tests the in-range slab of its bounding sphere.
 struct DeformArgs {
-  const double* x;        // (B,V,3) world positions
-  const int* surf_ids;    // (Vs,) vertex ids into x
-  const int* tris;        // (T,3) indices into surf_ids
+  const int* tris;        // (T,3) indices into the Vs rendered vertices
   const double* cam_pos;  // (B,3)
   const double* rot_inv;  // (B,3,3) world -> camera rotation (row-major)
   float* depth;           // (B,H,W)
-  int V, Vs, T, B, H, W;
+  int Vs, T, B, H, W;
   float fx, fy, cx, cy, near_m, far_m;
   int tiles_x, tiles_y, staged;
 };
-
-struct TriSetup {  // one list entry (64 B): what the per-pixel test of mesh_depth_kernel reads
-  float sx[3], sy[3], iz[3], area, inv_area;
-  int jx0, jx1, iy0, iy1, pad;
-};
-
-// (sx, sy, 1/z, front) of surface vertex `sv` of the env - mesh_depth_kernel's projection of the float32 camera-frame point
-__device__ __forceinline__ float4 project_deformed(const DeformArgs& a, const double* xb, const double* cp, const double* R, int sv) {
-  const size_t vi = (size_t)a.surf_ids[sv] * 3;
-  const double d0 = xb[vi] - cp[0], d1 = xb[vi + 1] - cp[1], d2 = xb[vi + 2] - cp[2];
-  const float px = (float)((R[0] * d0 + R[1] * d1) + R[2] * d2);
-  const float py = (float)((R[3] * d0 + R[4] * d1) + R[5] * d2);
-  const float pz = (float)((R[6] * d0 + R[7] * d1) + R[8] * d2);
-  const float iz = 1.0f / pz;
-  return make_float4((a.fx * px) * iz + a.cx, (a.fy * py) * iz + a.cy, iz, pz > 1e-6f ? 1.0f : 0.0f);
-}
 
 __device__ __forceinline__ float wave_min(float v) {
   for (int o = 32; o > 0; o >>= 1) v = fminf(v, __shfl_xor(v, o));
@@ -264,7 +256,104 @@ __device__ __forceinline__ float wave_max(float v) {
   return v;
 }
 
-__global__ __launch_bounds__(kDeformBlock) void deformed_mesh_depth_kernel(DeformArgs a) {
+struct FemSurfaceVerts {
+  const double* x;      // (B,V,3) world positions
+  const int* surf_ids;  // (Vs,) vertex ids into x
+  int V;
+  struct Env {
+    const double* xb;
+    const int* surf_ids;
+    __device__ __forceinline__ void world(int sv, double w[3]) const {
+      const size_t vi = (size_t)surf_ids[sv] * 3;
+      w[0] = xb[vi]; w[1] = xb[vi + 1]; w[2] = xb[vi + 2];
+    }
+    // (no bound on the pad's vertices cheaper than projecting them)
+    __device__ __forceinline__ bool out_of_tile(const DeformArgs&, const double*, const double*, int, int, int, int, float*) const { return false; }
+  };
+  __device__ __forceinline__ Env env(int e) const { return Env{x + (size_t)e * V * 3, surf_ids}; }
+};
+
+struct AffineBodyVerts {
+  const double* X;  // (Vs,3) rest vertices, body frame
+  const double* q;  // (B,4,3) p | c1 | c2 | c3
+  struct Env {
+    const double* X;
+    const double* q;  // this env's 12 unknowns
+    __device__ __forceinline__ void world(int sv, double w[3]) const {
+      const double X0 = X[3 * sv], X1 = X[3 * sv + 1], X2 = X[3 * sv + 2];
+#pragma unroll
+      for (int i = 0; i < 3; ++i) w[i] = ((q[i] + X0 * q[3 + i]) + X1 * q[6 + i]) + X2 * q[9 + i];
+    }
+    // Workgroup-uniform: true when the tile [x0, x1) x [y0, y1) can hold no fragment of the body.  The staging loop - which forms the
+    // float64 world point of every vertex once per TILE, 40 tiles per 320 x 240 env - is skipped then (measured,
+    // profiles/ball_depth_bench.md).  Conservative float32 bound: |A X| <= |A|_2 |X| with |A|_2^2 = the largest eigenvalue of A^T A <= its
+    // largest absolute row sum (Gershgorin; A^T A is close to I for the stiff body), so the body - vertices and triangles - lies in the
+    // sphere of radius r = |A|_2 max|X| about its origin c = R (p - cam_pos) in the camera frame (R a rotation).  A fragment also has
+    // near <= z <= far: it lies in the slab of the sphere between zlo = max(c.z - r, near) and zhi = min(c.z + r, far), whose points are
+    // within rho = sqrt(r^2 - dist^2) of the sphere's axis (dist: from c.z to the slab, 0 inside it) - for the ball pressed into the pad
+    // the small cap in front of the far plane, not the ball's silhouette.  The slab's screen bounds are taken like the bounding sphere's
+    // in raster_tile_empty, with its slack (0.1 % of the radius, one pixel) for the rounding of the bound.
+    // `red`: kDeformBlock / 64 floats of LDS.
+    __device__ __forceinline__ bool out_of_tile(const DeformArgs& a, const double* cp, const double* R, int x0, int x1, int y0, int y1,
+                                                float* red) const {
+      float r2 = 0.0f;
+      for (int v = threadIdx.x; v < a.Vs; v += kDeformBlock) {
+        const float X0 = (float)X[3 * v], X1 = (float)X[3 * v + 1], X2 = (float)X[3 * v + 2];
+        r2 = fmaxf(r2, (X0 * X0 + X1 * X1) + X2 * X2);
+      }
+      r2 = wave_max(r2);
+      if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = r2;
+      __syncthreads();
+      for (int w = 0; w < kDeformBlock / 64; ++w) r2 = fmaxf(r2, red[w]);
+      __syncthreads();  // (the caller reuses `red`)
+      float c[9];
+#pragma unroll
+      for (int i = 0; i < 9; ++i) c[i] = (float)q[3 + i];  // c[3 k + i]: component i of column k of A
+      float g[3][3];
+#pragma unroll
+      for (int j = 0; j < 3; ++j)
+#pragma unroll
+        for (int k = 0; k < 3; ++k) g[j][k] = fabsf((c[3 * j] * c[3 * k] + c[3 * j + 1] * c[3 * k + 1]) + c[3 * j + 2] * c[3 * k + 2]);
+      const float a2 = fmaxf(fmaxf((g[0][0] + g[0][1]) + g[0][2], (g[1][0] + g[1][1]) + g[1][2]), (g[2][0] + g[2][1]) + g[2][2]);
+      const double d0 = q[0] - cp[0], d1 = q[1] - cp[1], d2 = q[2] - cp[2];
+      const float bx = (float)((R[0] * d0 + R[1] * d1) + R[2] * d2), by = (float)((R[3] * d0 + R[4] * d1) + R[5] * d2);
+      const float bz = (float)((R[6] * d0 + R[7] * d1) + R[8] * d2);
+      const float m = 1.001f, r = (sqrtf(r2) * sqrtf(a2)) * m;
+      if (bz + r < a.near_m || bz - r > a.far_m) return true;
+      const float zlo = fmaxf(bz - r, a.near_m), zhi = fminf(bz + r, a.far_m);
+      if (!(zlo > 1e-4f)) return false;
+      const float dist = bz > zhi ? bz - zhi : (bz < zlo ? zlo - bz : 0.0f);
+      const float rho = sqrtf(fmaxf(r * r - dist * dist, 0.0f)) * m;
+      const float ulo = fminf(a.fx * (bx - rho) / zlo, a.fx * (bx - rho) / zhi) + a.cx - 1.0f;
+      const float uhi = fmaxf(a.fx * (bx + rho) / zlo, a.fx * (bx + rho) / zhi) + a.cx + 1.0f;
+      const float vlo = fminf(a.fy * (by - rho) / zlo, a.fy * (by - rho) / zhi) + a.cy - 1.0f;
+      const float vhi = fmaxf(a.fy * (by + rho) / zlo, a.fy * (by + rho) / zhi) + a.cy + 1.0f;
+      return uhi < (float)x0 || ulo > (float)x1 || vhi < (float)y0 || vlo > (float)y1;
+    }
+  };
+  __device__ __forceinline__ Env env(int e) const { return Env{X, q + (size_t)e * 12}; }
+};
+
+struct TriSetup {  // one list entry (64 B): what the per-pixel test of mesh_depth_kernel reads
+  float sx[3], sy[3], iz[3], area, inv_area;
+  int jx0, jx1, iy0, iy1, pad;
+};
+
+// (sx, sy, 1/z, front) of rendered vertex `sv` of the env - mesh_depth_kernel's projection of the float32 camera-frame point
+template <class VertsEnv>
+__device__ __forceinline__ float4 project_deformed(const DeformArgs& a, const VertsEnv& verts, const double* cp, const double* R, int sv) {
+  double w[3];
+  verts.world(sv, w);
+  const double d0 = w[0] - cp[0], d1 = w[1] - cp[1], d2 = w[2] - cp[2];
+  const float px = (float)((R[0] * d0 + R[1] * d1) + R[2] * d2);
+  const float py = (float)((R[3] * d0 + R[4] * d1) + R[5] * d2);
+  const float pz = (float)((R[6] * d0 + R[7] * d1) + R[8] * d2);
+  const float iz = 1.0f / pz;
+  return make_float4((a.fx * px) * iz + a.cx, (a.fy * py) * iz + a.cy, iz, pz > 1e-6f ? 1.0f : 0.0f);
+}
+
+template <class Verts>
+__global__ __launch_bounds__(kDeformBlock) void deformed_mesh_depth_kernel(DeformArgs a, Verts src) {
   extern __shared__ float4 stage[];  // (min(Vs, kDeformStageMax),) when a.staged
   __shared__ TriSetup list[kDeformBlock];
   __shared__ float box[4][kDeformBlock / 64];
@@ -274,14 +363,18 @@ __global__ __launch_bounds__(kDeformBlock) void deformed_mesh_depth_kernel(Defor
   const int ty = tile / a.tiles_x, tx = tile - ty * a.tiles_x;
   const int x0 = tx * kRasterTileW, y0 = ty * kRasterTileH;
   const int x1 = min(x0 + kRasterTileW, a.W), y1 = min(y0 + kRasterTileH, a.H);  // exclusive
-  const double* xb = a.x + (size_t)env * a.V * 3;
+  const typename Verts::Env verts = src.env(env);
   const double* cp = a.cam_pos + (size_t)env * 3;
   const double* R = a.rot_inv + (size_t)env * 9;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
 
+  // a source that can bound its vertices cheaply says so here: nothing is staged then, the vertex box below stays empty and the tile is
+  // stored as +inf by the one store at the end
+  const bool out = verts.out_of_tile(a, cp, R, x0, x1, y0, y1, box[0]);
+
   float minx = INFINITY, maxx = -INFINITY, miny = INFINITY, maxy = -INFINITY;
-  for (int v = tid; v < a.Vs; v += kDeformBlock) {
-    const float4 p = project_deformed(a, xb, cp, R, v);
+  for (int v = out ? a.Vs : tid; v < a.Vs; v += kDeformBlock) {
+    const float4 p = project_deformed(a, verts, cp, R, v);
     if (a.staged) stage[v] = p;
     if (p.w != 0.0f) { minx = fminf(minx, p.x); maxx = fmaxf(maxx, p.x); miny = fminf(miny, p.y); maxy = fmaxf(maxy, p.y); }
   }
@@ -309,7 +402,7 @@ __global__ __launch_bounds__(kDeformBlock) void deformed_mesh_depth_kernel(Defor
 #pragma unroll
       for (int k = 0; k < 3; ++k) {
         const int sv = a.tris[3 * t + k];
-        const float4 p = a.staged ? stage[sv] : project_deformed(a, xb, cp, R, sv);
+        const float4 p = a.staged ? stage[sv] : project_deformed(a, verts, cp, R, sv);
         sx[k] = p.x; sy[k] = p.y; iz[k] = p.z;
         ok = ok && p.w != 0.0f;
       }
@@ -363,6 +456,19 @@ __global__ __launch_bounds__(kDeformBlock) void deformed_mesh_depth_kernel(Defor
   }
 }
 
+// tiles, staging and the launch of either instantiation (a: everything but tiles_x / tiles_y / staged filled in)
+template <class Verts>
+static int launch_deformed_mesh_depth(DeformArgs a, Verts src, hipStream_t stream) {
+  a.tiles_x = (a.W + kRasterTileW - 1) / kRasterTileW; a.tiles_y = (a.H + kRasterTileH - 1) / kRasterTileH;
+  if ((size_t)a.B * a.tiles_x * a.tiles_y >= (size_t)1 << 31) { set_error("deformed_mesh_depth_kernel: grid too large"); return 2; }
+  a.staged = a.Vs <= kDeformStageMax;
+  const size_t lds = a.staged ? (size_t)a.Vs * sizeof(float4) : 0;
+  hipLaunchKernelGGL(deformed_mesh_depth_kernel<Verts>, dim3((unsigned)(a.B * a.tiles_x * a.tiles_y)), dim3(kDeformBlock), lds, stream, a, src);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) { set_error("deformed_mesh_depth_kernel: %s", hipGetErrorString(e)); return 1; }
+  return 0;
+}
+
 }  // namespace tacex
 
 extern "C" int tacex_depth_from_mesh(const float* verts_dev, const int32_t* tris_dev, int num_verts, int num_tris,
@@ -405,17 +511,34 @@ extern "C" int tacex_depth_from_deformed_mesh(const double* x_dev, int num_verts
     set_error("tacex_depth_from_deformed_mesh: clipping range (%g, %g)", near_clip_m, far_clip_m); return 2;
   }
   DeformArgs a{};
-  a.x = x_dev; a.surf_ids = surf_ids_dev; a.tris = tris_dev; a.cam_pos = cam_pos_dev; a.rot_inv = cam_rot_inv_dev; a.depth = depth_m_dev;
-  a.V = num_verts; a.Vs = num_surf_verts; a.T = num_tris; a.B = num_envs; a.H = height; a.W = width;
+  a.tris = tris_dev; a.cam_pos = cam_pos_dev; a.rot_inv = cam_rot_inv_dev; a.depth = depth_m_dev;
+  a.Vs = num_surf_verts; a.T = num_tris; a.B = num_envs; a.H = height; a.W = width;
   a.fx = fx; a.fy = fy; a.cx = cx; a.cy = cy; a.near_m = near_clip_m; a.far_m = far_clip_m;
-  a.tiles_x = (width + kRasterTileW - 1) / kRasterTileW; a.tiles_y = (height + kRasterTileH - 1) / kRasterTileH;
-  a.staged = num_surf_verts <= kDeformStageMax;
-  const size_t lds = a.staged ? (size_t)num_surf_verts * sizeof(float4) : 0;
-  hipLaunchKernelGGL(deformed_mesh_depth_kernel, dim3((unsigned)(num_envs * a.tiles_x * a.tiles_y)), dim3(kDeformBlock), lds,
-                     (hipStream_t)stream, a);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { set_error("deformed_mesh_depth_kernel: %s", hipGetErrorString(e)); return 1; }
-  return 0;
+  return launch_deformed_mesh_depth(a, FemSurfaceVerts{x_dev, surf_ids_dev, num_verts}, (hipStream_t)stream);
+}
+
+
+extern "C" int tacex_depth_from_affine_body(const double* rest_verts_dev, int num_verts, const int32_t* tris_dev, int num_tris,
+                                            const double* q_dev, const double* cam_pos_dev, const double* cam_rot_inv_dev, float fx, float fy,
+                                            float cx, float cy, float near_clip_m, float far_clip_m, float* depth_m_dev, int num_envs,
+                                            int height, int width, void* stream) {
+  using namespace tacex;
+  if (!rest_verts_dev || !tris_dev || !q_dev || !cam_pos_dev || !cam_rot_inv_dev || !depth_m_dev) {
+    set_error("tacex_depth_from_affine_body: null buffer"); return 2;
+  }
+  if (num_verts <= 0 || num_tris <= 0 || num_envs <= 0 || height <= 0 || width <= 0) {
+    set_error("tacex_depth_from_affine_body: bad counts (verts %d, tris %d, envs %d, image %dx%d)", num_verts, num_tris, num_envs, width,
+              height);
+    return 2;
+  }
+  if (!(near_clip_m >= 0.0f) || !(far_clip_m > near_clip_m)) {
+    set_error("tacex_depth_from_affine_body: clipping range (%g, %g)", near_clip_m, far_clip_m); return 2;
+  }
+  DeformArgs a{};
+  a.tris = tris_dev; a.cam_pos = cam_pos_dev; a.rot_inv = cam_rot_inv_dev; a.depth = depth_m_dev;
+  a.Vs = num_verts; a.T = num_tris; a.B = num_envs; a.H = height; a.W = width;
+  a.fx = fx; a.fy = fy; a.cx = cx; a.cy = cy; a.near_m = near_clip_m; a.far_m = far_clip_m;
+  return launch_deformed_mesh_depth(a, AffineBodyVerts{rest_verts_dev, q_dev}, (hipStream_t)stream);
 }
 
 

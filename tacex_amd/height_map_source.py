@@ -184,7 +184,53 @@ def contact_face_triangles(points, tets, optical_axis_w, min_cos: float = 0.5) -
     return np.ascontiguousarray(faces[cosang > min_cos], dtype=np.int32)
 
 
-class FemSurfaceDepthSource:
+class _SimCameraDepthSource:
+    """What `FemSurfaceDepthSource` and `AffineBodyDepthSource` share: the sensor camera over a `UipcSim` (pose, intrinsics, clipping
+    range, the (num_envs, H, W) depth image), the ordering behind a step on a side stream, and `fill`.  A subclass supplies `_render(sim)`,
+    the one launch that writes `self.depth` from the simulation state."""
+
+    def _init_camera(self, sim, camera_pos_w, camera_quat_w_ros, resolution, intrinsics, clipping_range):
+        """Sets `pos` / `rot_inv` / image size / intrinsics / clipping range / `depth`; returns the camera -> world rotation (3,3)."""
+        from .simulation_approaches.fem_based.sim.tactile_sensor_uipc import quat_to_matrix
+
+        name = type(self).__name__
+        self._sim, dev, B = sim, sim.device, sim.num_envs
+        q = torch.as_tensor(camera_quat_w_ros, dtype=torch.float64).reshape(-1, 4)
+        q = q / q.norm(dim=1, keepdim=True)
+        rot = quat_to_matrix(q)  # camera -> world
+        self.pos = torch.as_tensor(camera_pos_w, dtype=torch.float64).reshape(-1, 3).expand(B, 3).contiguous().to(dev)
+        self.rot_inv = rot.transpose(-1, -2).expand(B, 3, 3).contiguous().to(dev)
+        self.W, self.H = int(resolution[0]), int(resolution[1])
+        self.fx, self.fy, self.cx, self.cy = (float(v) for v in intrinsics)
+        self.near, self.far = float(clipping_range[0]), float(clipping_range[1])
+        if not (0.0 <= self.near < self.far):
+            raise ValueError(f"{name}: clipping range {clipping_range}")
+        self.depth = torch.empty((B, self.H, self.W), dtype=torch.float32, device=dev)
+        self._lib = _lib.load_library()
+        return rot[0]
+
+    def __call__(self) -> torch.Tensor:
+        sim = self._sim
+        sim.wait_for_step()  # a step enqueued on a side stream (UipcSim.step_done) is ordered before the render
+        self._render(sim)
+        return self.depth
+
+    def fill(self, hm: torch.Tensor, frame_min: torch.Tensor, indent: torch.Tensor | None, gelpad_height: float,
+             gelpad_to_camera_min_distance: float):
+        """hm (B, H, W) mm, frame_min (B,), indent (B,) or None: the render above, then the depth -> height-map pass
+        (`tacex_height_map_from_depth` with this source's clipping range), both on the current stream."""
+        if tuple(hm.shape) != tuple(self.depth.shape):
+            raise RuntimeError(f"height map has shape {tuple(hm.shape)}, the source renders {tuple(self.depth.shape)}")
+        depth = self()
+        B, H, W = hm.shape
+        with torch.cuda.device(hm.device):
+            rc = self._lib.tacex_height_map_from_depth(
+                _lib.ptr(depth), self.near, self.far, float(gelpad_height), float(gelpad_to_camera_min_distance), _lib.ptr(hm),
+                _lib.ptr(frame_min), _lib.ptr(indent), 0, 0, B, H, W, _lib.current_stream_handle(hm.device))
+        _lib.check(rc, "tacex_height_map_from_depth")
+
+
+class FemSurfaceDepthSource(_SimCameraDepthSource):
     """Camera depth of the FEM gel pad's deformed contact face, per env, straight from the FEM state (`UipcSim.x`) in one HIP launch
     (`tacex_depth_from_deformed_mesh`): the image the reference's sensor camera takes of the UIPC surface meshes after every step
     (tacex_uipc uipc_sim.py:268-284, read by GelSightSensor._get_height_map).  `source()` -> (num_envs, H, W) float32 depth in metres,
@@ -201,21 +247,15 @@ class FemSurfaceDepthSource:
 
     def __init__(self, uipc_object, camera_pos_w, camera_quat_w_ros, resolution=(320, 240), intrinsics=(340.0, 325.0, 160.0, 125.0),
                  clipping_range=(0.024, 0.029), triangles=None):
-        from .simulation_approaches.fem_based.sim.tactile_sensor_uipc import quat_to_matrix
-
         sim = getattr(uipc_object, "_uipc_sim", None)
         if sim is None or getattr(sim, "x", None) is None:
             raise RuntimeError("FemSurfaceDepthSource needs a UipcObject attached to a UipcSim that was set up (setup_sim)")
         if getattr(uipc_object, "is_affine_body", False):
             raise ValueError("FemSurfaceDepthSource renders the deformable object (the gel pad), not an affine body")
-        self._sim, dev, B = sim, sim.device, sim.num_envs
-        q = torch.as_tensor(camera_quat_w_ros, dtype=torch.float64).reshape(-1, 4)
-        q = q / q.norm(dim=1, keepdim=True)
-        rot = quat_to_matrix(q)  # camera -> world
-        self.pos = torch.as_tensor(camera_pos_w, dtype=torch.float64).reshape(-1, 3).expand(B, 3).contiguous().to(dev)
-        self.rot_inv = rot.transpose(-1, -2).expand(B, 3, 3).contiguous().to(dev)
+        rot = self._init_camera(sim, camera_pos_w, camera_quat_w_ros, resolution, intrinsics, clipping_range)
+        dev = sim.device
         if triangles is None:
-            tri = contact_face_triangles(uipc_object.points, uipc_object.tets, rot[0, :, 2].numpy())
+            tri = contact_face_triangles(uipc_object.points, uipc_object.tets, rot[:, 2].numpy())
         else:
             tri = np.asarray(triangles, dtype=np.int64).reshape(-1, 3)
             if len(tri) and (tri.min() < 0 or tri.max() >= uipc_object.num_verts):
@@ -226,17 +266,8 @@ class FemSurfaceDepthSource:
         self.triangles = np.ascontiguousarray(tri, dtype=np.int32)  # (F,3) object vertex ids
         self.surf_ids = torch.from_numpy(ids.astype(np.int32)).to(dev)
         self.tris = torch.from_numpy(local.reshape(-1, 3).astype(np.int32)).to(dev)
-        self.W, self.H = int(resolution[0]), int(resolution[1])
-        self.fx, self.fy, self.cx, self.cy = (float(v) for v in intrinsics)
-        self.near, self.far = float(clipping_range[0]), float(clipping_range[1])
-        if not (0.0 <= self.near < self.far):
-            raise ValueError(f"FemSurfaceDepthSource: clipping range {clipping_range}")
-        self.depth = torch.empty((B, self.H, self.W), dtype=torch.float32, device=dev)
-        self._lib = _lib.load_library()
 
-    def __call__(self) -> torch.Tensor:
-        sim = self._sim
-        sim.wait_for_step()  # a step enqueued on a side stream (UipcSim.step_done) is ordered before the render
+    def _render(self, sim):
         x = sim.x
         with torch.cuda.device(self.depth.device):
             rc = self._lib.tacex_depth_from_deformed_mesh(
@@ -244,18 +275,38 @@ class FemSurfaceDepthSource:
                 int(self.tris.shape[0]), _lib.ptr(self.pos), _lib.ptr(self.rot_inv), self.fx, self.fy, self.cx, self.cy, self.near,
                 self.far, _lib.ptr(self.depth), int(self.depth.shape[0]), self.H, self.W, _lib.current_stream_handle(self.depth.device))
         _lib.check(rc, "tacex_depth_from_deformed_mesh")
-        return self.depth
 
-    def fill(self, hm: torch.Tensor, frame_min: torch.Tensor, indent: torch.Tensor | None, gelpad_height: float,
-             gelpad_to_camera_min_distance: float):
-        """hm (B, H, W) mm, frame_min (B,), indent (B,) or None: the render above, then the depth -> height-map pass
-        (`tacex_height_map_from_depth` with this source's clipping range), both on the current stream."""
-        if tuple(hm.shape) != tuple(self.depth.shape):
-            raise RuntimeError(f"height map has shape {tuple(hm.shape)}, the source renders {tuple(self.depth.shape)}")
-        depth = self()
-        B, H, W = hm.shape
-        with torch.cuda.device(hm.device):
-            rc = self._lib.tacex_height_map_from_depth(
-                _lib.ptr(depth), self.near, self.far, float(gelpad_height), float(gelpad_to_camera_min_distance), _lib.ptr(hm),
-                _lib.ptr(frame_min), _lib.ptr(indent), 0, 0, B, H, W, _lib.current_stream_handle(hm.device))
-        _lib.check(rc, "tacex_height_map_from_depth")
+
+class AffineBodyDepthSource(_SimCameraDepthSource):
+    """Camera depth of the scene's affine body (the ball of `FemBallScene`), per env, straight from its 12-unknown state (`UipcSim.q`,
+    read in place) in one HIP launch (`tacex_depth_from_affine_body`): what the sensor camera sees of the object that presses into the
+    pad with the gel hidden - the height map Taxim is built for (its pyramid simulates the gel), and the depth ManiSkill-ViTac's
+    `gen_rgb_image` shades (tactile_sensor_sapienipc.py:424-457).  A kinematic body, whose `q` the caller moves, renders the same way.
+    Same interface as `FemSurfaceDepthSource`: `source()` -> (num_envs, H, W) float32 metres, inf where nothing is seen, a drop-in
+    `cfg.sensor_camera_cfg.depth_source`; `fill(...)`; `pos` / `rot_inv` updated in place by the caller.  Every triangle of the body's
+    surface is rendered (the nearest fragment wins, no culling)."""
+
+    def __init__(self, uipc_object, camera_pos_w, camera_quat_w_ros, resolution=(320, 240), intrinsics=(340.0, 325.0, 160.0, 125.0),
+                 clipping_range=(0.024, 0.029)):
+        sim = getattr(uipc_object, "_uipc_sim", None)
+        if not getattr(uipc_object, "is_affine_body", False):
+            raise ValueError("AffineBodyDepthSource renders an affine body (FemSurfaceDepthSource renders the gel pad)")
+        if sim is None or getattr(sim, "x", None) is None or getattr(sim, "_body", None) is not uipc_object:
+            raise RuntimeError("AffineBodyDepthSource needs the affine-body UipcObject of a UipcSim that was set up (setup_sim)")
+        self._init_camera(sim, camera_pos_w, camera_quat_w_ros, resolution, intrinsics, clipping_range)
+        tri = np.ascontiguousarray(uipc_object.tris, dtype=np.int32).reshape(-1, 3)
+        if len(tri) == 0 or tri.min() < 0 or tri.max() >= uipc_object.num_verts:
+            raise ValueError(f"AffineBodyDepthSource: no triangles, or triangle indices outside [0, {uipc_object.num_verts})")
+        self.rest_verts = torch.from_numpy(np.ascontiguousarray(uipc_object.points, dtype=np.float64)).to(sim.device)  # (nv,3) body frame
+        self.tris = torch.from_numpy(tri).to(sim.device)
+
+    def _render(self, sim):
+        q = sim.q
+        if q.dtype != torch.float64 or tuple(q.shape) != (self.depth.shape[0], 4, 3) or not q.is_contiguous():
+            raise ValueError(f"AffineBodyDepthSource: UipcSim.q must stay a contiguous ({self.depth.shape[0]}, 4, 3) float64 tensor")
+        with torch.cuda.device(self.depth.device):
+            rc = self._lib.tacex_depth_from_affine_body(
+                _lib.ptr(self.rest_verts), int(self.rest_verts.shape[0]), _lib.ptr(self.tris), int(self.tris.shape[0]), _lib.ptr(q),
+                _lib.ptr(self.pos), _lib.ptr(self.rot_inv), self.fx, self.fy, self.cx, self.cy, self.near, self.far, _lib.ptr(self.depth),
+                int(self.depth.shape[0]), self.H, self.W, _lib.current_stream_handle(self.depth.device))
+        _lib.check(rc, "tacex_depth_from_affine_body")

@@ -7,6 +7,7 @@ from typing import TYPE_CHECKING
 
 import torch
 
+from ..fots.marker_patches import MarkerImageMixin
 from ..gelsight_simulator import GelSightSimulator
 from .sim import VisionTactileSensorUIPC
 
@@ -15,7 +16,7 @@ if TYPE_CHECKING:
     from .mani_skill_sim_cfg import ManiSkillSimulatorCfg
 
 
-class ManiSkillSimulator(GelSightSimulator):
+class ManiSkillSimulator(MarkerImageMixin, GelSightSimulator):
     cfg: "ManiSkillSimulatorCfg"
 
     def __init__(self, sensor: "GelSightSensor", cfg: "ManiSkillSimulatorCfg"):
@@ -52,6 +53,13 @@ class ManiSkillSimulator(GelSightSimulator):
         if self.marker_data.dtype == torch.float32 and self.marker_motion_sim.gen_marker_flow_fused(out_f32=self.marker_data) is not None:
             return self.marker_data
         self.marker_data[:] = self.marker_motion_sim.gen_marker_flow().to(self.marker_data.dtype)
+        return self.marker_data
+
+    def _marker_pixels(self):
+        """`marker_images()` / `draw_markers()` (mani_skill_sim.py:218-257; `MarkerImageMixin`) stamp a dot at every marker's current PIXEL
+        position: with `cfg.normalize` the marker data are u / (W / 2) - 1, not pixels."""
+        if self.cfg.normalize:
+            raise ValueError("ManiSkillSimulator.marker_images: cfg.normalize is set, marker_data are not pixel positions - pass marker_data in pixels")
         return self.marker_data
 
     def reset(self):
