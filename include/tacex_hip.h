@@ -488,6 +488,31 @@ int tacex_fem_set_coarse_space(tacex_fem_ctx* ctx, int num_coarse, const int32_t
  * than the current gap" contract (UipcSim.contact_gaps). */
 int tacex_fem_contact_gaps(tacex_fem_ctx* ctx, const double* x_dev, double* gaps_dev, int num_envs, void* stream);
 
+/* Contact forces of the gelpad at the state x_dev (num_envs, V, 3) and their net wrench per env, from the solver's own barrier and
+ * friction terms.  Forces act ON THE PAD, in newtons; the force on the indenter is the negative.  Per surface vertex:
+ *   normal force   f_n = lam n, lam = -dB/dd >= 0 of the barrier at x, n the contact normal (away from the indenter);
+ *   friction force f_f = -grad of IPC's lagged friction potential at x (with_friction != 0): lag and sliding reference are those of the
+ *                  context's LAST tacex_fem_step - its start positions, indenter displacement and the indenter position it ended with,
+ *                  read from step_workspace_dev (the indenter rows give kind, radius and axis only: moving an indenter after the step
+ *                  changes the normal part, not the friction part) - with the env's own friction ratio (material library).  Reported for IPC's lag only (tacex_fem_set_friction_lag mode 1): a
+ *                  function of stored data alone.  With mode 0, a null workspace, or a workspace / num_envs other than the last
+ *                  step's, a call with with_friction set is refused (2) with a message; nothing is approximated.
+ * A vertex at or beyond the indenter surface contributes nothing (it shows in slot 15).  An env without an indenter (kind 0, a mesh id
+ * outside the library) reports zeros; an env whose friction reference was cleared (tacex_fem_reset_envs) and has not stepped since
+ * reports zero friction (the reset clears that reference only: the normal part is the barrier's at the reset state).  Friction ratio 0 or contact disabled: valid zeros.
+ * wrench_dev (num_envs, 16) f64:
+ *   0..2 sum f_n | 3..5 sum f_f | 6..8 torque sum (x_v - ref) x (f_n + f_f) | 9 sum lam_v | 10 contact area (sum of the vertex areas of
+ *   the active vertices) | 11 number of active vertices | 12..14 centre of pressure sum lam_v x_v / sum lam_v (the reference point when
+ *   sum lam = 0) | 15 smallest gap over the surface vertices (+inf without an indenter)
+ * ref_points_dev (num_envs, 3): the torque's reference point per env (NULL: the origin).  vertex_force_dev (num_envs, V, 3), nullable:
+ * f_n + f_f of every vertex, zeros at interior and inactive vertices.  One launch, fixed summation order: bit-reproducible, and an
+ * env's results do not depend on the batch it shares.  The rotation of an indenter between two steps does not enter the friction
+ * displacement (tacex_fem_set_friction).  Not implemented for a scene with an affine body (2).  Enqueued on `stream`. */
+int tacex_fem_contact_forces(tacex_fem_ctx* ctx, const double* x_dev, const void* step_workspace_dev /* nullable: no friction */,
+                             const double* ref_points_dev /* (B,3), nullable: origin */, int with_friction,
+                             double* wrench_dev /* (B,16) */, double* vertex_force_dev /* (B,V,3), nullable */,
+                             int num_envs, void* stream);
+
 /* Rigid TRIANGLE-MESH indenter shared by all envs (indenter kind 4 of tacex_fem_set_contact's rows): vertices (num_verts,3) f64 in
  * the mesh's own frame, triangles (num_tris,3) int32.  An env's indenter row [4, px, py, pz, offset, rx, ry, rz] places it: p =
  * position of the mesh origin, r = rotation vector (axis * angle), offset >= 0 inflates the surface.  The barrier acts between

@@ -148,6 +148,7 @@ SIGNATURES = {
     "tacex_fem_set_material_ids": (_i, [_vp, _vp]),
     "tacex_fem_set_material_coarse_inverses": (_i, [_vp, _i, _vp]),
     "tacex_fem_contact_gaps": (_i, [_vp, _vp, _vp, _i, _vp]),
+    "tacex_fem_contact_forces": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp]),
     "tacex_fem_newton_resident": (_i, [_vp]),
     "tacex_fem_newton_route": (_i, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "tacex_fem_set_friction_lag": (_i, [_vp, _i]),

@@ -42,6 +42,7 @@
 #include "fem_newton_lds.h"     // fem_newton_lds_kernel
 #include "fem_assemble.h"       // fem_assemble_blocks_kernel
 #include "fem_step_kernels.h"   // order, predict, velocity, reset, attachment, markers
+#include "fem_contact_forces.h" // fem_contact_forces_kernel: contact forces and net wrench at a state
 
 using namespace tacex;
 
@@ -386,6 +387,41 @@ int tacex_fem_contact_gaps(tacex_fem_ctx* c, const double* x_dev, double* gaps_d
   hipLaunchKernelGGL(fem_contact_gaps_kernel, dim3(num_envs), dim3(256), 0, (hipStream_t)stream, c->dev, x_dev, gaps_dev);
   e = hipGetLastError();
   return e == hipSuccess ? 0 : fail_hip(e, "fem_contact_gaps_kernel");
+}
+
+int tacex_fem_contact_forces(tacex_fem_ctx* c, const double* x_dev, const void* ws, const double* ref_points_dev, int with_friction,
+                             double* wrench_dev, double* vertex_force_dev, int num_envs, void* stream) {
+  if (!c || !x_dev || !wrench_dev) { set_error("tacex_fem_contact_forces: null argument"); return 2; }
+  if (num_envs < 0) { set_error("tacex_fem_contact_forces: num_envs = %d", num_envs); return 2; }
+  if (c->ball.nv > 0) {
+    set_error("tacex_fem_contact_forces: not implemented for a scene with an affine body (tacex_fem_set_affine_body): its contacts are pairs");
+    return 2;
+  }
+  const int B = num_envs;
+  const double *xprev = nullptr, *disp = nullptr, *ind_prev = nullptr;
+  if (with_friction && c->dev.indenters) {  // (contact disabled: valid zeros, whatever else is set)
+    if (c->fric_lag_mode != 1) {
+      set_error("tacex_fem_contact_forces: friction is reported for IPC's lag only (tacex_fem_set_friction_lag mode 1): the reaction-capped "
+                "lag depends on an iterate the step does not keep");
+      return 2;
+    }
+    if (!ws) { set_error("tacex_fem_contact_forces: friction needs the step workspace (x_prev and the indenter displacement live there)"); return 2; }
+    if (c->ind_prev_ws != ws || c->ind_prev_B != B) {
+      set_error("tacex_fem_contact_forces: friction needs the workspace and num_envs of the context's last tacex_fem_step (num_envs %d, last step %d)",
+                B, c->ind_prev_B);
+      return 2;
+    }
+    const StepLayout lay(c->dev.V, c->dev.T, B);
+    const double* base = static_cast<const double*>(ws);
+    xprev = base + lay.x_prev; disp = base + lay.disp; ind_prev = base + lay.ind_prev;
+  }
+  if (B == 0) return 0;
+  hipError_t e = hipSetDevice(c->device);
+  if (e != hipSuccess) return fail_hip(e, "hipSetDevice");
+  hipLaunchKernelGGL(fem_contact_forces_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, c->dev, x_dev, xprev, disp, ind_prev, ref_points_dev,
+                     wrench_dev, vertex_force_dev, c->mat);
+  e = hipGetLastError();
+  return e == hipSuccess ? 0 : fail_hip(e, "fem_contact_forces_kernel");
 }
 
 int tacex_fem_set_deterministic(tacex_fem_ctx* c, int enable) {

@@ -55,6 +55,10 @@ class ManiSkillSimulator(MarkerImageMixin, GelSightSimulator):
         self.marker_data[:] = self.marker_motion_sim.gen_marker_flow().to(self.marker_data.dtype)
         return self.marker_data
 
+    def contact_wrench(self, **kw):
+        """Contact forces and net wrench on the gelpad in the camera frame (`VisionTactileSensorUIPC.contact_wrench`)."""
+        return self.marker_motion_sim.contact_wrench(**kw)
+
     def _marker_pixels(self):
         """`marker_images()` / `draw_markers()` (mani_skill_sim.py:218-257; `MarkerImageMixin`) stamp a dot at every marker's current PIXEL
         position: with `cfg.normalize` the marker data are u / (W / 2) - 1, not pixels."""

@@ -157,6 +157,10 @@ class FemGelpad:
             self._pending = self.ev
             self.ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
 
+    def contact_forces(self, **kw):
+        """`UipcSim.contact_forces` of the scene's sim (forces ON the pad, world frame)."""
+        return self.sim.contact_forces(**kw)
+
     def reset_indenters(self, env_ids):
         """Indenters of `env_ids` back to where the scene started them (what a task does together with `gelpad.reset(env_ids)`)."""
         self.ind[env_ids] = self.ind0[env_ids]

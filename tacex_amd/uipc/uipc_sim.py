@@ -10,6 +10,7 @@ scene - ONE free affine-body ball per env on the ground plane under the gelpad, 
 from __future__ import annotations
 
 import ctypes as C
+from dataclasses import dataclass
 
 import numpy as np
 import torch
@@ -122,6 +123,62 @@ class UipcSimCfg:
     contact: Contact = Contact()
     collision_detection_method: str = "linear_bvh"
     diff_sim: bool = False
+
+
+@dataclass
+class ContactForces:
+    """Contact forces of the gelpad per env (`UipcSim.contact_forces`): views into the one (num_envs, 16) float64 `record` of
+    `tacex_fem_contact_forces`.  Forces act ON THE PAD, in newtons, in the frame the record is expressed in (world; the sensor's
+    `contact_wrench()`: camera); the force on the indenter is the negative."""
+
+    record: torch.Tensor
+    vertex_forces: torch.Tensor | None = None
+    """(num_envs, V, 3) normal + friction force of every vertex (zeros at interior and inactive vertices), or None."""
+
+    @property
+    def normal_force(self) -> torch.Tensor:
+        """(num_envs, 3) sum of the barrier forces."""
+        return self.record[:, 0:3]
+
+    @property
+    def friction_force(self) -> torch.Tensor:
+        """(num_envs, 3) sum of the lagged friction forces (zeros when friction was not evaluated)."""
+        return self.record[:, 3:6]
+
+    @property
+    def force(self) -> torch.Tensor:
+        """(num_envs, 3) normal + friction."""
+        return self.record[:, 0:3] + self.record[:, 3:6]
+
+    @property
+    def torque(self) -> torch.Tensor:
+        """(num_envs, 3) sum (x_v - ref) x f_v about the env's reference point."""
+        return self.record[:, 6:9]
+
+    @property
+    def normal_magnitude(self) -> torch.Tensor:
+        """(num_envs,) sum of the normal-force magnitudes of the vertices (what Coulomb's bound multiplies)."""
+        return self.record[:, 9]
+
+    @property
+    def contact_area(self) -> torch.Tensor:
+        """(num_envs,) sum of the vertex areas of the active vertices [m^2]."""
+        return self.record[:, 10]
+
+    @property
+    def num_contacts(self) -> torch.Tensor:
+        """(num_envs,) number of active vertices (float64, exact)."""
+        return self.record[:, 11]
+
+    @property
+    def centre_of_pressure(self) -> torch.Tensor:
+        """(num_envs, 3) normal-force weighted mean of the active vertices (the reference point without contact)."""
+        return self.record[:, 12:15]
+
+    @property
+    def min_gap(self) -> torch.Tensor:
+        """(num_envs,) smallest gap over the surface vertices (+inf without an indenter; <= 0: penetration)."""
+        return self.record[:, 15]
 
 
 class UipcSim:
@@ -271,6 +328,7 @@ class UipcSim:
         if indenters is None:
             _lib.check(self._lib.tacex_fem_set_contact(self._handle, 0, 0.0, 0.0, 0), "tacex_fem_set_contact")
             self.contact_indenters = None
+            self._friction_ref = False  # (the library drops the friction reference with the contact: contact_forces)
             return
         if not self.cfg.contact.enable:
             raise RuntimeError("UipcSimCfg.contact.enable is False")
@@ -278,6 +336,8 @@ class UipcSim:
             raise NotImplementedError("a scene with an affine body takes its contact from the body, the ground and the gelpad (pairs); prescribed "
                                       "indenters are the other kind of scene (or make the body kinematic: AffineBodyConstitutionCfg.kinematic)")
         ind = indenters.to(self.device, torch.float64).reshape(self.num_envs, 8).contiguous()
+        if getattr(self, "contact_indenters", None) is None:
+            self._friction_ref = False  # contact enabled for the first time (or again): no step has run with it yet
         area = None
         if not getattr(self, "_contact_area_set", False):
             area = np.ascontiguousarray(self._obj.surface_vertex_areas(), dtype=np.float64)
@@ -474,6 +534,51 @@ class UipcSim:
         gaps = torch.empty(x.shape[:2], dtype=torch.float64, device=self.device)
         _lib.check(self._lib.tacex_fem_contact_gaps(self._handle, _lib.ptr(x), _lib.ptr(gaps), x.shape[0], self._stream()), "tacex_fem_contact_gaps")
         return gaps
+
+    def contact_forces(self, x=None, ref_points=None, per_vertex: bool = False, friction: bool | None = None) -> ContactForces:
+        """Contact forces of the gelpad at `x` (None: the current state) and their net wrench per env, from the solver's own barrier
+        and friction terms (`tacex_fem_contact_forces`: one launch on the current stream, no host round trip).
+
+        SIGN: forces act ON THE PAD, in newtons - a pressing indenter pushes the pad's face inward; the force on the indenter is the
+        negative of what is returned.
+
+        ref_points (num_envs, 3): the point the torque is taken about, per env (None: the world origin).  per_vertex: also return the
+        (num_envs, V, 3) force of every vertex.  friction: None = friction iff `cfg.contact.enable_friction`, `friction_lag == "ipc"`
+        and a step has run since contact was enabled; True where the library would refuse (another lag rule, no step yet) raises
+        ValueError; False = the normal part alone.  The friction part is IPC's lagged friction of the LAST step - lag from that step's
+        start positions against the indenter where it stood then, sliding measured from there - evaluated at `x`; only the indenter's
+        translation enters it (`set_contact_indenters`), and moving an indenter after that step changes the normal part only.  An env reset
+        since (`reset(env_ids)`) reports zero friction until it steps; its normal part is the barrier's at the reset state.
+        Without contact indenters: zeros and +inf gaps, nothing is launched.  Scenes with an affine body are not covered."""
+        if getattr(self, "_body", None) is not None:
+            raise NotImplementedError("contact_forces covers prescribed indenters; the pair contacts of a scene with an affine body are not reported")
+        self.wait_for_step()  # (a side-stream step writes self.x AND the workspace rows the friction part reads)
+        x = self.x if x is None else x.to(self.device, torch.float64).contiguous()
+        if x.dim() != 3 or x.shape[0] > self.num_envs or x.shape[1] != self._obj.num_verts or x.shape[2] != 3:
+            raise ValueError(f"contact_forces: x must be (<= {self.num_envs}, {self._obj.num_verts}, 3), got {tuple(x.shape)}")
+        B, V = x.shape[0], x.shape[1]
+        c = self.cfg.contact
+        have_ind = getattr(self, "contact_indenters", None) is not None
+        can = bool(have_ind and getattr(c, "friction_lag", "ipc") == "ipc" and getattr(self, "_friction_ref", False) and B == self.num_envs)
+        if friction is None:
+            friction = bool(c.enable_friction) and can
+        elif friction and have_ind and not can:
+            raise ValueError("contact_forces(friction=True): friction is reported for friction_lag = 'ipc' only, after a step() with the "
+                             "contact indenters, for all num_envs envs")
+        if not have_ind:
+            rec = torch.zeros((B, 16), dtype=torch.float64, device=self.device)
+            rec[:, 15] = float("inf")
+            if ref_points is not None:
+                rec[:, 12:15] = ref_points.to(self.device, torch.float64).reshape(B, 3)
+            return ContactForces(rec, torch.zeros((B, V, 3), dtype=torch.float64, device=self.device) if per_vertex else None)
+        ref = None if ref_points is None else ref_points.to(self.device, torch.float64).reshape(B, 3).contiguous()
+        rec = torch.empty((B, 16), dtype=torch.float64, device=self.device)
+        vf = torch.empty((B, V, 3), dtype=torch.float64, device=self.device) if per_vertex else None
+        with torch.cuda.device(self.device):
+            rc = self._lib.tacex_fem_contact_forces(self._handle, _lib.ptr(x), _lib.ptr(self._ws) if friction else 0, _lib.ptr(ref),
+                                                    1 if friction else 0, _lib.ptr(rec), _lib.ptr(vf), B, self._stream())
+        _lib.check(rc, "tacex_fem_contact_forces")
+        return ContactForces(rec, vf)
 
     def contact_gaps_torch(self, x=None) -> torch.Tensor:
         """The same distances restated in torch ops (tests compare the two)."""
@@ -729,6 +834,8 @@ class UipcSim:
                 self._g_host, n_max, float(self.cfg.newton.velocity_tol), int(self.cfg.linear_system.max_iter),
                 float(self.cfg.linear_system.tol_rate), int(self.cfg.line_search.max_iter), self._stream())
         _lib.check(rc, "tacex_fem_step")
+        if getattr(self, "contact_indenters", None) is not None:
+            self._friction_ref = True  # the workspace now holds this step's start positions and indenter displacement (contact_forces)
         return self.x
 
     # -- a step on a side stream ---------------------------------------------------------------------------------------
