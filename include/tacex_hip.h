@@ -303,6 +303,22 @@ int tacex_resize_bilinear_aa_nhwc(const float* src_dev, int src_h, int src_w, fl
  * 0 = every level as its own kernel + separate shade kernel. */
 int tacex_taxim_set_fused_tail(tacex_taxim_ctx* ctx, int enabled);
 
+/* Route read-back (tests, diagnostics): which kernel family the context's next render runs pyramid level `level` on - the
+ * library answers from the same decision its launch code takes.  -1: null context / level out of range. */
+#define TACEX_ROUTE_GENERIC 0        /* two-pass generic blur */
+#define TACEX_ROUTE_BAND 1           /* fully unrolled band kernel */
+#define TACEX_ROUTE_BAND_LOOP_384 2  /* looped band kernel, 384-thread form (W <= 384) */
+#define TACEX_ROUTE_BAND_LOOP_640 3  /* looped band kernel, 640-thread form */
+#define TACEX_ROUTE_MFMA 4           /* matrix-core band kernel */
+#define TACEX_ROUTE_TAIL 5           /* fused into the tail (tacex_taxim_set_fused_tail) */
+int tacex_taxim_level_route(const tacex_taxim_ctx* ctx, int level);
+/* ... and how a render without the shadow branch ends: with_frames = 0 a plain render, != 0 one that also stores the full
+ * deformed-gel / mask frames (z_out / mask_out).  -1: null context. */
+#define TACEX_TAIL_NONE 0    /* every level as its own kernel, then the shade kernel */
+#define TACEX_TAIL_TILED 1   /* LDS-tiled fused tail (taxim_tail.hip) */
+#define TACEX_TAIL_STREAM 2  /* streaming fused tail (taxim_stream.hip) */
+int tacex_taxim_tail_route(const tacex_taxim_ctx* ctx, int with_frames);
+
 /* Frames one pass of the kernel sequence covers for a call with num_frames frames: large shards are walked in chunks whose
  * level buffers stay resident in the 256 MB Infinity Cache (== num_frames when the shard is rendered in one pass).
  * bench.py needs it to turn per-launch durations into bytes per launch. */

@@ -115,6 +115,8 @@ SIGNATURES = {
     "tacex_resize_bilinear_aa_nhwc": (_i, [_vp, _i, _i, _vp, _i, _i, _i, _i, _vp, _vp]),
     "tacex_taxim_set_fused_tail": (_i, [_vp, _i]),
     "tacex_taxim_chunk_frames": (_i, [_vp, _i]),
+    "tacex_taxim_level_route": (_i, [_vp, _i]),
+    "tacex_taxim_tail_route": (_i, [_vp, _i]),
     "tacex_taxim_set_profiling": (_i, [_vp, _i]),
     "tacex_taxim_read_profile": (_i, [_vp, _i, C.POINTER(C.c_double), C.POINTER(C.c_int)]),
     "tacex_taxim_num_stages": (_i, [_vp]),

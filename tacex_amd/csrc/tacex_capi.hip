@@ -676,12 +676,22 @@ static hipError_t level_stream(int device, hipStream_t caller, int q, hipStream_
 // >= 2048 strips to fill the chip without splitting strips into short segments (each segment re-runs an 18-row warm-up), and
 // with it the band kernels measured the same chunked or not (C3: 3.95 ms chunked at 256, 3.86 ms in one pass) - passes of up
 // to 1024 frames of 320x240 there.  TACEX_CHUNK_FRAMES overrides (0 = whole batch in one pass).
+// How a pass ends (the TACEX_TAIL_* of include/tacex_hip.h): the ONE decision behind pipeline_chunk, the pass policy and the
+// read-back of tacex_taxim_tail_route.  want_rgb: the pass shades; want_frames: it stores full deformed-gel / mask frames (which
+// the streaming tail does not produce).
+enum TailRoute { kTailNone = 0, kTailTiled = 1, kTailStream = 2 };
+static TailRoute tail_route(const tacex_taxim_ctx* c, bool want_rgb, bool want_frames) {
+  if (!c->use_tail || c->n_fused <= 0) return kTailNone;
+  const bool stream = c->use_stream && want_rgb && !want_frames &&
+                      stream_supported(c->n_fused, c->levels[c->n_levels - c->n_fused].kw, c->H, c->W);
+  return stream ? kTailStream : kTailTiled;
+}
+
 static int chunk_frames(const tacex_taxim_ctx* c, int B) {
   static const int env = getenv("TACEX_CHUNK_FRAMES") ? atoi(getenv("TACEX_CHUNK_FRAMES")) : -1;
   if (env == 0) return B;
   if (env > 0) return env < B ? env : B;
-  const bool stream = c->use_tail && c->use_stream && c->n_fused > 0 &&
-                      stream_supported(c->n_fused, c->levels[c->n_levels - c->n_fused].kw, c->H, c->W);
+  const bool stream = tail_route(c, true, false) == kTailStream;
   const size_t per_frame = (size_t)3 * c->H * c->W * sizeof(float);
   // (2048 frames of 320x240 per streaming pass since round 5: a GelSightSensorGroup of two 1024-env sensors is one pass - 1571 us for the
   //  tail's 2048 frames against 2 x 802, C3 660 K against 652 K frames/s in two passes, profiles/r05_experiments.md.
@@ -898,9 +908,9 @@ static int pipeline_chunk(tacex_taxim_ctx* c, const Pass& p) {
     // the kernels read ARE the frame-min and press arrays - no (B,)-sized helper launch (~5 us of a ~600 us step)
     s.sa = p.frame_min; s.sb = p.press; s.pd = p.press;
   }
-  s.n_fused = c->use_tail ? c->n_fused : 0; s.n_band = c->n_levels - s.n_fused;
-  s.stream_tail = s.n_fused > 0 && c->use_stream && p.rgb && !p.z_out && !p.mask_out &&
-                  stream_supported(s.n_fused, c->levels[c->n_levels - s.n_fused].kw, c->H, c->W);
+  const TailRoute tail = tail_route(c, p.rgb != nullptr, p.z_out || p.mask_out);
+  s.n_fused = tail != kTailNone ? c->n_fused : 0; s.n_band = c->n_levels - s.n_fused;
+  s.stream_tail = tail == kTailStream;
   for (int l = 0; l < s.n_band; ++l) s.band_grow += (c->levels[l].kh - 1) / 2;
   const float* src = nullptr; bool order_done = false;
   if (int rc = run_band_levels(c, p, s, plan_band_levels(c, p, s), &src, &order_done)) return rc;
@@ -1039,7 +1049,7 @@ int tacex_taxim_set_fots_taps(tacex_taxim_ctx* c, const int32_t* marker_x, const
 }
 
 int tacex_taxim_fots_partials_per_env(const tacex_taxim_ctx* c) {
-  if (!c || !c->use_tail || c->n_fused <= 0) return 0;
+  if (!c || tail_route(c, true, false) == kTailNone) return 0;
   return (int)(tail_tiles_per_frame(c->H, c->W) * kTailWavesPerTile);
 }
 
@@ -1074,6 +1084,19 @@ int tacex_taxim_set_fused_tail(tacex_taxim_ctx* c, int enabled) {
   c->use_tail = enabled != 0;
   c->use_stream = enabled == 1;
   return 0;
+}
+
+/* route read-back: what the next render of this context launches (the decisions of run_blur_level / pipeline_chunk themselves) */
+int tacex_taxim_level_route(const tacex_taxim_ctx* c, int level) {
+  if (!c || level < 0 || level >= c->n_levels) return -1;
+  const int n_fused = tail_route(c, true, false) != kTailNone ? c->n_fused : 0;
+  if (level >= c->n_levels - n_fused) return TACEX_ROUTE_TAIL;
+  return (int)blur_level_route(c->levels[level], level == 0, c->H, c->W);
+}
+
+int tacex_taxim_tail_route(const tacex_taxim_ctx* c, int with_frames) {
+  if (!c) return -1;
+  return (int)tail_route(c, true, with_frames != 0);
 }
 
 int tacex_resize_bilinear_aa(const float* src, int sh, int sw, float* dst, int dh, int dw, int B, void* stream) {

@@ -49,6 +49,10 @@ hipError_t run_indenter_height_map(const float* desc, float* hm, float* fmin, fl
                                    float gel_top_mm, float far_clip_mm, float gelpad_h, float gelpad_dmin, hipStream_t st);
 hipError_t run_press_depth(const float* fmin, const float* press, float* sa, float* sb, float* pd, int B,
                            int no_shift, hipStream_t st);
+// The kernel family run_blur_level launches for a level: the ONE decision behind the launch, blur_level_single_kernel and the
+// read-back of tacex_taxim_level_route (the values are the TACEX_ROUTE_* of include/tacex_hip.h).
+enum BlurRoute { kRouteGeneric = 0, kRouteBand = 1, kRouteBandLoop384 = 2, kRouteBandLoop640 = 3, kRouteMfma = 4 };
+BlurRoute blur_level_route(const LevelDesc& lv, bool first, int H, int W);
 bool blur_level_single_kernel(const LevelDesc& lv, bool first, int H, int W);  // one launch, no use of the shared scratch image
 hipError_t run_blur_level(const LevelDesc& lv, const float* src, const float* hm, const float* gel,
                           const float* sa, const float* sb, const float* pd, float* dst, float* tmp,

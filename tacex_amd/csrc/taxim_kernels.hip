@@ -1011,15 +1011,26 @@ hipError_t run_press_depth(const float* fmin, const float* press, float* sa, flo
 }
 
 // true: run_blur_level runs this level as ONE matrix-core launch that never touches `tmp` (launches of different frame ranges may overlap)
-bool blur_level_single_kernel(const LevelDesc& lv, bool first, int H, int W) {
-  return lv.same_taps && lv.taps_mfma_dev && mfma_supported(lv.kw, first, H, W);
+// matrix-core kernel, else the looped band kernel (k >= band_loop_min_k, or sizes the unrolled one is not instantiated for), else
+// the unrolled band kernel, else the generic two-pass blur
+BlurRoute blur_level_route(const LevelDesc& lv, bool first, int H, int W) {
+  if (lv.same_taps && lv.taps_mfma_dev && mfma_supported(lv.kw, first, H, W)) return kRouteMfma;
+  const bool unrolled_ok = band_supported(lv.kw, H, W) && (!first || band_first_supported(lv.kw));
+  if (lv.same_taps && lv.taps_pad_dev && band_loop_supported(lv.kw, H, W) && (!unrolled_ok || lv.kw >= band_loop_min_k()) &&
+      (band_loop_min_k() != 35 || !unrolled_ok))
+    return W <= 384 ? kRouteBandLoop384 : kRouteBandLoop640;
+  if (lv.same_taps && unrolled_ok) return kRouteBand;
+  return kRouteGeneric;
 }
+
+bool blur_level_single_kernel(const LevelDesc& lv, bool first, int H, int W) { return blur_level_route(lv, first, H, W) == kRouteMfma; }
 
 hipError_t run_blur_level(const LevelDesc& lv, const float* src, const float* hm, const float* gel,
                           const float* sa, const float* sb, const float* pd, float* dst, float* tmp,
                           uint8_t* mask_out, int B, int H, int W, float contact_scale, int restore,
                           bool first, hipStream_t st, const int* rows_ext, int ext_grow, int ext_grow_x) {
-  if (lv.same_taps && lv.taps_mfma_dev && mfma_supported(lv.kw, first, H, W)) {
+  const BlurRoute route = blur_level_route(lv, first, H, W);
+  if (route == kRouteMfma) {
     BlurArgs a{};
     a.src = src; a.hm = hm; a.shift_a = sa; a.shift_b = sb; a.pdepth = pd;
     a.rows_ext = lv.gel_zero ? rows_ext : nullptr; a.ext_grow = ext_grow; a.ext_grow_x = ext_grow_x;  // zero-band / zero-block skipping needs J = min(S, 0)
@@ -1028,17 +1039,15 @@ hipError_t run_blur_level(const LevelDesc& lv, const float* src, const float* hm
     a.contact_scale = contact_scale; a.restore = restore;
     return dispatch_mfma(lv.kw, first, a, st);
   }
-  const bool unrolled_ok = band_supported(lv.kw, H, W) && (!first || band_first_supported(lv.kw));
-  if (lv.same_taps && lv.taps_pad_dev && band_loop_supported(lv.kw, H, W) && (!unrolled_ok || lv.kw >= band_loop_min_k()) &&
-      (band_loop_min_k() != 35 || !unrolled_ok)) {
+  if (route == kRouteBandLoop384 || route == kRouteBandLoop640) {
     BlurArgs a{};
     a.src = src; a.hm = hm; a.gel = gel; a.shift_a = sa; a.shift_b = sb; a.pdepth = pd;
     a.dst = dst; a.mask_out = mask_out; a.taps = lv.taps_pad_dev; a.H = H; a.W = W; a.B = B;
     a.contact_scale = contact_scale; a.restore = restore;
-    if (W <= 384) return first ? launch_band_loop<true, 384>(a, lv.kw, st) : launch_band_loop<false, 384>(a, lv.kw, st);
+    if (route == kRouteBandLoop384) return first ? launch_band_loop<true, 384>(a, lv.kw, st) : launch_band_loop<false, 384>(a, lv.kw, st);
     return first ? launch_band_loop<true, 640>(a, lv.kw, st) : launch_band_loop<false, 640>(a, lv.kw, st);
   }
-  if (lv.same_taps && band_supported(lv.kw, H, W) && (!first || band_first_supported(lv.kw))) {
+  if (route == kRouteBand) {
     BlurArgs a{};
     a.src = src; a.hm = hm; a.gel = gel; a.shift_a = sa; a.shift_b = sb; a.pdepth = pd;
     a.dst = dst; a.mask_out = mask_out; a.taps = lv.taps_w_dev; a.H = H; a.W = W; a.B = B;

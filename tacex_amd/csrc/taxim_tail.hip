@@ -638,8 +638,20 @@ int tail_levels(const LevelDesc* lv, int n_levels, int H, int W) {
   // two workgroups per CU).  TACEX_TAIL_LEVELS_640=4 restores the four-level kernel (A/B hook).
   static const int lv640 = getenv("TACEX_TAIL_LEVELS_640") ? atoi(getenv("TACEX_TAIL_LEVELS_640")) : 3;
   static const int lv320 = getenv("TACEX_TAIL_LEVELS_320") ? atoi(getenv("TACEX_TAIL_LEVELS_320")) : 4;
-  if (match(4, k320)) return lv320 == 3 ? 3 : 4;
-  if (match(4, k640)) return lv640 == 4 ? 4 : 3;
+  // A set is fused only
+  //  - with a band level left in front of it: both tails read that level's output (zin), there is none to read otherwise.  A
+  //    four-level request of the 640x480 set on a four-level context falls back to the default three levels (k = 15 stays in
+  //    front); a context of the four 320x240 levels alone runs unfused (<5,3,5> is the A/B choice there, never a default);
+  //  - in a frame larger than the set's summed radii: the halo is loaded at SINGLY reflected (then clamped) coordinates and the
+  //    mirrored halo is the reflect padding of every later level only while that mirror index stays inside the frame.
+  auto admit = [&](int n) {
+    if (n >= n_levels) return 0;
+    int sum_r = 0;
+    for (int i = 0; i < n; ++i) sum_r += (lv[n_levels - n + i].kw - 1) / 2;
+    return (H > sum_r && W > sum_r) ? n : 0;
+  };
+  if (match(4, k320)) return admit(lv320 == 3 ? 3 : 4);
+  if (match(4, k640)) return admit((lv640 == 4 && n_levels > 4) ? 4 : 3);
   return 0;
 }
 

@@ -366,6 +366,22 @@ class TaximHip:
         ctx = self.context(shape_hw)
         _lib.check(self._lib.tacex_taxim_set_fused_tail(ctx.handle, int(enabled)), "set_fused_tail")
 
+    LEVEL_ROUTE_NAMES = ("generic", "band", "band_loop_384", "band_loop_640", "mfma", "tail")  # TACEX_ROUTE_* of the header
+    TAIL_ROUTE_NAMES = ("shade", "tiled", "stream")                                               # TACEX_TAIL_*
+
+    def level_routes(self, shape_hw) -> dict:
+        """What the next render at this resolution launches (`tacex_taxim_level_route` / `tacex_taxim_tail_route`, the library's own
+        launch decisions): {"ksize": kernel size per pyramid level, "levels": one of LEVEL_ROUTE_NAMES per level, "tail": how a plain
+        render ends, "tail_frames": how one with `z_out` / `mask_out` (and `deform`) ends - each one of TAIL_ROUTE_NAMES}."""
+        ctx = self.context(shape_hw)
+        n = len(ctx.tables.ksize_w)
+        levels = [int(self._lib.tacex_taxim_level_route(ctx.handle, l)) for l in range(n)]
+        tails = [int(self._lib.tacex_taxim_tail_route(ctx.handle, f)) for f in (0, 1)]
+        if min(levels + tails) < 0:
+            raise _lib.TacexHipError("tacex_taxim_level_route / tacex_taxim_tail_route rejected the context")
+        return {"ksize": list(ctx.tables.ksize_w), "levels": [self.LEVEL_ROUTE_NAMES[r] for r in levels],
+                "tail": self.TAIL_ROUTE_NAMES[tails[0]], "tail_frames": self.TAIL_ROUTE_NAMES[tails[1]]}
+
     # -- FOTS contact statistics as a by-product of the render (fused tail only) -------------------------------------
     def fots_partials_per_env(self, shape_hw) -> int:
         """Records per env the fused tail writes (0: no fused tail for this shape / tail disabled)."""

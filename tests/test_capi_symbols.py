@@ -28,6 +28,23 @@ def test_library_exports_every_declared_symbol():
     assert lib.tacex_abi_version() == hdr == _lib.ABI_VERSION
 
 
+def test_route_read_back_is_declared_and_named():
+    """tacex_taxim_level_route / tacex_taxim_tail_route: declared, exported, and the header's TACEX_ROUTE_* / TACEX_TAIL_* values are
+    the positions of the names Taxim.level_routes() reports."""
+    from tacex_amd import _lib
+    from tacex_amd.simulation_approaches.gpu_taxim.sim import TaximHip
+
+    txt = (REPO / "include" / "tacex_hip.h").read_text()
+    lib = _lib.load_library()
+    for name in ("tacex_taxim_level_route", "tacex_taxim_tail_route"):
+        assert name in _declared_functions() and hasattr(lib, name) and _lib.SIGNATURES[name][0] is _lib.C.c_int
+        assert getattr(lib, name)(None, 0) == -1  # a null context is an error value, not a route
+    routes = {m.group(1).lower(): int(m.group(2)) for m in re.finditer(r"#define\s+TACEX_ROUTE_([A-Z0-9_]+)\s+(\d+)", txt)}
+    assert routes == {n: i for i, n in enumerate(TaximHip.LEVEL_ROUTE_NAMES)}
+    tails = {m.group(1).lower(): int(m.group(2)) for m in re.finditer(r"#define\s+TACEX_TAIL_([A-Z0-9_]+)\s+(\d+)", txt)}
+    assert tails == {"none": 0, "tiled": 1, "stream": 2} and TaximHip.TAIL_ROUTE_NAMES == ("shade", "tiled", "stream")
+
+
 def test_argument_validation_needs_no_gpu():
     """NULL / bad arguments are rejected before any HIP call, with a message in tacex_last_error()."""
     import ctypes as C

@@ -373,7 +373,7 @@ def test_mfma_and_valu_band_kernels_agree(calib_dir, golden_dir, tmp_path):
 
 
 @pytest.mark.parametrize("shape,segs,mcols", [((240, 320), "0", 11), ((240, 320), "3", 11), ((240, 320), "8", 11), ((480, 640), "0", 11),
-                                              ((480, 640), "5", 11), ((240, 320), "0", 26)])
+                                              ((480, 640), "5", 11), ((240, 320), "0", 26), ((243, 324), "0", 11), ((243, 324), "3", 11)])
 def test_streaming_tail_matches_tiled_tail(calib_dir, tmp_path, shape, segs, mcols):
     """The wave-autonomous streaming tail (taxim_stream.hip, default) against the LDS-tiled tail (taxim_tail.hip) through the
     sensor boundary: RGB bit-equal (same summation order of every level, same shading code), uint8 / float policy observation
