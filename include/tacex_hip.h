@@ -204,7 +204,7 @@ typedef struct tacex_shadow_params {
   float height_precision;      /* params.json simulator.height_precision (0.1) */
   float discretize_precision;  /* params.json simulator.discretize_precision (0.1) */
   float step_x, step_y;        /* shadow_step(shape)[1], [0] (sic: x uses the height-scaled value), TT:298-305 */
-  int32_t blur_kw, blur_kh;    /* shadow_blur_sigma kernel, TT:339-342 */
+  int32_t blur_kw, blur_kh;    /* shadow_blur_sigma kernel, TT:339-342: odd, (k - 1) / 2 smaller than the image (reflect padding) */
   const float* blur_taps_w;
   const float* blur_taps_h;
 } tacex_shadow_params;

@@ -86,11 +86,29 @@ def gaussian_kernel1d(sigma: float, k: int) -> np.ndarray:
     return (pdf / pdf.sum(dtype=F32)).astype(F32)
 
 
-def blur_direct(img: np.ndarray, sigma_wh, ksize_wh=None) -> np.ndarray:
-    """Separable correlation over the last two axes in float64, mirror borders (== torch 'reflect', TT:411)."""
+def _correlate1d_plain(img: np.ndarray, taps: np.ndarray, axis: int) -> np.ndarray:
+    """Mirror-border correlation summed tap by tap in img's own dtype (no wider accumulator)."""
+    r = (len(taps) - 1) // 2
+    pad = [(0, 0)] * img.ndim
+    pad[axis] = (r, r)
+    xp = np.moveaxis(np.pad(img, pad, mode="reflect"), axis, -1)
+    n = img.shape[axis]
+    out = np.zeros(xp.shape[:-1] + (n,), dtype=img.dtype)
+    for j, t in enumerate(taps.astype(img.dtype)):
+        out += t * xp[..., j : j + n]
+    return np.moveaxis(out, -1, axis)
+
+
+def blur_direct(img: np.ndarray, sigma_wh, ksize_wh=None, dtype=np.float64) -> np.ndarray:
+    """Separable correlation over the last two axes in float64, mirror borders (== torch 'reflect', TT:411).  Another `dtype`
+    (float32) sums tap by tap in that type instead: a float32 evaluation of the same blur."""
     sw, sh = sigma_wh
     kw = gaussian_kernel_size(sw) if ksize_wh is None else ksize_wh[0]
     kh = gaussian_kernel_size(sh) if ksize_wh is None else ksize_wh[1]
+    if np.dtype(dtype) != np.float64:
+        out = np.asarray(img, dtype=dtype)
+        out = _correlate1d_plain(out, gaussian_kernel1d(sh, kh), -2)
+        return _correlate1d_plain(out, gaussian_kernel1d(sw, kw), -1)
     gw = gaussian_kernel1d(sw, kw).astype(np.float64)
     gh = gaussian_kernel1d(sh, kh).astype(np.float64)
     out = np.asarray(img, dtype=np.float64)
@@ -309,37 +327,39 @@ class TaximOracle:
         first = total // 2
         return [np.maximum(1, first), np.maximum(1, total - first)]  # each (kw, kh)
 
-    def shadow_map(self, Z: np.ndarray, M: np.ndarray):
+    def shadow_map(self, Z: np.ndarray, M: np.ndarray, steps_wh=None):
         """(B,H,W,3) per-pixel / channel minimum of the shadow-table samples (+inf: no sample) = `shadow_img` of TT:324-336,
         and the gradient direction map it was marched with."""
-        return self.shade_with_shadow(Z, M, _return_shadow_map=True)
+        return self.shade_with_shadow(Z, M, _return_shadow_map=True, steps_wh=steps_wh)
 
-    def shade_with_shadow(self, Z: np.ndarray, M: np.ndarray, _return_shadow_map: bool = False) -> np.ndarray:
-        """Deformed gel (B,H,W) + shrunken contact mask -> (B,H,W,3) RGB with cast shadows."""
-        H, W = self.H, self.W
-        B = Z.shape[0]
-        Zf = np.asarray(Z, F32)
-        z_px = -(Zf / F32(self.p.pixmm))
-        mag, dr = self.normals(z_px)
-        im, idd = self.bins(mag, dr)
-        coef = self.poly[:, im, idd]
-        sim = np.moveaxis((coef * self.feat[None, None]).sum(-1, dtype=F32), 0, 1).astype(F32)  # (B,3,H,W)
+    def ring(self, M: np.ndarray) -> np.ndarray:
+        """The pixels that cast rays: contact mask dilated by the two box rounds, minus the mask itself (TT:261-273)."""
         dil = M.astype(F32)
         for (kw, kh) in self.shadow_attachment_rounds():
             dil = self._box_dilate_same(dil, int(kh), int(kw))
-        boundary = (dil != 0) & ~M
+        return (dil != 0) & ~M
+
+    def shadow_samples(self, Z: np.ndarray, M: np.ndarray, dr: np.ndarray, steps_wh=None, gel: np.ndarray | None = None) -> dict:
+        """The ray march of TT:275-323 as index arrays: ring pixels (bi, yi, xi), their direction / height bins (the height bin
+        before and after the out-of-table clamp), the truncated sample pixels sx / sy (N, fan, step), which of them lie `inside` the
+        image, which are `valid` (inside, and the target higher than the source) and the table values `sel` (3, N, step).
+        `steps_wh` / `gel` replace shadow_step (w_val, h_val) / the gel map: what tests use to show that either one matters."""
+        H, W = self.H, self.W
+        Zf = np.asarray(Z, F32)
+        gel = self.gel if gel is None else np.asarray(gel, F32)
+        boundary = self.ring(M)
         bi, yi, xi = np.nonzero(boundary)
         norm_idx = np.floor((dr[boundary].astype(F32) + F32(math.pi)) / F32(self.p.sim["discretize_precision"])).astype(np.int64)
         zpx = (Zf / F32(self.p.pixmm)).astype(F32)  # deformed_gel_px
-        contact_px = ((self.gel[None] - Zf) / F32(self.p.pixmm)).astype(F32)[boundary]
-        hidx = np.floor((contact_px * F32(self.p.pixmm) - F32(self.shadow_depth_0)) / F32(self.p.sim["height_precision"])).astype(np.int64) + 6
+        contact_px = ((gel[None] - Zf) / F32(self.p.pixmm)).astype(F32)[boundary]
+        hraw = np.floor((contact_px * F32(self.p.pixmm) - F32(self.shadow_depth_0)) / F32(self.p.sim["height_precision"])).astype(np.int64) + 6
         max_h = self.shadow_table.shape[2] - 1
+        hidx = hraw.copy()
         hidx[(hidx < 0) | (hidx >= max_h)] = max_h
         sel = self.shadow_table[:, norm_idx, hidx]  # (3,N,51)
-        thetas = self.fan[norm_idx]                 # (N,4)
         nstep = sel.shape[-1]
         steps = (np.arange(nstep) + 1).astype(F32)
-        step_w, step_h = self.p.rel("shadow_step", (H, W))  # (w_val, h_val); x uses [1], y uses [0] (TT:300-305)
+        step_w, step_h = self.p.rel("shadow_step", (H, W)) if steps_wh is None else steps_wh  # (w_val, h_val); x uses [1], y uses [0] (TT:300-305)
         # cos / sin of the float32 fan table (TT:299,303 take them of the gathered angles; taking them of the table first and
         # gathering is the same numbers and lets the device use the very same bits, tacex_amd/calibration.py:build_shadow_tables)
         cos_t, sin_t = np.cos(self.fan).astype(F32)[norm_idx], np.sin(self.fan).astype(F32)[norm_idx]
@@ -348,7 +368,25 @@ class TaximOracle:
         sx = np.trunc(sx).astype(np.int64)
         sy = np.trunc(sy).astype(np.int64)
         cx, cy = np.clip(sx, 0, W - 1), np.clip(sy, 0, H - 1)
-        valid = (sx >= 0) & (sx < W) & (sy >= 0) & (sy < H) & (zpx[bi, yi, xi][:, None, None] < zpx[bi[:, None, None], cy, cx])
+        inside = (sx >= 0) & (sx < W) & (sy >= 0) & (sy < H)
+        valid = inside & (zpx[bi, yi, xi][:, None, None] < zpx[bi[:, None, None], cy, cx])
+        return dict(bi=bi, yi=yi, xi=xi, norm_idx=norm_idx, hraw=hraw, hidx=hidx, max_h=max_h, sx=sx, sy=sy, inside=inside, valid=valid,
+                    sel=sel)
+
+    def shade_with_shadow(self, Z: np.ndarray, M: np.ndarray, _return_shadow_map: bool = False, steps_wh=None,
+                          work_dtype=None) -> np.ndarray:
+        """Deformed gel (B,H,W) + shrunken contact mask -> (B,H,W,3) RGB with cast shadows.  `work_dtype` float32 runs the two image
+        blurs of the "direct" mode in float32 (tap by tap, no wider accumulator): the round-off yardstick of the shadow tests."""
+        H, W = self.H, self.W
+        B = Z.shape[0]
+        Zf = np.asarray(Z, F32)
+        z_px = -(Zf / F32(self.p.pixmm))
+        mag, dr = self.normals(z_px)
+        im, idd = self.bins(mag, dr)
+        coef = self.poly[:, im, idd]
+        sim = np.moveaxis((coef * self.feat[None, None]).sum(-1, dtype=F32), 0, 1).astype(F32)  # (B,3,H,W)
+        s = self.shadow_samples(Zf, M, dr, steps_wh)
+        bi, sx, sy, valid, sel = s["bi"], s["sx"], s["sy"], s["valid"], s["sel"]
         shadow = np.full((3, B * H * W), np.inf, F32)
         n_i, f_i, s_i = np.nonzero(valid)
         flat = (bi[n_i] * H + sy[valid]) * W + sx[valid]
@@ -358,8 +396,13 @@ class TaximOracle:
             return np.moveaxis(shadow.reshape(3, B, H, W), 0, -1), dr
         sim = np.minimum(sim, np.moveaxis(shadow.reshape(3, B, H, W), 0, 1))
         wdt = np.float64 if self.blur_mode == "direct" else F32
-        s1 = self._blur(sim.astype(wdt), self.p.rel("shadow_blur_sigma", (H, W)))
-        s2 = self._blur(s1 + self.bg[None].astype(wdt), self.final_sigma)
+        if work_dtype is not None and self.blur_mode == "direct":
+            wdt = np.dtype(work_dtype).type
+            blur = lambda img, sg: blur_direct(img, sg, dtype=wdt)
+        else:
+            blur = self._blur
+        s1 = blur(sim.astype(wdt), self.p.rel("shadow_blur_sigma", (H, W)))
+        s2 = blur(s1 + self.bg[None].astype(wdt), self.final_sigma)
         return np.moveaxis(np.clip(s2, 0, 1), 1, -1).astype(F32)
 
     # -- TI:153-163 + TT:174-195 ----------------------------------------------------------------------

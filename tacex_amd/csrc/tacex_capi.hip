@@ -417,6 +417,13 @@ int tacex_taxim_set_shadow(tacex_taxim_ctx* c, const tacex_shadow_params* p) {
     set_error("tacex_taxim_set_shadow: bad table dimensions");
     return 2;
   }
+  // blur_nhwc3_kernel mirrors an index once (reflect_idx): like torch 'reflect' padding, the pad must be smaller than the image
+  // (the final blur is a pyramid level: tacex_taxim_create has checked it)
+  if (p->blur_kw < 1 || p->blur_kh < 1 || (p->blur_kw - 1) / 2 >= c->W || (p->blur_kh - 1) / 2 >= c->H) {
+    set_error("tacex_taxim_set_shadow: shadow blur reflect padding (%d, %d) must be smaller than the image (%d, %d)",
+              (p->blur_kw - 1) / 2, (p->blur_kh - 1) / 2, c->W, c->H);
+    return 2;
+  }
   HIP_TRY(hipSetDevice(c->device), "hipSetDevice");
   ShadowParams& s = c->shadow;
   s.ndir = p->num_directions; s.nfan = p->num_fan_rays; s.nheight = p->num_heights; s.nstep = p->num_steps;

@@ -310,16 +310,21 @@ class TaximHip:
         _lib.check(rc, "tacex_taxim_deform")
         return z_out, mask_out
 
-    def shadow_rays(self, deformed_gel: torch.Tensor, contact_mask: torch.Tensor, grad_dir: torch.Tensor) -> torch.Tensor:
+    def shadow_rays(self, deformed_gel: torch.Tensor, contact_mask: torch.Tensor, grad_dir: torch.Tensor,
+                    out: torch.Tensor | None = None) -> torch.Tensor:
         """Ray march of the shadow branch alone (taxim_torch.py:261-337): (B,H,W) deformed gel [mm], uint8 shrunken contact
-        mask and gradient direction -> (B,H,W,3) per-pixel / channel minimum of the shadow-table samples (+inf: none)."""
+        mask and gradient direction -> (B,H,W,3) per-pixel / channel minimum of the shadow-table samples (+inf: none),
+        into `out` where one is given."""
         z = self._check_hm(deformed_gel)
         B, H, W = z.shape
         ctx = self.context((H, W))
         self._ensure_shadow(ctx)
         m = contact_mask.to(self._device, torch.uint8).reshape(B, H, W).contiguous()
         g = grad_dir.to(self._device, torch.float32).reshape(B, H, W).contiguous()
-        out = torch.empty((B, H, W, 3), dtype=torch.float32, device=self._device)
+        if out is None:
+            out = torch.empty((B, H, W, 3), dtype=torch.float32, device=self._device)
+        elif tuple(out.shape) != (B, H, W, 3) or not out.is_contiguous() or out.dtype != torch.float32 or out.device != self._device:
+            raise ValueError("out must be a contiguous float32 (B,H,W,3) tensor on the simulator's device")
         with torch.cuda.device(self._device):
             rc = self._lib.tacex_taxim_shadow_rays(ctx.handle, _lib.ptr(z), _lib.ptr(m), _lib.ptr(g), _lib.ptr(out), B,
                                                    _lib.current_stream_handle(self._device))

@@ -2,7 +2,11 @@
 // offset and total of the Taxim render workspace and of the shadow branch's regions behind it equals the expression the host layer used
 // before the layouts got a header of their own (written out below as literals); the regions are in order, do not overlap, are 256-byte
 // aligned and end at the total; a chunk's regions stay in front of the whole batch's contact rows; the observation scratch bound.
+// With arguments "H W B [H W B ...]" the same checks run on those frames and frame counts instead of the built-in set.
 #include <stdio.h>
+#include <stdlib.h>
+
+#include <vector>
 
 #include "taxim_layout.h"
 
@@ -27,13 +31,21 @@ static void check_regions(const Region* r, int count, size_t total, int H, int W
   CHECK(align_up(r[count - 1].begin + r[count - 1].length, 256) == total);
 }
 
-int main() {
+int main(int argc, char** argv) {
   const int sizes[][2] = {{16, 16}, {17, 20}, {240, 320}, {480, 640}}, Bs[] = {1, 2, 63, 64, 65, 512, 2048};
   const int obs[][2] = {{32, 32}, {8, 64}, {64, 8}};
+  struct Frames { int H, W, B; };
+  std::vector<Frames> set;
+  if (argc > 1) {
+    if ((argc - 1) % 3) { printf("usage: %s [H W B]...\n", argv[0]); return 2; }
+    for (int i = 1; i + 2 < argc; i += 3) set.push_back({atoi(argv[i]), atoi(argv[i + 1]), atoi(argv[i + 2])});
+  } else {
+    for (const auto& hw : sizes)
+      for (int B : Bs) set.push_back({hw[0], hw[1], B});
+  }
   int cases = 0;
-  for (const auto& hw : sizes)
-    for (int B : Bs) {
-      const int H = hw[0], W = hw[1];
+  for (const Frames& fr : set) {
+      const int H = fr.H, W = fr.W, B = fr.B;
       int n = 0;
       const size_t px = (size_t)B * H * W;
       const size_t img = align_up((size_t)B * H * W * sizeof(float), 256), vec = align_up((size_t)B * sizeof(float), 256);
@@ -89,7 +101,7 @@ int main() {
       }
       // the max takes each side somewhere in the set
       CHECK(H * 64 > 8 * W && 64 * W > H * 8);
-    }
+  }
   printf("%d layouts checked, %d failures\n", cases, failures);
   return failures ? 1 : 0;
 }
