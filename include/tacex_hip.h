@@ -523,7 +523,8 @@ int tacex_fem_contact_gaps(tacex_fem_ctx* ctx, const double* x_dev, double* gaps
  * ref_points_dev (num_envs, 3): the torque's reference point per env (NULL: the origin).  vertex_force_dev (num_envs, V, 3), nullable:
  * f_n + f_f of every vertex, zeros at interior and inactive vertices.  One launch, fixed summation order: bit-reproducible, and an
  * env's results do not depend on the batch it shares.  The rotation of an indenter between two steps does not enter the friction
- * displacement (tacex_fem_set_friction).  Not implemented for a scene with an affine body (2).  Enqueued on `stream`. */
+ * displacement (tacex_fem_set_friction).  Not implemented for a scene with an affine body (2): tacex_fem_ball_contact_forces reports
+ * that scene's pair contacts.  Enqueued on `stream`. */
 int tacex_fem_contact_forces(tacex_fem_ctx* ctx, const double* x_dev, const void* step_workspace_dev /* nullable: no friction */,
                              const double* ref_points_dev /* (B,3), nullable: origin */, int with_friction,
                              double* wrench_dev /* (B,16) */, double* vertex_force_dev /* (B,V,3), nullable */,
@@ -700,6 +701,44 @@ int tacex_fem_reset_envs(tacex_fem_ctx* ctx, const int32_t* env_ids_dev, int num
  * envs keep theirs.  Enqueued on `stream`. */
 int tacex_fem_ball_reset_envs(tacex_fem_ctx* ctx, const int32_t* env_ids_dev, int num_reset, const double* q0_dev, double* q_dev,
                               double* qv_dev, void* ball_workspace_dev, int num_envs, void* stream);
+
+/* Contact forces of the ball scene (tacex_fem_set_affine_body) at the state x_dev (num_envs, V, 3), q_dev (num_envs, 4, 3): the pairs
+ * between pad and body (pad vertex x body triangle, body vertex x pad triangle, pad edge x body edge unless tacex_fem_set_edge_edge
+ * switched them off), the ground under both, and IPC's lagged friction of all of them - tacex_fem_ball_step's own terms evaluated once,
+ * in one launch.  A force on a state row is -(1 / dt^2) d/d row of the term's share of the incremental potential, in newtons, world
+ * frame.  A pair is active when it is closer than d_hat and its weight is positive; lam = -kappa w m b'(d / d_hat) / d_hat >= 0.
+ * Friction (with_friction != 0): the lagged contacts are the active pairs and ground contacts of the state the last step STARTED from -
+ * x_prev / q_prev of ball_workspace_dev, or x_prev_dev (num_envs, V, 3) / q_prev_dev (num_envs, 4, 3) when given (both or neither; they
+ * override the workspace's rows: the entry the parity tests use, like tacex_fem_ball_terms) - with lam, normal and coefficients frozen
+ * there; the force is -mu lam f1(|u|) / |u| u on every row, u the tangential relative displacement since that state, mu and
+ * eps_velocity * dt the context's (tacex_fem_set_friction).  A kinematic body's rows slide from the pose the last step measured the body's
+ * motion from (where it stood when the step before ended; that step's first with its workspace: no motion), which tacex_fem_ball_step
+ * leaves in the workspace: the friction reported is what the step balanced.  An env put back by tacex_fem_ball_reset_envs reports zero friction
+ * until it steps.  Friction ratio 0: valid zeros.  Refused (2, with a message): a context without a body, null x / q / record, one of
+ * x_prev_dev / q_prev_dev alone, with_friction with neither explicit previous states nor the workspace and num_envs of the context's last
+ * tacex_fem_ball_step.
+ * record_dev (num_envs, 44) f64 - forces act ON THE BODY NAMED FIRST:
+ *   0..2   pad <- body: sum of the barrier forces on the pad rows (the mollifier's term of nearly parallel edge pairs included)
+ *   3..5   pad <- body: sum of the friction forces of the pair contacts on the pad rows
+ *   6..8   torque of 0..5 on the pad, sum (x_row - ref) x f_row
+ *   9      sum lam over the active pairs         10  number of active pairs        11  flags (0, or 16: a candidate list overflowed)
+ *   12..14 centre of pressure sum lam_k c_k / sum lam_k, c_k the pad-side closest point (the reference point when sum lam = 0)
+ *   15     smallest distance over the active pairs (+inf: none)      16..18 active pairs of kind 0 / 1 / 2      19  0
+ *   20..31 body: generalised contact force on its 12 rows (p, c_1, c_2, c_3): pairs + their friction + ground + ground friction
+ *   32..34 body <- ground: friction (x, y) and normal (z) force
+ *   35 / 36 / 37 sum lam, count and smallest gap of the body's ground contacts (+inf: none)
+ *   38..40 pad <- ground force     41 / 42 count and smallest gap of the pad's ground contacts (+inf: none)     43  0
+ * Slots 0..9 and 12..15 mean what they mean in tacex_fem_contact_forces' record.  ref_points_dev (num_envs, 3): the torque's reference
+ * point per env (NULL: the origin).  vertex_force_dev (num_envs, V, 3), nullable: the total contact force of every pad vertex (pairs,
+ * their friction, ground, ground friction).  Candidates are culled as in the step (lists of 512 per env in LDS); an overflow sets flag
+ * 16 and the sums then miss contacts - nothing is written out of bounds.  List slots are handed out with atomics: results agree to
+ * round-off from run to run and batch to batch, not bit for bit.  Enqueued on `stream`.  The call was added without a change of
+ * TACEX_ABI_VERSION (no existing signature or struct moved): a caller detects it by looking the symbol up, not by the version. */
+int tacex_fem_ball_contact_forces(tacex_fem_ctx* ctx, const double* x_dev, const double* q_dev,
+                                  const void* ball_workspace_dev /* nullable */, const double* x_prev_dev /* nullable */,
+                                  const double* q_prev_dev /* nullable */, const double* ref_points_dev /* (B,3), nullable: origin */,
+                                  int with_friction, double* record_dev /* (B,44) */, double* vertex_force_dev /* (B,V,3), nullable */,
+                                  int num_envs, void* stream);
 
 /* Attachment animation (UA:364-428: `_compute_aim_positions` + the animator callback `animate_tet` UA:365-385) for all envs:
  *   aim_position[b, idx[a]] = R(body_quat[b]) * offsets[a] + body_pos[b];  is_constrained[b, idx[a]] = 1

@@ -163,6 +163,7 @@ SIGNATURES = {
     "tacex_fem_ball_step": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, C.POINTER(C.c_double), _i, _d, _d, _i, _d, _i, _vp]),
     "tacex_fem_reset_envs": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
     "tacex_fem_ball_reset_envs": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp]),
+    "tacex_fem_ball_contact_forces": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp]),
     "tacex_fem_set_friction": (_i, [_vp, _d, _d]),
     "tacex_fem_set_contact_following": (_i, [_vp, _i]),
     "tacex_fem_set_deterministic": (_i, [_vp, _i]),

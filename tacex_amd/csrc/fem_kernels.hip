@@ -39,6 +39,7 @@
 #include "fem_terms.h"          // element terms, energy, gradient
 #include "fem_newton_stream.h"  // fem_newton_kernel
 #include "fem_ball.h"           // fem_ball_newton_kernel: pad + affine body + ground
+#include "fem_ball_contact_forces.h"  // fem_ball_contact_forces_kernel: the ball scene's contact forces and wrenches at a state
 #include "fem_newton_lds.h"     // fem_newton_lds_kernel
 #include "fem_assemble.h"       // fem_assemble_blocks_kernel
 #include "fem_step_kernels.h"   // order, predict, velocity, reset, attachment, markers
@@ -75,6 +76,8 @@ struct tacex_fem_ctx {
   tacex::BallDev ball{};     // the env's free affine body + ground (tacex_fem_set_affine_body); nv == 0: none
   const void* ball_last_ws = nullptr;  // workspace / env count whose "q at the end of the previous step" rows are valid (kinematic bodies)
   int ball_last_B = 0;
+  const void* ball_step_ws = nullptr;  // workspace / env count of the last tacex_fem_ball_step: its x_prev / q_prev rows are that step's start state
+  int ball_step_B = 0;                 // (tacex_fem_ball_contact_forces takes its friction lag from them)
   // what tacex_fem_set_material_library needs to build a material's mass table (lumped_mass)
   std::vector<int> tets_host;    // (4,T) SoA, re-oriented
   std::vector<double> vol_host;  // (T)
@@ -394,7 +397,8 @@ int tacex_fem_contact_forces(tacex_fem_ctx* c, const double* x_dev, const void* 
   if (!c || !x_dev || !wrench_dev) { set_error("tacex_fem_contact_forces: null argument"); return 2; }
   if (num_envs < 0) { set_error("tacex_fem_contact_forces: num_envs = %d", num_envs); return 2; }
   if (c->ball.nv > 0) {
-    set_error("tacex_fem_contact_forces: not implemented for a scene with an affine body (tacex_fem_set_affine_body): its contacts are pairs");
+    set_error("tacex_fem_contact_forces: not implemented for a scene with an affine body (tacex_fem_set_affine_body): its contacts are pairs, "
+              "tacex_fem_ball_contact_forces reports them");
     return 2;
   }
   const int B = num_envs;
@@ -965,6 +969,7 @@ int tacex_fem_set_affine_body(tacex_fem_ctx* c, int num_verts, const double* ver
   fem_release(c, bd.bedge, &synced); fem_release(c, bd.bearea, &synced); fem_release(c, bd.belen2, &synced);
   bd = BallDev{};
   c->ball_last_ws = nullptr; c->ball_last_B = 0;
+  c->ball_step_ws = nullptr; c->ball_step_B = 0;
   if (num_verts == 0) return 0;  // remove the body
   if (!verts_host || !tris_host || !pad_vertex_area_host || !pad_tris_host || num_verts < 4 || num_tris < 4 || num_pad_tris < 1) {
     set_error("tacex_fem_set_affine_body: null / too small mesh argument");
@@ -1153,11 +1158,57 @@ int tacex_fem_ball_step(tacex_fem_ctx* c, double* x, double* v, double* q, doubl
                      static_cast<double*>(nullptr), B);
   hipLaunchKernelGGL(fem_ball_velocity_kernel, dim3((unsigned)((B * 12 + 255) / 256)), dim3(256), 0, st, q, qprev, qv, B, 1.0 / dt);
   if (c->ball.kinematic) {
+    // the pose this step's friction slid the body rows from is kept for tacex_fem_ball_contact_forces in the q~ rows, which nothing reads
+    // once the Newton kernel has ended (a kinematic body has no inertia term to predict for): no workspace region of its own
+    (void)hipMemcpyAsync(qt, have_last ? qlast : qprev, (size_t)B * 12 * sizeof(double), hipMemcpyDeviceToDevice, st);
     (void)hipMemcpyAsync(qlast, q, (size_t)B * 12 * sizeof(double), hipMemcpyDeviceToDevice, st);
     c->ball_last_ws = ws; c->ball_last_B = B;
   }
+  c->ball_step_ws = ws; c->ball_step_B = B;
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? 0 : fail_hip(e, "tacex_fem_ball_step");
+}
+
+int tacex_fem_ball_contact_forces(tacex_fem_ctx* c, const double* x_dev, const double* q_dev, const void* ws, const double* x_prev_dev,
+                                  const double* q_prev_dev, const double* ref_points_dev, int with_friction, double* record_dev,
+                                  double* vertex_force_dev, int num_envs, void* stream) {
+  if (!c || !x_dev || !q_dev || !record_dev) { set_error("tacex_fem_ball_contact_forces: null argument"); return 2; }
+  if (c->ball.nv == 0) { set_error("tacex_fem_ball_contact_forces: no affine body (tacex_fem_set_affine_body); tacex_fem_contact_forces covers prescribed indenters"); return 2; }
+  if (num_envs < 0) { set_error("tacex_fem_ball_contact_forces: num_envs = %d", num_envs); return 2; }
+  if ((x_prev_dev == nullptr) != (q_prev_dev == nullptr)) { set_error("tacex_fem_ball_contact_forces: x_prev_dev and q_prev_dev go together"); return 2; }
+  const int B = num_envs;
+  const double *xprev = nullptr, *qlag = nullptr, *qref = nullptr;
+  if (with_friction && c->dev.fric_mu > 0.0) {  // (friction ratio 0: valid zeros, whatever else is set)
+    if (x_prev_dev) {
+      xprev = x_prev_dev; qlag = q_prev_dev; qref = q_prev_dev;
+    } else {
+      if (!ws || c->ball_step_ws != ws || c->ball_step_B != B) {
+        set_error("tacex_fem_ball_contact_forces: friction needs x_prev_dev / q_prev_dev or the workspace and num_envs of the context's last "
+                  "tacex_fem_ball_step (num_envs %d, last step %d)", B, c->ball_step_B);
+        return 2;
+      }
+      const BallLayout lay = ball_layout(c, B);
+      const double* base = static_cast<const double*>(ws);
+      xprev = base + lay.x_prev; qlag = base + lay.q_prev;
+      // the step's own rule for the body rows: a free body slides from where the step started; a kinematic one from where it stood at
+      // the end of the step BEFORE the last one (what that step's friction measured the body's motion from: tacex_fem_ball_step leaves
+      // it in the q~ rows; its first step with a workspace leaves q_prev there: no body motion)
+      qref = c->ball.kinematic ? base + lay.qt : qlag;
+    }
+  }
+  if (B == 0) return 0;
+  const size_t lds = ball_force_lds_bytes(c->dev.V, c->ball.nv, vertex_force_dev != nullptr);
+  if (lds > (size_t)40 * 1024) {
+    set_error("tacex_fem_ball_contact_forces: body of %d vertices, pad of %d (the body's surface points%s are kept in 40 KB of LDS: %zu B)", c->ball.nv,
+              c->dev.V, vertex_force_dev ? " and the per-vertex forces" : "", lds);
+    return 2;
+  }
+  hipError_t e = hipSetDevice(c->device);
+  if (e != hipSuccess) return fail_hip(e, "hipSetDevice");
+  hipLaunchKernelGGL(fem_ball_contact_forces_kernel, dim3(B), dim3(256), lds, (hipStream_t)stream, c->ball, c->dev.V, c->dev.fric_mu, c->dev.fric_eps,
+                     x_dev, q_dev, xprev, qlag, qref, ref_points_dev, record_dev, vertex_force_dev);
+  e = hipGetLastError();
+  return e == hipSuccess ? 0 : fail_hip(e, "fem_ball_contact_forces_kernel");
 }
 
 int tacex_fem_reset_envs(tacex_fem_ctx* c, const int32_t* env_ids, int num_reset, const double* positions, double* x, double* v,
@@ -1191,6 +1242,10 @@ int tacex_fem_ball_reset_envs(tacex_fem_ctx* c, const int32_t* env_ids, int num_
   if (c->ball.kinematic && ws && c->ball_last_ws == ws && c->ball_last_B == B)
     hipLaunchKernelGGL(fem_reset_envs_kernel, dim3(num_reset), dim3(256), 0, (hipStream_t)stream, env_ids, static_cast<const double*>(nullptr), q0,
                        ball_qlast(c, ws, B), qv, static_cast<double*>(nullptr), static_cast<double*>(nullptr), 4, B);  // (qv: zeroed again)
+  // the env's friction reference of tacex_fem_ball_contact_forces: none until it steps (the rows of the other envs stay valid)
+  if (ws && c->ball_step_ws == ws && c->ball_step_B == B)
+    hipLaunchKernelGGL(fem_ball_clear_friction_ref_kernel, dim3(num_reset), dim3(64), 0, (hipStream_t)stream, env_ids,
+                       static_cast<double*>(ws) + ball_layout(c, B).q_prev, B);
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? 0 : fail_hip(e, "fem_reset_envs_kernel(ball)");
 }

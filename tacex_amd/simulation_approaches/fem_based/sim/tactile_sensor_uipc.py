@@ -255,16 +255,23 @@ class VisionTactileSensorUIPC:
     def contact_wrench(self, per_vertex: bool = False, friction: bool | None = None):
         """`UipcSim.contact_forces` of the current state expressed in the CAMERA frame: the torque's reference point is the camera
         position of every env, vectors are rotated with the camera rotation, the centre of pressure becomes a camera-frame point.
-        Forces act ON the pad (`UipcSim.contact_forces`).  A handful of (num_envs, 3) torch ops behind the one launch, no host round trip."""
-        from ....uipc.uipc_sim import ContactForces
+        Forces act ON the pad (`UipcSim.contact_forces`).  A handful of (num_envs, 3) torch ops behind the one launch, no host round trip.
+        On a scene with an affine body the result is a `BallContactForces`: its pad-side vectors, the body's generalised force rows and
+        the ground's forces are rotated alike."""
+        from ....uipc.uipc_sim import BallContactForces, ContactForces
 
         w = self.uipc_sim.contact_forces(ref_points=self.cam_pos_w, per_vertex=per_vertex, friction=friction)
         Rt = self.cam_rot_inv.transpose(-1, -2)  # (the product transform_world_to_camera_frame takes points to the camera frame with)
         rec = w.record.clone()
-        for k in (0, 3, 6):
+        ball = isinstance(w, BallContactForces)
+        # a scene with an affine body: the body's four generalised-force rows and the ground's forces on both bodies are vectors too
+        for k in (0, 3, 6) + ((20, 23, 26, 29, 32, 38) if ball else ()):
             rec[:, k:k + 3] = torch.matmul(w.record[:, None, k:k + 3], Rt)[:, 0]
         rec[:, 12:15] = torch.matmul((w.record[:, 12:15] - self.cam_pos_w)[:, None], Rt)[:, 0]
         vf = None if w.vertex_forces is None else torch.matmul(w.vertex_forces, Rt)
+        if ball:  # (the body rows c_k rotate like vectors; p becomes a camera-frame point: body_torque stays sum c_k x G_k)
+            q = torch.cat([((w.q[:, 0] - self.cam_pos_w)[:, None] @ Rt), w.q[:, 1:4] @ Rt], 1)
+            return BallContactForces(rec, vf, q)
         return ContactForces(rec, vf)
 
     def get_surface_vertices_camera(self) -> torch.Tensor:

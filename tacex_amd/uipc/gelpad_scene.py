@@ -245,6 +245,11 @@ class FemBallScene:
         self.iters_max = None
         self._pending = None
 
+    def contact_forces(self, **kw):
+        """`UipcSim.contact_forces` of the scene's sim: `BallContactForces` (pad <- body wrench, the body's generalised force, the ground's
+        force on both; world frame)."""
+        return self.sim.contact_forces(**kw)
+
     def camera_pose(self, cam_pos_pad=(0.008, 0.012625, -0.024)):
         """(position, ROS quaternion wxyz) of the sensor camera in this scene's world frame, given its position in the upright pad's frame."""
         p = np.asarray(cam_pos_pad, np.float64) * np.array([1.0, -1.0, -1.0]) + self.pad_offset

@@ -181,6 +181,107 @@ class ContactForces:
         return self.record[:, 15]
 
 
+@dataclass
+class BallContactForces:
+    """Contact forces of a scene with an affine body per env (`UipcSim.contact_forces`): views into the one (num_envs, 44) float64
+    `record` of `tacex_fem_ball_contact_forces`.  Forces act ON THE BODY NAMED FIRST, in newtons, in the frame the record is expressed in
+    (world; the sensor's `contact_wrench()`: camera).  The pad side carries `ContactForces`' property names where a counterpart exists."""
+
+    record: torch.Tensor
+    vertex_forces: torch.Tensor | None = None
+    """(num_envs, V, 3) total contact force of every pad vertex (pairs, their friction, ground, ground friction), or None."""
+    q: torch.Tensor | None = None
+    """(num_envs, 4, 3) the body rows the record was evaluated at, in the record's frame (`body_torque` reads c_1..c_3)."""
+
+    @property
+    def normal_force(self) -> torch.Tensor:
+        """(num_envs, 3) pad <- body: sum of the pairs' barrier forces on the pad rows."""
+        return self.record[:, 0:3]
+
+    @property
+    def friction_force(self) -> torch.Tensor:
+        """(num_envs, 3) pad <- body: sum of the pair contacts' lagged friction on the pad rows (zeros when friction was not evaluated)."""
+        return self.record[:, 3:6]
+
+    @property
+    def force(self) -> torch.Tensor:
+        """(num_envs, 3) pad <- body: normal + friction."""
+        return self.record[:, 0:3] + self.record[:, 3:6]
+
+    @property
+    def torque(self) -> torch.Tensor:
+        """(num_envs, 3) of `force` on the pad, sum (x_row - ref) x f_row about the env's reference point."""
+        return self.record[:, 6:9]
+
+    @property
+    def normal_magnitude(self) -> torch.Tensor:
+        """(num_envs,) sum of the normal-force magnitudes lam of the active pairs."""
+        return self.record[:, 9]
+
+    @property
+    def num_contacts(self) -> torch.Tensor:
+        """(num_envs,) number of active pairs (float64, exact); `num_pairs_by_kind` splits it."""
+        return self.record[:, 10]
+
+    @property
+    def flags(self) -> torch.Tensor:
+        """(num_envs,) 0, or 16: a candidate list of the env overflowed (the sums miss contacts)."""
+        return self.record[:, 11]
+
+    @property
+    def centre_of_pressure(self) -> torch.Tensor:
+        """(num_envs, 3) normal-force weighted mean of the pairs' pad-side closest points (the reference point without contact)."""
+        return self.record[:, 12:15]
+
+    @property
+    def min_gap(self) -> torch.Tensor:
+        """(num_envs,) smallest distance over the active pairs (+inf: none)."""
+        return self.record[:, 15]
+
+    @property
+    def num_pairs_by_kind(self) -> torch.Tensor:
+        """(num_envs, 3) active pairs: pad vertex x body triangle | body vertex x pad triangle | pad edge x body edge."""
+        return self.record[:, 16:19]
+
+    @property
+    def body_generalized_force(self) -> torch.Tensor:
+        """(num_envs, 4, 3) contact force on the body's rows (p, c_1, c_2, c_3): pairs + their friction + ground + ground friction."""
+        return self.record[:, 20:32].reshape(-1, 4, 3)
+
+    @property
+    def body_force(self) -> torch.Tensor:
+        """(num_envs, 3) net contact force on the body (the p row of `body_generalized_force`)."""
+        return self.record[:, 20:23]
+
+    @property
+    def body_torque(self) -> torch.Tensor:
+        """(num_envs, 3) net contact torque on the body about its origin p: sum_k c_k x G_k over the rows c_k (a force f at the surface
+        point p + sum_k X_k c_k adds X_k f to row c_k and sum_k X_k c_k x f to the torque).  A few torch ops on the record and `q`."""
+        if self.q is None:
+            raise ValueError("body_torque needs the body rows q the record was evaluated at")
+        return torch.cross(self.q[:, 1:4], self.record[:, 23:32].reshape(-1, 3, 3), dim=-1).sum(1)
+
+    @property
+    def ground_force_on_body(self) -> torch.Tensor:
+        """(num_envs, 3) body <- ground: friction (x, y) and normal (z) in the world frame."""
+        return self.record[:, 32:35]
+
+    @property
+    def ground_force_on_pad(self) -> torch.Tensor:
+        """(num_envs, 3) pad <- ground."""
+        return self.record[:, 38:41]
+
+    @property
+    def ground_contacts_body(self) -> torch.Tensor:
+        """(num_envs, 3) sum lam, count and smallest gap (+inf: none) of the body's ground contacts."""
+        return self.record[:, 35:38]
+
+    @property
+    def ground_contacts_pad(self) -> torch.Tensor:
+        """(num_envs, 2) count and smallest gap (+inf: none) of the pad's ground contacts."""
+        return self.record[:, 41:43]
+
+
 class UipcSim:
     cfg: UipcSimCfg
 
@@ -274,6 +375,7 @@ class UipcSim:
         self.qv = torch.zeros_like(self.q)
         self._body_Y = torch.from_numpy(np.concatenate([np.ones((len(verts), 1)), verts], 1)).to(dev)
         self._ball_ws = torch.empty(self._lib.tacex_fem_ball_workspace_bytes(self._handle, B), dtype=torch.uint8, device=dev)
+        self._ball_friction_ref = False  # no step has run with this workspace yet (contact_forces)
 
     def body_points(self, q=None) -> torch.Tensor:
         """(num_envs, nv, 3) world positions of the affine body's surface vertices."""
@@ -535,7 +637,46 @@ class UipcSim:
         _lib.check(self._lib.tacex_fem_contact_gaps(self._handle, _lib.ptr(x), _lib.ptr(gaps), x.shape[0], self._stream()), "tacex_fem_contact_gaps")
         return gaps
 
-    def contact_forces(self, x=None, ref_points=None, per_vertex: bool = False, friction: bool | None = None) -> ContactForces:
+    def _ball_contact_forces(self, x, q, ref_points, per_vertex, friction, x_prev=None, q_prev=None) -> BallContactForces:
+        """`contact_forces` of a scene with an affine body (`tacex_fem_ball_contact_forces`).  x_prev / q_prev: explicit previous states in
+        place of the workspace's rows (the library's parity entry, like `ball_terms`; not part of the public method)."""
+        self.wait_for_step()  # (a side-stream step writes x, q AND the workspace rows the friction part reads)
+        V = self._obj.num_verts
+        x = self.x if x is None else x.to(self.device, torch.float64).contiguous()
+        if x.dim() != 3 or x.shape[0] > self.num_envs or x.shape[1] != V or x.shape[2] != 3:
+            raise ValueError(f"contact_forces: x must be (<= {self.num_envs}, {V}, 3), got {tuple(x.shape)}")
+        B = x.shape[0]
+        q = self.q[:B] if q is None else q.to(self.device, torch.float64).contiguous()
+        if tuple(q.shape) != (B, 4, 3):
+            raise ValueError(f"contact_forces: q must be ({B}, 4, 3) like x's envs, got {tuple(q.shape)}")
+        if (x_prev is None) != (q_prev is None):
+            raise ValueError("contact_forces: x_prev and q_prev go together")
+        c = self.cfg.contact
+        mu_on = bool(c.enable_friction) and float(c.default_friction_ratio) > 0.0
+        explicit = x_prev is not None
+        can = explicit or bool(self._ball_friction_ref and B == self.num_envs)
+        if friction is None:
+            friction = mu_on and can
+        elif friction and mu_on and not can:
+            raise ValueError("contact_forces(friction=True): friction is reported after a step(), for all num_envs envs (its lag is the state "
+                             "that step started from, kept in the step's workspace)")
+        if explicit:
+            x_prev = x_prev.to(self.device, torch.float64).contiguous()
+            q_prev = q_prev.to(self.device, torch.float64).contiguous()
+            if tuple(x_prev.shape) != (B, V, 3) or tuple(q_prev.shape) != (B, 4, 3):
+                raise ValueError(f"contact_forces: x_prev / q_prev must be ({B}, {V}, 3) / ({B}, 4, 3)")
+        ref = None if ref_points is None else ref_points.to(self.device, torch.float64).reshape(B, 3).contiguous()
+        rec = torch.empty((B, 44), dtype=torch.float64, device=self.device)
+        vf = torch.empty((B, V, 3), dtype=torch.float64, device=self.device) if per_vertex else None
+        with torch.cuda.device(self.device):
+            rc = self._lib.tacex_fem_ball_contact_forces(self._handle, _lib.ptr(x), _lib.ptr(q), _lib.ptr(self._ball_ws) if friction else 0,
+                                                         _lib.ptr(x_prev) if friction else 0, _lib.ptr(q_prev) if friction else 0, _lib.ptr(ref),
+                                                         1 if friction else 0, _lib.ptr(rec), _lib.ptr(vf), B, self._stream())
+        _lib.check(rc, "tacex_fem_ball_contact_forces")
+        return BallContactForces(rec, vf, q)
+
+    def contact_forces(self, x=None, q=None, ref_points=None, per_vertex: bool = False,
+                       friction: bool | None = None) -> ContactForces | BallContactForces:
         """Contact forces of the gelpad at `x` (None: the current state) and their net wrench per env, from the solver's own barrier
         and friction terms (`tacex_fem_contact_forces`: one launch on the current stream, no host round trip).
 
@@ -549,9 +690,18 @@ class UipcSim:
         start positions against the indenter where it stood then, sliding measured from there - evaluated at `x`; only the indenter's
         translation enters it (`set_contact_indenters`), and moving an indenter after that step changes the normal part only.  An env reset
         since (`reset(env_ids)`) reports zero friction until it steps; its normal part is the barrier's at the reset state.
-        Without contact indenters: zeros and +inf gaps, nothing is launched.  Scenes with an affine body are not covered."""
+        Without contact indenters: zeros and +inf gaps, nothing is launched.
+
+        A scene with an AFFINE BODY returns `BallContactForces` (`tacex_fem_ball_contact_forces`, one launch): the pad <- body wrench under
+        the names above, the body's generalised force, the ground's force on both.  `q` (num_envs, 4, 3): the body rows (None: current).
+        Friction there is the lagged friction of the pairs and ground contacts of the state the LAST step started from (kept in the step's
+        workspace), evaluated at (x, q); True before any step or with fewer envs raises ValueError.  A kinematic body's rows slide from the
+        pose that step measured the body's motion from, as in the step.  An env reset since
+        reports zero friction until it steps.  Results agree to round-off between runs and batches, not bit for bit."""
         if getattr(self, "_body", None) is not None:
-            raise NotImplementedError("contact_forces covers prescribed indenters; the pair contacts of a scene with an affine body are not reported")
+            return self._ball_contact_forces(x, q, ref_points, per_vertex, friction)
+        if q is not None:
+            raise ValueError("contact_forces: q belongs to a scene with an affine body")
         self.wait_for_step()  # (a side-stream step writes self.x AND the workspace rows the friction part reads)
         x = self.x if x is None else x.to(self.device, torch.float64).contiguous()
         if x.dim() != 3 or x.shape[0] > self.num_envs or x.shape[1] != self._obj.num_verts or x.shape[2] != 3:
@@ -824,6 +974,7 @@ class UipcSim:
                     float(self.cfg.newton.velocity_tol), float(self.cfg.newton.transrate_tol), int(self.cfg.linear_system.max_iter),
                     float(self.cfg.linear_system.tol_rate), int(self.cfg.line_search.max_iter), self._stream())
             _lib.check(rc, "tacex_fem_ball_step")
+            self._ball_friction_ref = True  # the ball workspace now holds this step's start state (contact_forces)
             return self.x
         if self._precond_dirty:
             self.refresh_preconditioner()
