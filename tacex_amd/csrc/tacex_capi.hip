@@ -778,6 +778,12 @@ static LevelPlan plan_band_levels(const tacex_taxim_ctx* c, const Pass& p, const
   return lp;
 }
 
+// TACEX_BAND_LEAN: 1 (default) = lean loads and no stores for skipped bands in the matrix-core levels (BlurArgs::lean), 0 = full loads
+static bool band_lean() {
+  static const bool v = !(getenv("TACEX_BAND_LEAN") && atoi(getenv("TACEX_BAND_LEAN")) == 0);
+  return v;
+}
+
 // The band levels of a pass, chunk by chunk: fork onto the level streams, the deferred depth pass, the early item order, the join.
 // *out: what the last level wrote (nullptr without band levels); *order_done: the tail's item order has been issued.
 static int run_band_levels(tacex_taxim_ctx* c, const Pass& p, const PassState& s, const LevelPlan& lp, const float** out, bool* order_done) {
@@ -828,9 +834,25 @@ static int run_band_levels(tacex_taxim_ctx* c, const Pass& p, const PassState& s
     for (int l = 0; l < s.n_band; ++l) {
       const bool last = l == c->n_levels - 1;
       float* dst = (last && p.z_out) ? p.z_out : s.z[l & 1];
+      // LEAN LEVELS (TACEX_BAND_LEAN=0: off): a matrix-core level of a zero gel map that has the contact rectangle loads the height map
+      // and its input inside the (grown) rectangle only.  It may also leave its skipped bands unwritten when EVERY reader of dst is
+      // range-aware - the level buffers then hold stale data there, see PassLayout:
+      //  - the next band level, if it is a lean matrix-core level too: its V-pass loads row yy only for yy in [lo - G, hi + G], G = this
+      //    level's input growth g + its radius R, and this level skips a band [b, b + 15] only if b - R > hi + g or b + 15 + R < lo - g:
+      //    no such yy lies in a skipped band;
+      //  - the streaming tail, handed the rows: it loads zin only on rows in [lo - band_grow, hi + band_grow] (issue_row), band_grow =
+      //    g + R of the last band level: the same two inequalities, so every row it loads lies in a band that was stored.
+      // Never when dst is the caller's (z_out, mask_out: last level of the pyramid), nor ahead of the tiled tail, shade_kernel or a
+      // VALU / generic level: they read every row.
+      const bool lean = band_lean() && q.rows && c->levels[l].gel_zero;
+      bool unread = lean && dst != p.z_out && !last;
+      if (unread && l + 1 < s.n_band)
+        unread = c->levels[l + 1].gel_zero && blur_level_single_kernel(c->levels[l + 1], false, c->H, c->W);
+      else if (unread)
+        unread = s.stream_tail && stream_tail_range_aware(c->levels);
       StageTimer t(c, cst, 1 + l);
       HIP_TRY(run_blur_level(c->levels[l], src ? src + b0 * npix : nullptr, q.hm, c->gel_dev, s.sa + b0, s.sb + b0, s.pd + b0, dst + b0 * npix,
-                             s.tmp, last ? q.mask_out : nullptr, q.B, c->H, c->W, c->contact_scale, last ? 0 : 1, l == 0, cst, q.rows, grow, grow_x),
+                             s.tmp, last ? q.mask_out : nullptr, q.B, c->H, c->W, c->contact_scale, last ? 0 : 1, l == 0, cst, q.rows, grow, grow_x, lean, unread),
               "blur level");
       grow += (c->levels[l].kh - 1) / 2;
       grow_x += (c->levels[l].kw - 1) / 2;

@@ -57,7 +57,8 @@ bool blur_level_single_kernel(const LevelDesc& lv, bool first, int H, int W);  /
 hipError_t run_blur_level(const LevelDesc& lv, const float* src, const float* hm, const float* gel,
                           const float* sa, const float* sb, const float* pd, float* dst, float* tmp,
                           uint8_t* mask_out, int B, int H, int W, float contact_scale, int restore,
-                          bool first, hipStream_t st, const int* rows_ext = nullptr, int ext_grow = 0, int ext_grow_x = 0);
+                          bool first, hipStream_t st, const int* rows_ext = nullptr, int ext_grow = 0, int ext_grow_x = 0, bool lean = false,
+                          bool zero_bands_unread = false);
 bool frame_rows_supported(int H, int W);
 hipError_t run_fill_rows(int* rows, int B, int H, int W, hipStream_t st);
 hipError_t run_frame_rows(const float* in, bool from_depth, float* hm_out, float* fmin, float* indent, uint8_t* cam_u8,
@@ -157,6 +158,8 @@ struct StreamPlan {
 int stream_obs_lds_floats();
 int stream_obs_max_cols();
 bool stream_supported(int n_fused, int k0, int H, int W);
+// true: a streaming tail handed the contact rows loads its input `zin` on the rows within ext_grow of them only (issue_row)
+bool stream_tail_range_aware(const LevelDesc* lv);
 bool stream_geometry(int n_fused, int k0, int W, int* nstrips, int* strip_w, int* lv_nstrips, int* lv_strip_w);
 int stream_segments(int B, int nstrips, int H, int warm_rows, int waves_per_simd);
 int stream_warm_rows(int n_fused, int k0, bool levels_kernel);

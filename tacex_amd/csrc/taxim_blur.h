@@ -26,6 +26,10 @@ struct BlurArgs {
                         // zero-band and zero-block skipping)
   int ext_grow;         // rows by which the non-zero range of THIS level's input has grown (sum of the previous levels' radii)
   int ext_grow_x;       // columns, likewise
+  int lean;             // MFMA kernel, zero gel map and rows_ext only: lanes whose pixels lie outside the contact rectangle (grown by
+                        // ext_grow / ext_grow_x for a later level's input) fetch nothing and use the +0.0f / "no contact" they would have read
+  int zero_bands_unread;  // with `lean`: every reader of dst knows the skipped bands from rows_ext and never loads them - a skipped band
+                          // returns without storing its zeros (dst keeps whatever it held there)
 };
 
 bool mfma_supported(int k, bool first, int H, int W);

@@ -13,6 +13,9 @@ inline size_t taxim_align(size_t bytes) { return (bytes + 255) / 256 * 256; }
 // with TACEX_FLAG_NO_SHIFT) | contact rows / columns (B,4 int32) of the library's own minimum pass.
 // A pass of B frames walked in chunks lays every chunk out with PassLayout(n), n <= B, on the same base; `rows` is written once for the
 // whole batch with PassLayout(B): it lies behind everything a chunk lays out because every term grows with the frame count.
+// Z ping / Z pong are NOT complete images: a lean band level (BlurArgs::zero_bands_unread) leaves the 16-row bands it knows to be zero
+// unwritten, so they hold stale data of earlier passes.  Every reader of these two buffers redirects its loads by the same contact
+// ranges (the lean V-pass of the next level, issue_row of the streaming tail) and never sees them; a new reader must do the same.
 struct PassLayout {
   size_t z[2], tmp, shift_a, shift_b, pdepth, rows, total;
   PassLayout(int H, int W, int B) {

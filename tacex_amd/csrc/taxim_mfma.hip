@@ -42,8 +42,17 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 #define TACEX_MFMA_H_CONSEC 0
 #endif
 
-template <int K, bool FIRST, int NTILE, bool GZ>
+// LEAN (GZ with rows_ext only, BlurArgs::lean): the loads of the V-pass window and of the masked restore go through raw buffer
+// descriptors of the frame, and a lane whose four pixels cannot matter - outside the contact rectangle [lo, hi] x [clo, chi] of
+// frame_rows_kernel for the height map, outside the rectangle grown by ext_grow / ext_grow_x for the previous level - gets an
+// out-of-range offset: the load returns 0 without touching memory.  That 0 IS the value the full load finds for a previous level
+// (stored +0.0f); for the height map the operand J = min(S, 0) = +0.0f is selected / the mask bit cleared by the same predicate
+// (S >= 0 outside the rectangle: it comes from the same float32 expression).  No branch encloses a load, an LDS read or an MFMA:
+// the instruction stream is the one of the full kernel with buffer_load in place of global_load.
+template <int K, bool FIRST, int NTILE, bool GZ, bool LEAN>
 __global__ __launch_bounds__(640) void blur_mfma_kernel(BlurArgs a) {
+  static_assert(GZ || !LEAN, "the lean loads need J = min(S, 0)");
+  constexpr unsigned kNoLoad = 0x80000000u;  // buffer offset beyond every frame: the range check drops the load, the lane reads 0
   constexpr int TH = 16 * NTILE;
   constexpr int R = (K - 1) / 2, RA = (R + 7) & ~7, WIN = 16 + 2 * RA, KS = WIN / 4;
   constexpr int KU = KS + 4 * (NTILE - 1);  // k-steps over the union window of the band's tiles
@@ -73,9 +82,11 @@ __global__ __launch_bounds__(640) void blur_mfma_kernel(BlurArgs a) {
     // [lo, hi] (frame_rows_kernel), and level l's input only within ext_grow rows of them.  A band whose whole window lies
     // outside has an exactly zero blur and no contact pixel to restore: store zeros, read nothing.  (Reflect padding cannot
     // bring a non-zero row in: a mirrored row index -k maps to row k, which the window contains as well.)
-    if (a.rows_ext != nullptr) {
+    if (LEAN || a.rows_ext != nullptr) {
       const int lo = a.rows_ext[4 * frame] - a.ext_grow, hi = a.rows_ext[4 * frame + 1] + a.ext_grow;
       if (by0 - R > hi || by0 + TH - 1 + R < lo) {
+        if constexpr (LEAN)
+          if (a.zero_bands_unread) return;  // no reader loads these rows (run_band_levels)
         const int w4 = W >> 2;
         for (int i = threadIdx.x; i < TH * w4; i += blockDim.x) {
           const int r = i / w4, c = i - r * w4;
@@ -100,9 +111,18 @@ __global__ __launch_bounds__(640) void blur_mfma_kernel(BlurArgs a) {
 #ifndef TACEX_MFMA_BLOCK_SKIP_MIN_K
 #define TACEX_MFMA_BLOCK_SKIP_MIN_K 0  // (A/B hook: levels below this kernel size are compiled without the block tests)
 #endif
+  // LEAN: the frame's contact rectangle and the frame-sized buffer descriptors (wave-uniform: kernel arguments and the block index)
+  int ct_lo = 0, ct_hi = 0, ct_clo = 0, ct_chi = 0;
+  __amdgpu_buffer_rsrc_t src_rs, hm_rs;
+  if constexpr (LEAN) {
+    ct_lo = a.rows_ext[4 * frame]; ct_hi = a.rows_ext[4 * frame + 1];
+    ct_clo = a.rows_ext[4 * frame + 2]; ct_chi = a.rows_ext[4 * frame + 3];
+    src_rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(src), 0, H * W * (int)sizeof(float), 0x00020000);
+    hm_rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(hm), 0, H * W * (int)sizeof(float), 0x00020000);
+  }
   bool v_need = true, h_need = true;
   if constexpr (GZ && K >= TACEX_MFMA_BLOCK_SKIP_MIN_K) {
-    if (a.rows_ext != nullptr) {
+    if (LEAN || a.rows_ext != nullptr) {
       const int in_lo = a.rows_ext[4 * frame + 2] - a.ext_grow_x, in_hi = a.rows_ext[4 * frame + 3] + a.ext_grow_x;
       v_need = !(c0 + 63 < in_lo || c0 > in_hi);
       h_need = !(c0 + 63 < in_lo - R || c0 > in_hi + R);
@@ -127,6 +147,10 @@ __global__ __launch_bounds__(640) void blur_mfma_kernel(BlurArgs a) {
     const int rb = by0 - RA + g;
     const unsigned coff = (unsigned)(c0 + 4 * li);
     v4f xb[2][CH], gb[FIRST ? 2 : 1][FIRST ? CH : 1];
+    // LEAN: rows / columns in which this level's input can be non-zero; `vin`: the lane's window row of a k-step lies inside
+    const int vr_lo = ct_lo - a.ext_grow, vr_hi = ct_hi + a.ext_grow;
+    const bool vcol = LEAN & ((int)coff + 3 >= ct_clo - a.ext_grow_x) & ((int)coff <= ct_chi + a.ext_grow_x);  // (&: no short-circuit branches)
+    bool vin[2][(LEAN && FIRST) ? CH : 1];
     auto issue = [&](auto chunk_c) {
       constexpr int chunk = decltype(chunk_c)::value;
       static_for<0, CH>([&](auto cc) {
@@ -134,7 +158,13 @@ __global__ __launch_bounds__(640) void blur_mfma_kernel(BlurArgs a) {
         int yy = reflect_idx(rb + 4 * (chunk * CH + c), H);
         yy = yy < 0 ? 0 : (yy >= H ? H - 1 : yy);  // zero-weight rows beyond the reflect range: any finite data
         const unsigned off = (unsigned)yy * (unsigned)W + coff;
-        xb[chunk & 1][c] = *reinterpret_cast<const v4f*>(src + off);
+        if constexpr (LEAN) {
+          const bool in = vcol & (yy >= vr_lo) & (yy <= vr_hi);
+          xb[chunk & 1][c] = __builtin_bit_cast(v4f, __builtin_amdgcn_raw_buffer_load_b128(src_rs, in ? off * 4u : kNoLoad, 0, 0));
+          if constexpr (FIRST) vin[chunk & 1][c] = in;
+        } else {
+          xb[chunk & 1][c] = *reinterpret_cast<const v4f*>(src + off);
+        }
         if constexpr (FIRST) gb[chunk & 1][c] = GZ ? (v4f)(0.0f) : *reinterpret_cast<const v4f*>(gel + off);  // GZ: gel == 0 everywhere
       });
     };
@@ -153,6 +183,10 @@ __global__ __launch_bounds__(640) void blur_mfma_kernel(BlurArgs a) {
           const v4f gq = gb[chunk & 1][c];  // inline-asm fmin_raw: the hazard recognizer cannot see asm feeding an MFMA
           x.x = fminf((x.x - sa) - sb, gq.x); x.y = fminf((x.y - sa) - sb, gq.y);
           x.z = fminf((x.z - sa) - sb, gq.z); x.w = fminf((x.w - sa) - sb, gq.w);
+          if constexpr (LEAN) {  // nothing was loaded: J = +0.0f, what min(S, 0) gives outside the contact rectangle
+            const bool in = vin[chunk & 1][c];
+            x.x = in ? x.x : 0.0f; x.y = in ? x.y : 0.0f; x.z = in ? x.z : 0.0f; x.w = in ? x.w : 0.0f;
+          }
         }
         static_for<0, NTILE>([&](auto tc) {
           constexpr int t = decltype(tc)::value;
@@ -221,9 +255,20 @@ __global__ __launch_bounds__(640) void blur_mfma_kernel(BlurArgs a) {
       const int hrow = TACEX_MFMA_H_CONSEC ? li : mfma_h_row(li);  // tile row of this lane (see mfma_h_window_col)
       const size_t p0 = (size_t)(by0 + 16 * t + hrow) * W + c0 + 4 * g;
       v4f hv[4], gv[4];
+      // LEAN: only a lane whose row lies on the contact rows and whose four columns meet the contact columns can restore a pixel
+      const int orow = by0 + 16 * t + hrow;
+      const bool hrow_in = LEAN & (orow >= ct_lo) & (orow <= ct_hi);
+      bool hin[4];
 #pragma unroll
       for (int n = 0; n < 4; ++n) {
-        hv[n] = *reinterpret_cast<const v4f*>(hm + p0 + 16 * n);
+        if constexpr (LEAN) {
+          const int oc = c0 + 4 * g + 16 * n;
+          hin[n] = hrow_in & (oc + 3 >= ct_clo) & (oc <= ct_chi);
+          hv[n] = __builtin_bit_cast(v4f, __builtin_amdgcn_raw_buffer_load_b128(hm_rs, hin[n] ? (unsigned)(p0 + 16 * n) * 4u : kNoLoad, 0, 0));
+        } else {
+          hin[n] = true;
+          hv[n] = *reinterpret_cast<const v4f*>(hm + p0 + 16 * n);
+        }
         gv[n] = GZ ? (v4f)(0.0f) : *reinterpret_cast<const v4f*>(gel + p0 + 16 * n);
       }
       if constexpr (TACEX_MFMA_H_CONSEC) {
@@ -265,7 +310,7 @@ __global__ __launch_bounds__(640) void blur_mfma_kernel(BlurArgs a) {
         for (int k = 0; k < 4; ++k) {
           const float S = (hv[n][k] - sa) - sb;
           const float J = fminf(S, gv[n][k]);
-          const bool M = ((J - gv[n][k]) < thr) && (S < 0.0f);  // TT:457-461
+          const bool M = (((J - gv[n][k]) < thr) && (S < 0.0f)) & hin[n];  // TT:457-461
           o[k] = (a.restore && M) ? J : acc[n][k];              // TT:467
           mk[k] = M ? 1 : 0;
         }
@@ -276,7 +321,7 @@ __global__ __launch_bounds__(640) void blur_mfma_kernel(BlurArgs a) {
   }
 }
 
-template <int K, bool FIRST, int NTILE, bool GZ>
+template <int K, bool FIRST, int NTILE, bool GZ, bool LEAN = false>
 static hipError_t launch_mfma_tiles(BlurArgs a, int row0, int nbands, hipStream_t st) {
   constexpr int TH = 16 * NTILE, R = (K - 1) / 2, RA = (R + 7) & ~7;
   a.row0 = row0;
@@ -286,7 +331,7 @@ static hipError_t launch_mfma_tiles(BlurArgs a, int row0, int nbands, hipStream_
   if (((a.pitch >> 2) & 1) == 0) a.pitch += 4;
   static const size_t lds_pad = getenv("TACEX_MFMA_LDS_PAD") ? (size_t)atoi(getenv("TACEX_MFMA_LDS_PAD")) * 1024 : 0;  // occupancy A/B hook
   const size_t lds = (size_t)TH * a.pitch * sizeof(float) + lds_pad;
-  auto kern = blur_mfma_kernel<K, FIRST, NTILE, GZ>;
+  auto kern = blur_mfma_kernel<K, FIRST, NTILE, GZ, LEAN>;
   static size_t granted[64] = {};
   if (hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), lds, granted); e != hipSuccess) return e;
   hipLaunchKernelGGL(kern, dim3(nbands * a.B), dim3(a.W), lds, st, a);
@@ -306,9 +351,11 @@ template <int K, bool FIRST>
 static hipError_t launch_mfma(const BlurArgs& a, hipStream_t st) {
   constexpr int NT = K == 117 ? TACEX_MFMA_NT117 : (K == 61 ? TACEX_MFMA_NT61 : 1);
   if (NT > 1 && a.H % (16 * NT) == 0 && a.W > 320) {  // (taller bands only where the window is many times the band: the 640-wide levels)
+    if (a.gel == nullptr && a.lean && a.rows_ext) return launch_mfma_tiles<K, FIRST, NT, true, true>(a, 0, a.H / (16 * NT), st);
     if (a.gel == nullptr) return launch_mfma_tiles<K, FIRST, NT, true>(a, 0, a.H / (16 * NT), st);
     return launch_mfma_tiles<K, FIRST, NT, false>(a, 0, a.H / (16 * NT), st);
   }
+  if (a.gel == nullptr && a.lean && a.rows_ext) return launch_mfma_tiles<K, FIRST, 1, true, true>(a, 0, a.H / 16, st);
   if (a.gel == nullptr) return launch_mfma_tiles<K, FIRST, 1, true>(a, 0, a.H / 16, st);
   return launch_mfma_tiles<K, FIRST, 1, false>(a, 0, a.H / 16, st);
 }

@@ -1339,6 +1339,14 @@ hipError_t run_stream_order(const LevelDesc* lv, int n_levels, int n_fused, cons
   return e;
 }
 
+bool stream_tail_range_aware(const LevelDesc* lv) {
+#ifdef TACEX_STREAM_HM_ALWAYS
+  return false;
+#else
+  return lv[0].gel_zero;
+#endif
+}
+
 hipError_t run_stream_tail(const LevelDesc* lv, int n_levels, int n_fused, const float* zin, const float* hm, const float* gel,
                            const float* sa, const float* sb, const float* pd, const ShadeParams* sp, float* rgb, float* z_last,
                            int B, int H, int W, float contact_scale, const StreamPlan& plan, float* obs_part,
