@@ -148,6 +148,31 @@ int tacex_depth_from_deformed_mesh(const double* x_dev, int num_verts, const int
                                    float fx, float fy, float cx, float cy, float near_clip_m, float far_clip_m, float* depth_m_dev,
                                    int num_envs, int height, int width, void* stream);
 
+/* Contact TRACTION of the FEM gel pad as an image in the camera frame: the per-vertex contact force of tacex_fem_contact_forces /
+ * tacex_fem_ball_contact_forces (vertex_force_out_dev), divided by the barrier's vertex area and carried through the rasteriser of
+ * tacex_depth_from_deformed_mesh - pixel for pixel the image that function renders, so aligned with the height map and the tactile RGB
+ * frame it feeds.  Forces act ON the pad: [..., 2] is the normal pressure along the optical axis (negative where an indenter pushes the
+ * face towards the camera), [..., 0:2] the shear.
+ *   x_dev, num_verts, surf_ids_dev, num_surf_verts, tris_dev, num_tris, cam_pos_dev, cam_rot_inv_dev, intrinsics, clipping range: as in
+ *   tacex_depth_from_deformed_mesh (the index tables are not checked on the device);
+ *   vertex_force_dev (B, num_verts, 3) f64 world frame [N]; vertex_area_dev (num_verts,) f64 [m^2], one table for all envs
+ *   (UipcObject.surface_vertex_areas): vertex traction tw = f / area per component in f64, camera frame
+ *   tc[i] = (Rinv[i][0] tw[0] + Rinv[i][1] tw[1]) + Rinv[i][2] tw[2] in f64, rounded once to f32; zero where area <= 0;
+ *   fragments are that function's; a pixel takes the fragment with the smallest (bits of z, triangle index) - the index decides between
+ *   the equal depths two triangles give at a pixel centre on their shared edge, so the image does not depend on the order the workgroup
+ *   happens to list its triangles in - and interpolates perspective-correctly with f32 operations, separately rounded:
+ *   w_k = (l_k * iz_k) * z, t[i] = (w_0 t_0[i] + w_1 t_1[i]) + w_2 t_2[i];
+ *   traction_dev (B,H,W,3) f32 out [Pa], 0 where no fragment lies inside the clipping range; depth_m_dev (B,H,W) f32 out or NULL:
+ *   bit-equal to tacex_depth_from_deformed_mesh on the same arguments.
+ *   Vertex tractions of up to 1536 surface vertices are formed once per workgroup in LDS; larger surfaces form them per pixel (same image).
+ * Returns 2 (no GPU call) on a null buffer other than depth_m_dev, a count <= 0, Vs > num_verts or a clipping range that is not
+ * 0 <= near < far. */
+int tacex_traction_image_from_deformed_mesh(const double* x_dev, int num_verts, const int32_t* surf_ids_dev, int num_surf_verts,
+                                            const int32_t* tris_dev, int num_tris, const double* vertex_force_dev,
+                                            const double* vertex_area_dev, const double* cam_pos_dev, const double* cam_rot_inv_dev,
+                                            float fx, float fy, float cx, float cy, float near_clip_m, float far_clip_m,
+                                            float* traction_dev, float* depth_m_dev, int num_envs, int height, int width, void* stream);
+
 /* Height-map SOURCE for the affine body that presses into the pad (ball_rolling_uipc.py:71-139): the same depth image, rendered from the
  * body's 12-unknown state - what the sensor camera sees of the object with the gel hidden, the input Taxim is built for
  * (ManiSkill-ViTac gen_rgb_image, tactile_sensor_sapienipc.py:424-457).

@@ -3,7 +3,7 @@ from .gelsight_sensor import GelSightSensor
 from .gelsight_sensor_cfg import GelSightSensorCfg
 from .gelsight_sensor_data import GelSightSensorData
 from .gelsight_sensor_group import GelSightSensorGroup
-from .height_map_source import AffineBodyDepthSource, FemSurfaceDepthSource, IndenterHeightMapSource, MeshDepthSource, MeshLibraryDepthSource
+from .height_map_source import AffineBodyDepthSource, FemSurfaceDepthSource, FemTractionImage, IndenterHeightMapSource, MeshDepthSource, MeshLibraryDepthSource
 
-__all__ = ["AffineBodyDepthSource", "GelSightSensor", "GelSightSensorCfg", "GelSightSensorData", "GelSightSensorGroup", "FemSurfaceDepthSource", "IndenterHeightMapSource", "MeshDepthSource",
+__all__ = ["AffineBodyDepthSource", "GelSightSensor", "GelSightSensorCfg", "GelSightSensorData", "GelSightSensorGroup", "FemSurfaceDepthSource", "FemTractionImage", "IndenterHeightMapSource", "MeshDepthSource",
            "MeshLibraryDepthSource"]

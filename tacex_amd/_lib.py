@@ -105,6 +105,8 @@ SIGNATURES = {
     "tacex_taxim_set_frame_rows": (_i, [_vp, _vp, _i]),
     "tacex_depth_from_mesh": (_i, [_vp, _vp, _i, _i, _vp, _vp, _f, _f, _f, _f, _f, _f, _vp, _vp, _i, _i, _i, _vp]),
     "tacex_depth_from_deformed_mesh": (_i, [_vp, _i, _vp, _i, _vp, _i, _vp, _vp, _f, _f, _f, _f, _f, _f, _vp, _i, _i, _i, _vp]),
+    "tacex_traction_image_from_deformed_mesh": (_i, [_vp, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _f, _f, _vp, _vp, _i, _i,
+                                                     _i, _vp]),
     "tacex_depth_from_affine_body": (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp, _f, _f, _f, _f, _f, _f, _vp, _i, _i, _i, _vp]),
     "tacex_depth_from_mesh_library": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _f, _f, _f, _f, _f, _f, _vp, _i, _i, _i, _vp]),
     "tacex_taxim_render": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _u, _vp]),

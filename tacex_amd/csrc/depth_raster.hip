@@ -352,9 +352,47 @@ __device__ __forceinline__ float4 project_deformed(const DeformArgs& a, const Ve
   return make_float4((a.fx * px) * iz + a.cx, (a.fy * py) * iz + a.cy, iz, pz > 1e-6f ? 1.0f : 0.0f);
 }
 
-template <class Verts>
-__global__ __launch_bounds__(kDeformBlock) void deformed_mesh_depth_kernel(DeformArgs a, Verts src) {
-  extern __shared__ float4 stage[];  // (min(Vs, kDeformStageMax),) when a.staged
+// ---- Contact traction of the pad's face as an image (tacex_traction_image_from_deformed_mesh) -----------------------------------------
+// fem_traction_image_kernel is deformed_mesh_depth_kernel<FemSurfaceVerts> with a per-vertex quantity carried through it: the body below
+// is the one copy of both (TRACTION is a compile-time switch; the depth kernels compile to what they were without it).
+//  - Vertex traction [Pa], camera frame, of rendered vertex sv with v = surf_ids[sv]: tw[i] = f[env][v][i] / area[v] (float64 division),
+//    tc[i] = (Rinv[i][0] tw[0] + Rinv[i][1] tw[1]) + Rinv[i][2] tw[2] in float64, rounded ONCE to float32; zero where area[v] <= 0.
+//    Up to kTractionStageMax vertices are computed once per workgroup into LDS (12 B each, behind the projections); above that they are
+//    computed per winner with the same function, so the image is the same.
+//  - Fragments are the depth kernel's.  The WINNER of a pixel is the fragment with the smallest (bits of z, triangle index t in tris):
+//    the list in LDS is filled through an atomicAdd, so fragments arrive in an order that differs from run to run, and at a pixel centre on
+//    an edge two triangles share both give a fragment, often with the same z.  The key (z bits, t) lives in registers next to each other.
+//  - After the walk the winner's l_k, 1/z_k and z are formed AGAIN with the expressions of the walk (same bits) and the traction is
+//    interpolated perspective-correctly: w_k = (l_k * iz[k]) * z, t[i] = (w0 t0[i] + w1 t1[i]) + w2 t2[i].  A pixel without a fragment
+//    gets 0, 0, 0.  Plain stores, no float atomics.
+constexpr int kTractionStageMax = 1536;  // vertices whose traction is staged in LDS: 1536 * (16 + 12) B = 42 KB, with the 16 KB triangle
+                                         // list under the 64 KB a launch gets without hipFuncSetAttribute (2048 * 28 B would not be)
+struct TractionArgs {
+  const double* force;  // (B,V,3) world frame [N]
+  const double* area;   // (V,) [m^2]
+  float* traction;      // (B,H,W,3) camera frame [Pa]
+  int tstaged;
+};
+struct NoTraction {};
+
+struct float3s { float x, y, z; };  // (12 B: float3 of the HIP headers is 12 B too, but carries operators this file does not use)
+
+__device__ __forceinline__ float3s vertex_traction(const double* fb, const double* area, const int* surf_ids, const double* R, int sv) {
+  const int v = surf_ids[sv];
+  const double ar = area[v];
+  float3s t{0.0f, 0.0f, 0.0f};
+  if (ar > 0.0) {
+    const double w0 = fb[(size_t)v * 3] / ar, w1 = fb[(size_t)v * 3 + 1] / ar, w2 = fb[(size_t)v * 3 + 2] / ar;
+    t.x = (float)((R[0] * w0 + R[1] * w1) + R[2] * w2);
+    t.y = (float)((R[3] * w0 + R[4] * w1) + R[5] * w2);
+    t.z = (float)((R[6] * w0 + R[7] * w1) + R[8] * w2);
+  }
+  return t;
+}
+
+template <class Verts, bool TRACTION, class Extra>
+__device__ __forceinline__ void deformed_raster(const DeformArgs& a, const Verts& src, const Extra& tr) {
+  extern __shared__ float4 stage[];  // (min(Vs, kDeformStageMax),) when a.staged [| (Vs,) float3s tractions when tr.tstaged]
   __shared__ TriSetup list[kDeformBlock];
   __shared__ float box[4][kDeformBlock / 64];
   __shared__ int count;
@@ -389,9 +427,24 @@ __global__ __launch_bounds__(kDeformBlock) void deformed_mesh_depth_kernel(Defor
   const bool tile_empty = !(floorf(maxx - 0.5f) >= (float)x0 && ceilf(minx - 0.5f) <= (float)(x1 - 1) &&
                             floorf(maxy - 0.5f) >= (float)y0 && ceilf(miny - 0.5f) <= (float)(y1 - 1));
 
+  const double* fb = nullptr;  // this env's vertex forces
+  float3s* tstage = nullptr;
+  if constexpr (TRACTION) {
+    fb = tr.force + (size_t)env * src.V * 3;
+    tstage = reinterpret_cast<float3s*>(stage + (a.staged ? a.Vs : 0));
+    // (visible to the interpolation at the end: every setup round below has a barrier)
+    if (tr.tstaged && !tile_empty)
+      for (int v = tid; v < a.Vs; v += kDeformBlock) tstage[v] = vertex_traction(fb, tr.area, src.surf_ids, R, v);
+  }
+
   unsigned zb[kDeformRows];
+  int tw[TRACTION ? kDeformRows : 1];  // the winner's triangle, -1: no fragment
 #pragma unroll
   for (int k = 0; k < kDeformRows; ++k) zb[k] = 0x7f800000u;  // +inf
+  if constexpr (TRACTION) {
+#pragma unroll
+    for (int k = 0; k < kDeformRows; ++k) tw[k] = -1;
+  }
   const int col = lane, row0 = wave;  // this thread's pixels: (y0 + row0 + 4k, x0 + col)
   const float pxc = (float)(x0 + col) + 0.5f;
   for (int base = tile_empty ? a.T : 0; base < a.T; base += kDeformBlock) {
@@ -418,6 +471,7 @@ __global__ __launch_bounds__(kDeformBlock) void deformed_mesh_depth_kernel(Defor
           for (int k = 0; k < 3; ++k) { e.sx[k] = sx[k]; e.sy[k] = sy[k]; e.iz[k] = iz[k]; }
           e.area = area; e.inv_area = 1.0f / area;
           e.jx0 = jx0; e.jx1 = jx1; e.iy0 = iy0; e.iy1 = iy1;
+          if constexpr (TRACTION) e.pad = t;
         }
       }
     }
@@ -440,20 +494,75 @@ __global__ __launch_bounds__(kDeformBlock) void deformed_mesh_depth_kernel(Defor
         const float invz = (l0 * e.iz[0] + l1 * e.iz[1]) + l2 * e.iz[2];
         const float z = 1.0f / invz;
         if (!(z >= a.near_m && z <= a.far_m)) continue;  // clipping range (also drops NaN)
-        zb[k] = min(zb[k], __float_as_uint(z));
+        if constexpr (TRACTION) {
+          const unsigned zu = __float_as_uint(z);
+          // (a finite z: zu < +inf's bits, so the first fragment always wins against tw = -1)
+          if (zu < zb[k] || (zu == zb[k] && e.pad < tw[k])) { zb[k] = zu; tw[k] = e.pad; }
+        } else {
+          zb[k] = min(zb[k], __float_as_uint(z));
+        }
       }
     }
     __syncthreads();
     if (tid == 0) count = 0;
     __syncthreads();
   }
-  if (x0 + col < x1) {
+  if constexpr (TRACTION) {
+    if (x0 + col < x1) {
 #pragma unroll
-    for (int k = 0; k < kDeformRows; ++k) {
-      const int i = y0 + row0 + 4 * k;
-      if (i < y1) a.depth[((size_t)env * a.H + i) * a.W + x0 + col] = __uint_as_float(zb[k]);
+      for (int k = 0; k < kDeformRows; ++k) {
+        const int i = y0 + row0 + 4 * k;
+        if (i >= y1) continue;
+        float o0 = 0.0f, o1 = 0.0f, o2 = 0.0f;
+        if (tw[k] >= 0) {
+          float sx[3], sy[3], iz[3];
+          float3s tv[3];
+#pragma unroll
+          for (int c = 0; c < 3; ++c) {
+            const int sv = a.tris[3 * tw[k] + c];
+            const float4 p = a.staged ? stage[sv] : project_deformed(a, verts, cp, R, sv);
+            sx[c] = p.x; sy[c] = p.y; iz[c] = p.z;
+            tv[c] = tr.tstaged ? tstage[sv] : vertex_traction(fb, tr.area, src.surf_ids, R, sv);
+          }
+          // the walk's expressions for this triangle and pixel: the same l_k and z, bit for bit
+          const float area = (sx[1] - sx[0]) * (sy[2] - sy[0]) - (sy[1] - sy[0]) * (sx[2] - sx[0]);
+          const float inv_area = 1.0f / area;
+          const float py = (float)i + 0.5f, px = pxc;
+          const float e0 = (sx[2] - sx[1]) * (py - sy[1]) - (sy[2] - sy[1]) * (px - sx[1]);
+          const float e1 = (sx[0] - sx[2]) * (py - sy[2]) - (sy[0] - sy[2]) * (px - sx[2]);
+          const float e2 = (sx[1] - sx[0]) * (py - sy[0]) - (sy[1] - sy[0]) * (px - sx[0]);
+          const float l0 = e0 * inv_area, l1 = e1 * inv_area, l2 = e2 * inv_area;
+          const float invz = (l0 * iz[0] + l1 * iz[1]) + l2 * iz[2];
+          const float z = 1.0f / invz;
+          const float w0 = (l0 * iz[0]) * z, w1 = (l1 * iz[1]) * z, w2 = (l2 * iz[2]) * z;
+          o0 = (w0 * tv[0].x + w1 * tv[1].x) + w2 * tv[2].x;
+          o1 = (w0 * tv[0].y + w1 * tv[1].y) + w2 * tv[2].y;
+          o2 = (w0 * tv[0].z + w1 * tv[1].z) + w2 * tv[2].z;
+        }
+        const size_t px_id = ((size_t)env * a.H + i) * a.W + x0 + col;
+        float* o = tr.traction + px_id * 3;
+        o[0] = o0; o[1] = o1; o[2] = o2;
+        if (a.depth) a.depth[px_id] = __uint_as_float(zb[k]);
+      }
+    }
+  } else {
+    if (x0 + col < x1) {
+#pragma unroll
+      for (int k = 0; k < kDeformRows; ++k) {
+        const int i = y0 + row0 + 4 * k;
+        if (i < y1) a.depth[((size_t)env * a.H + i) * a.W + x0 + col] = __uint_as_float(zb[k]);
+      }
     }
   }
+}
+
+template <class Verts>
+__global__ __launch_bounds__(kDeformBlock) void deformed_mesh_depth_kernel(DeformArgs a, Verts src) {
+  deformed_raster<Verts, false>(a, src, NoTraction{});
+}
+
+__global__ __launch_bounds__(kDeformBlock) void fem_traction_image_kernel(DeformArgs a, FemSurfaceVerts src, TractionArgs tr) {
+  deformed_raster<FemSurfaceVerts, true>(a, src, tr);
 }
 
 // tiles, staging and the launch of either instantiation (a: everything but tiles_x / tiles_y / staged filled in)
@@ -515,6 +624,41 @@ extern "C" int tacex_depth_from_deformed_mesh(const double* x_dev, int num_verts
   a.Vs = num_surf_verts; a.T = num_tris; a.B = num_envs; a.H = height; a.W = width;
   a.fx = fx; a.fy = fy; a.cx = cx; a.cy = cy; a.near_m = near_clip_m; a.far_m = far_clip_m;
   return launch_deformed_mesh_depth(a, FemSurfaceVerts{x_dev, surf_ids_dev, num_verts}, (hipStream_t)stream);
+}
+
+
+extern "C" int tacex_traction_image_from_deformed_mesh(const double* x_dev, int num_verts, const int32_t* surf_ids_dev, int num_surf_verts,
+                                                       const int32_t* tris_dev, int num_tris, const double* vertex_force_dev,
+                                                       const double* vertex_area_dev, const double* cam_pos_dev,
+                                                       const double* cam_rot_inv_dev, float fx, float fy, float cx, float cy,
+                                                       float near_clip_m, float far_clip_m, float* traction_dev, float* depth_m_dev,
+                                                       int num_envs, int height, int width, void* stream) {
+  using namespace tacex;
+  if (!x_dev || !surf_ids_dev || !tris_dev || !vertex_force_dev || !vertex_area_dev || !cam_pos_dev || !cam_rot_inv_dev || !traction_dev) {
+    set_error("tacex_traction_image_from_deformed_mesh: null buffer"); return 2;
+  }
+  if (num_verts <= 0 || num_surf_verts <= 0 || num_surf_verts > num_verts || num_tris <= 0 || num_envs <= 0 || height <= 0 || width <= 0) {
+    set_error("tacex_traction_image_from_deformed_mesh: bad counts (verts %d, surface verts %d, tris %d, envs %d, image %dx%d)", num_verts,
+              num_surf_verts, num_tris, num_envs, width, height);
+    return 2;
+  }
+  if (!(near_clip_m >= 0.0f) || !(far_clip_m > near_clip_m)) {
+    set_error("tacex_traction_image_from_deformed_mesh: clipping range (%g, %g)", near_clip_m, far_clip_m); return 2;
+  }
+  DeformArgs a{};
+  a.tris = tris_dev; a.cam_pos = cam_pos_dev; a.rot_inv = cam_rot_inv_dev; a.depth = depth_m_dev;
+  a.Vs = num_surf_verts; a.T = num_tris; a.B = num_envs; a.H = height; a.W = width;
+  a.fx = fx; a.fy = fy; a.cx = cx; a.cy = cy; a.near_m = near_clip_m; a.far_m = far_clip_m;
+  a.tiles_x = (a.W + kRasterTileW - 1) / kRasterTileW; a.tiles_y = (a.H + kRasterTileH - 1) / kRasterTileH;
+  if ((size_t)a.B * a.tiles_x * a.tiles_y >= (size_t)1 << 31) { set_error("fem_traction_image_kernel: grid too large"); return 2; }
+  a.staged = a.Vs <= kDeformStageMax;
+  TractionArgs tr{vertex_force_dev, vertex_area_dev, traction_dev, a.Vs <= kTractionStageMax};
+  const size_t lds = (a.staged ? (size_t)a.Vs * sizeof(float4) : 0) + (tr.tstaged ? (size_t)a.Vs * sizeof(float3s) : 0);
+  hipLaunchKernelGGL(fem_traction_image_kernel, dim3((unsigned)(a.B * a.tiles_x * a.tiles_y)), dim3(kDeformBlock), lds, (hipStream_t)stream, a,
+                     FemSurfaceVerts{x_dev, surf_ids_dev, num_verts}, tr);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) { set_error("fem_traction_image_kernel: %s", hipGetErrorString(e)); return 1; }
+  return 0;
 }
 
 

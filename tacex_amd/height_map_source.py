@@ -184,10 +184,9 @@ def contact_face_triangles(points, tets, optical_axis_w, min_cos: float = 0.5) -
     return np.ascontiguousarray(faces[cosang > min_cos], dtype=np.int32)
 
 
-class _SimCameraDepthSource:
-    """What `FemSurfaceDepthSource` and `AffineBodyDepthSource` share: the sensor camera over a `UipcSim` (pose, intrinsics, clipping
-    range, the (num_envs, H, W) depth image), the ordering behind a step on a side stream, and `fill`.  A subclass supplies `_render(sim)`,
-    the one launch that writes `self.depth` from the simulation state."""
+class _SimCamera:
+    """The sensor camera over a `UipcSim`: pose, intrinsics, clipping range and the (num_envs, H, W) depth image - what the depth sources
+    and `FemTractionImage` share."""
 
     def _init_camera(self, sim, camera_pos_w, camera_quat_w_ros, resolution, intrinsics, clipping_range):
         """Sets `pos` / `rot_inv` / image size / intrinsics / clipping range / `depth`; returns the camera -> world rotation (3,3)."""
@@ -208,6 +207,12 @@ class _SimCameraDepthSource:
         self.depth = torch.empty((B, self.H, self.W), dtype=torch.float32, device=dev)
         self._lib = _lib.load_library()
         return rot[0]
+
+
+class _SimCameraDepthSource(_SimCamera):
+    """What `FemSurfaceDepthSource` and `AffineBodyDepthSource` share: the sensor camera over a `UipcSim` (`_SimCamera`), the ordering behind
+    a step on a side stream, and `fill`.  A subclass supplies `_render(sim)`, the one launch that writes `self.depth` from the simulation
+    state."""
 
     def __call__(self) -> torch.Tensor:
         sim = self._sim
@@ -230,7 +235,35 @@ class _SimCameraDepthSource:
         _lib.check(rc, "tacex_height_map_from_depth")
 
 
-class FemSurfaceDepthSource(_SimCameraDepthSource):
+class _FemContactFace:
+    """The pad's rendered face, shared by `FemSurfaceDepthSource` and `FemTractionImage`: the object's checks, the face selection and the
+    index tables the kernels read (`surf_ids`, `tris`), validated here on the host - the device does not check them."""
+
+    def _init_face(self, uipc_object, camera_pos_w, camera_quat_w_ros, resolution, intrinsics, clipping_range, triangles):
+        name = type(self).__name__
+        sim = getattr(uipc_object, "_uipc_sim", None)
+        if sim is None or getattr(sim, "x", None) is None:
+            raise RuntimeError(f"{name} needs a UipcObject attached to a UipcSim that was set up (setup_sim)")
+        if getattr(uipc_object, "is_affine_body", False):
+            raise ValueError(f"{name} renders the deformable object (the gel pad), not an affine body")
+        rot = self._init_camera(sim, camera_pos_w, camera_quat_w_ros, resolution, intrinsics, clipping_range)
+        dev = sim.device
+        if triangles is None:
+            tri = contact_face_triangles(uipc_object.points, uipc_object.tets, rot[:, 2].numpy())
+        else:
+            tri = np.asarray(triangles, dtype=np.int64).reshape(-1, 3)
+            if len(tri) and (tri.min() < 0 or tri.max() >= uipc_object.num_verts):
+                raise ValueError(f"{name}: triangle indices outside [0, {uipc_object.num_verts})")
+        if len(tri) == 0:
+            raise ValueError(f"{name}: no triangles to render")
+        ids, local = np.unique(tri.reshape(-1), return_inverse=True)
+        self.triangles = np.ascontiguousarray(tri, dtype=np.int32)  # (F,3) object vertex ids
+        self.surf_ids = torch.from_numpy(ids.astype(np.int32)).to(dev)
+        self.tris = torch.from_numpy(local.reshape(-1, 3).astype(np.int32)).to(dev)
+        return sim
+
+
+class FemSurfaceDepthSource(_FemContactFace, _SimCameraDepthSource):
     """Camera depth of the FEM gel pad's deformed contact face, per env, straight from the FEM state (`UipcSim.x`) in one HIP launch
     (`tacex_depth_from_deformed_mesh`): the image the reference's sensor camera takes of the UIPC surface meshes after every step
     (tacex_uipc uipc_sim.py:268-284, read by GelSightSensor._get_height_map).  `source()` -> (num_envs, H, W) float32 depth in metres,
@@ -247,25 +280,7 @@ class FemSurfaceDepthSource(_SimCameraDepthSource):
 
     def __init__(self, uipc_object, camera_pos_w, camera_quat_w_ros, resolution=(320, 240), intrinsics=(340.0, 325.0, 160.0, 125.0),
                  clipping_range=(0.024, 0.029), triangles=None):
-        sim = getattr(uipc_object, "_uipc_sim", None)
-        if sim is None or getattr(sim, "x", None) is None:
-            raise RuntimeError("FemSurfaceDepthSource needs a UipcObject attached to a UipcSim that was set up (setup_sim)")
-        if getattr(uipc_object, "is_affine_body", False):
-            raise ValueError("FemSurfaceDepthSource renders the deformable object (the gel pad), not an affine body")
-        rot = self._init_camera(sim, camera_pos_w, camera_quat_w_ros, resolution, intrinsics, clipping_range)
-        dev = sim.device
-        if triangles is None:
-            tri = contact_face_triangles(uipc_object.points, uipc_object.tets, rot[:, 2].numpy())
-        else:
-            tri = np.asarray(triangles, dtype=np.int64).reshape(-1, 3)
-            if len(tri) and (tri.min() < 0 or tri.max() >= uipc_object.num_verts):
-                raise ValueError(f"FemSurfaceDepthSource: triangle indices outside [0, {uipc_object.num_verts})")
-        if len(tri) == 0:
-            raise ValueError("FemSurfaceDepthSource: no triangles to render")
-        ids, local = np.unique(tri.reshape(-1), return_inverse=True)
-        self.triangles = np.ascontiguousarray(tri, dtype=np.int32)  # (F,3) object vertex ids
-        self.surf_ids = torch.from_numpy(ids.astype(np.int32)).to(dev)
-        self.tris = torch.from_numpy(local.reshape(-1, 3).astype(np.int32)).to(dev)
+        self._init_face(uipc_object, camera_pos_w, camera_quat_w_ros, resolution, intrinsics, clipping_range, triangles)
 
     def _render(self, sim):
         x = sim.x
@@ -310,3 +325,49 @@ class AffineBodyDepthSource(_SimCameraDepthSource):
                 _lib.ptr(self.pos), _lib.ptr(self.rot_inv), self.fx, self.fy, self.cx, self.cy, self.near, self.far, _lib.ptr(self.depth),
                 int(self.depth.shape[0]), self.H, self.W, _lib.current_stream_handle(self.depth.device))
         _lib.check(rc, "tacex_depth_from_affine_body")
+
+
+class FemTractionImage(_FemContactFace, _SimCamera):
+    """Contact traction of the FEM gel pad as an image in the camera frame, per env, in one HIP launch
+    (`tacex_traction_image_from_deformed_mesh`): the per-vertex contact forces of `UipcSim.contact_forces(per_vertex=True)` divided by
+    the barrier's vertex areas (`UipcObject.surface_vertex_areas()`) and interpolated over the deformed contact face by the rasteriser
+    of `FemSurfaceDepthSource`.  `image()` -> (num_envs, H, W, 3) float32 in Pa, pixel-aligned with that source's depth (so with
+    `height_map` and `tactile_rgb` when it feeds the sensor), zero where nothing is seen.  Forces act ON the pad, in the camera frame
+    (x right, y down, z along the optical axis): `[..., 2]` is the normal pressure, negative where an indenter pushes the face towards the
+    camera, `[..., 0:2]` the shear.  Works on the prescribed-indenter scene and on a scene with an affine body (the pad of `FemBallScene`).
+
+    Constructor arguments, face selection, `pos` / `rot_inv` (updated in place by the caller) as in `FemSurfaceDepthSource`.  `traction`
+    and `depth` are persistent tensors, overwritten by every call."""
+
+    def __init__(self, uipc_object, camera_pos_w, camera_quat_w_ros, resolution=(320, 240), intrinsics=(340.0, 325.0, 160.0, 125.0),
+                 clipping_range=(0.024, 0.029), triangles=None):
+        sim = self._init_face(uipc_object, camera_pos_w, camera_quat_w_ros, resolution, intrinsics, clipping_range, triangles)
+        self.num_verts = int(uipc_object.num_verts)
+        self.vertex_areas = torch.from_numpy(np.ascontiguousarray(uipc_object.surface_vertex_areas(), dtype=np.float64)).to(sim.device)
+        self.traction = torch.zeros((sim.num_envs, self.H, self.W, 3), dtype=torch.float32, device=sim.device)
+
+    def __call__(self, friction: bool | None = None, with_depth: bool = False) -> torch.Tensor:
+        """The traction image of the current state: `contact_forces(per_vertex=True, friction=friction)` and the render, both on the
+        current stream behind the last step, no host synchronisation.  `with_depth`: also write `self.depth` (bit-equal to
+        `FemSurfaceDepthSource`'s)."""
+        sim = self._sim
+        sim.wait_for_step()  # a step enqueued on a side stream (UipcSim.step_done) is ordered before both launches
+        forces = sim.contact_forces(per_vertex=True, friction=friction)
+        return self.render(forces.vertex_forces, with_depth=with_depth)
+
+    def render(self, vertex_forces: torch.Tensor, with_depth: bool = False) -> torch.Tensor:
+        """The image of explicit per-vertex forces (num_envs, V, 3) float64 [N, world frame] on the current FEM state."""
+        x = self._sim.x
+        B = int(self.traction.shape[0])
+        f = vertex_forces
+        if not isinstance(f, torch.Tensor) or f.dtype != torch.float64 or tuple(f.shape) != (B, self.num_verts, 3) or f.device != x.device:
+            raise ValueError(f"FemTractionImage.render: vertex_forces must be a ({B}, {self.num_verts}, 3) float64 tensor on {x.device}")
+        f = f if f.is_contiguous() else f.contiguous()
+        with torch.cuda.device(self.traction.device):
+            rc = self._lib.tacex_traction_image_from_deformed_mesh(
+                _lib.ptr(x), int(x.shape[1]), _lib.ptr(self.surf_ids), int(self.surf_ids.shape[0]), _lib.ptr(self.tris),
+                int(self.tris.shape[0]), _lib.ptr(f), _lib.ptr(self.vertex_areas), _lib.ptr(self.pos), _lib.ptr(self.rot_inv), self.fx,
+                self.fy, self.cx, self.cy, self.near, self.far, _lib.ptr(self.traction), _lib.ptr(self.depth) if with_depth else None, B,
+                self.H, self.W, _lib.current_stream_handle(self.traction.device))
+        _lib.check(rc, "tacex_traction_image_from_deformed_mesh")
+        return self.traction

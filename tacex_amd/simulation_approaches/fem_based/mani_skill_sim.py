@@ -34,6 +34,8 @@ class ManiSkillSimulator(MarkerImageMixin, GelSightSimulator):
         sim = self.gelpad_uipc._uipc_sim
         if sim.num_envs != self._num_envs:
             raise RuntimeError(f"UipcSim has {sim.num_envs} envs, the sensor {self._num_envs}")
+        cam_cfg = getattr(self.sensor.cfg, "sensor_camera_cfg", None)  # (the camera `traction_image` renders with clips like the sensor's)
+        clip = {} if getattr(cam_cfg, "clipping_range", None) is None else {"clipping_range": tuple(cam_cfg.clipping_range)}
         self.marker_motion_sim = VisionTactileSensorUIPC(
             self.gelpad_uipc, sim,
             cam_pos_w=torch.as_tensor(self.cfg.camera_pos_w, dtype=torch.float64),
@@ -44,7 +46,7 @@ class ManiSkillSimulator(MarkerImageMixin, GelSightSimulator):
             marker_random_noise=self.cfg.marker_random_noise,
             marker_lose_tracking_probability=self.cfg.marker_lose_tracking_probability, normalize=self.cfg.normalize,
             num_markers=self.cfg.marker_params.num_markers, camera_params=self.cfg.camera_params,
-            marker_patterns=self.cfg.marker_patterns, seed=self.cfg.marker_seed)
+            marker_patterns=self.cfg.marker_patterns, seed=self.cfg.marker_seed, **clip)
         self.marker_data = torch.zeros((self._num_envs, 2, self.cfg.marker_params.num_markers, 2), device=self._device)
 
     def marker_motion_simulation(self):
@@ -58,6 +60,10 @@ class ManiSkillSimulator(MarkerImageMixin, GelSightSimulator):
     def contact_wrench(self, **kw):
         """Contact forces and net wrench on the gelpad in the camera frame (`VisionTactileSensorUIPC.contact_wrench`)."""
         return self.marker_motion_sim.contact_wrench(**kw)
+
+    def traction_image(self, **kw):
+        """Contact traction of the gelpad as a camera-frame image in Pa (`VisionTactileSensorUIPC.traction_image`)."""
+        return self.marker_motion_sim.traction_image(**kw)
 
     def _marker_pixels(self):
         """`marker_images()` / `draw_markers()` (mani_skill_sim.py:218-257; `MarkerImageMixin`) stamp a dot at every marker's current PIXEL

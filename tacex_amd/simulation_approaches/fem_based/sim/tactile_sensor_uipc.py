@@ -163,8 +163,11 @@ class VisionTactileSensorUIPC:
                  tactile_img_width=320, tactile_img_height=240, marker_interval_range=(2.0625, 2.0625),
                  marker_rotation_range=0.0, marker_translation_range=(0.0, 0.0), marker_pos_shift_range=(0.0, 0.0),
                  marker_random_noise=0.0, marker_lose_tracking_probability=0.0, normalize=False, num_markers=128,
-                 camera_params=(340, 325, 160, 125, 0.0), seed: int = 0, marker_patterns: int = 0, **kwargs):
+                 camera_params=(340, 325, 160, 125, 0.0), seed: int = 0, marker_patterns: int = 0, clipping_range=(0.024, 0.029),
+                 **kwargs):
         self.gelpad_obj = uipc_gelpad
+        self.clipping_range = (float(clipping_range[0]), float(clipping_range[1]))  # of the camera `traction_image` renders with [m]
+        self._cam_quat_w_ros = cam_quat_w_ros.detach().to("cpu", torch.float64)
         self.uipc_sim = uipc_sim
         self.tactile_img_width, self.tactile_img_height = tactile_img_width, tactile_img_height
         self.marker_interval_range = marker_interval_range
@@ -273,6 +276,40 @@ class VisionTactileSensorUIPC:
             q = torch.cat([((w.q[:, 0] - self.cam_pos_w)[:, None] @ Rt), w.q[:, 1:4] @ Rt], 1)
             return BallContactForces(rec, vf, q)
         return ContactForces(rec, vf)
+
+    def traction_image(self, friction: bool | None = None, obs_res=None):
+        """The pad's contact traction as a (num_envs, H, W, 3) float32 image in Pa, camera frame, forces ON the pad (`FemTractionImage`,
+        built on first use from this sensor's camera pose, intrinsics and image size): `[..., 2]` the normal pressure (negative under an
+        indenter), `[..., 0:2]` the shear; pixel-aligned with `FemSurfaceDepthSource`'s depth.  `friction` as in `contact_wrench`.
+        Clipping range: `self.clipping_range` - the owning sensor's `cfg.sensor_camera_cfg.clipping_range` when a `ManiSkillSimulator`
+        built this object, (0.024, 0.029) m otherwise.  The camera is the one this sensor was constructed with; a caller that moves it
+        updates `traction_source.pos` / `.rot_inv` in place.
+        With `obs_res = (ow, oh)`: returns (image, observation), the observation the (num_envs, oh, ow, 3) antialiased down-sample of the
+        image (`tacex_resize_bilinear_aa_nhwc`, two passes).  The tensors returned are overwritten by the next call."""
+        src = getattr(self, "traction_source", None)
+        if src is None:
+            from ....height_map_source import FemTractionImage
+
+            src = self.traction_source = FemTractionImage(
+                self.gelpad_obj, self.cam_pos_w.cpu(), self._cam_quat_w_ros, resolution=(self.tactile_img_width, self.tactile_img_height),
+                intrinsics=(self.fx, self.fy, self.cx, self.cy), clipping_range=self.clipping_range)
+            self._traction_obs = {}
+        img = src(friction=friction)
+        if obs_res is None:
+            return img
+        ow, oh = int(obs_res[0]), int(obs_res[1])
+        if ow <= 0 or oh <= 0:
+            raise ValueError(f"traction_image: obs_res {obs_res}")
+        B, H, W = img.shape[0], img.shape[1], img.shape[2]
+        if (ow, oh) not in self._traction_obs:
+            self._traction_obs[(ow, oh)] = (torch.empty((B, oh, ow, 3), dtype=torch.float32, device=self.device),
+                                            torch.empty((B, oh, W, 3), dtype=torch.float32, device=self.device))
+        obs, tmp = self._traction_obs[(ow, oh)]
+        with torch.cuda.device(self.device):
+            rc = self._lib.tacex_resize_bilinear_aa_nhwc(_lib.ptr(img), H, W, _lib.ptr(obs), oh, ow, 3, B, _lib.ptr(tmp),
+                                                         _lib.current_stream_handle(self.device))
+        _lib.check(rc, "tacex_resize_bilinear_aa_nhwc")
+        return img, obs
 
     def get_surface_vertices_camera(self) -> torch.Tensor:
         return self.transform_world_to_camera_frame(self.get_surface_vertices_world()).contiguous()
