@@ -834,6 +834,42 @@ int tacex_fem_marker_flow_library(const double* x_dev, const int64_t* surf_ids_d
  * generator.  ctr (4), key (2) -> out (4) uint32. */
 int tacex_philox4x32(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]);
 
+/* Sensor camera model: what a GelSight's camera does to the rendered frame - a per-unit colour response, pixel-to-pixel gain
+ * differences (fixed pattern), read and shot noise, 8-bit quantisation - applied to rgb_dev (B,H,W,3) f32 in ONE launch on `stream`
+ * (tacex_amd/csrc/camera_model.hip).  B = num_frames, any H, W >= 1; inputs are finite.
+ *   out_dtype 0: out_dev is (B,H,W,3) f32 in [0,1]; out_dev == rgb_dev (in place) is allowed and gives the same image.
+ *   out_dtype 1: out_dev is (B,H,W,3) uint8 = floor(255 v + 0.5).
+ * All arithmetic is float32, every operation rounded on its own (no fused multiply-add), in the order written below.
+ * Profiles: profiles_dev (P,16) f32, P = num_profiles.  Row: [0..8] colour matrix M row-major, [9..11] offset o, [12] read-noise sigma
+ *   `read` (in units of full scale), [13] shot coefficient s (variance = s * signal), [14] fixed-pattern sigma_f, [15] reserved, written 0.
+ *   Frame b uses row profile_ids_dev[b] ((B,) int32; NULL: row 0 for every frame).  An id outside [0, P) is the identity profile
+ *   (M = I, everything else 0): the output is the clamped input.
+ * Draws: the pixels of a frame are taken in row-major order in groups of four; group g holds pixels 4g .. 4g+3 (the last group of a
+ *   frame may be partial).  Sample j = 3 p + c of a group (pixel p of the group, channel c) takes word j % 4 of Philox4x32-10
+ *   (tacex_philox4x32) with key (seed & 0xffffffff, seed >> 32) and counter (g, j / 4, frame_offset + b, call).  The draw is the
+ *   integer d = (sum of the word's four bytes) - 510: mean exactly 0, variance exactly 4 (256^2 - 1) / 12 = 21845, bounded at +-3.45
+ *   standard deviations, no transcendental function.  S = float32(1 / sqrt(21845.0)).  The fixed-pattern draw d_f is the same with
+ *   counter (g, 4 + j / 4, frame_offset + b, 0): it does not depend on `call`.
+ * Per pixel (r, g, b) and output channel c:
+ *     a = ((M[c][0]*r + M[c][1]*g) + M[c][2]*b) + o[c]
+ *     if sigma_f != 0:  a = a * (1 + (sigma_f*S) * float(d_f))
+ *     a = min(max(a, 0), 1)
+ *     sig = sqrtf(read*read + s*a)
+ *     v = a + (sig*S) * float(d)
+ *     v = min(max(v, 0), 1)
+ *     out = v (out_dtype 0)   or   (uint8) floorf(255*v + 0.5f) (out_dtype 1)
+ * An image depends on (seed, frame_offset + b, call, profile) alone - not on B, the other frames or the launch shape: a shard of
+ * envs passes its first global env index as frame_offset and renders the frames the whole batch would.
+ * Returns 2 before any HIP call for a NULL rgb_dev, profiles_dev or out_dev, num_profiles <= 0, num_frames, height or width <= 0,
+ * an out_dtype other than 0 or 1, out_dtype 1 with out_dev == rgb_dev, and a batch beyond one launch (2^31 - 1 workgroups). */
+int tacex_camera_model(const float* rgb_dev, const float* profiles_dev, int num_profiles, const int32_t* profile_ids_dev,
+                       uint64_t seed, uint32_t frame_offset, uint32_t call, void* out_dev, int out_dtype, int num_frames, int height,
+                       int width, void* stream);
+
+/* HOST: the 12 integer draws d (fixed_pattern 0) or d_f (fixed_pattern != 0; `call` is ignored) of group `group` of frame
+ * `frame` (= frame_offset + b) - the function the kernel calls, compiled for the host, so that a CPU test pins the draws. */
+int tacex_camera_noise_draw(uint64_t seed, uint32_t frame, uint32_t call, uint32_t group, int fixed_pattern, int32_t out[12]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -177,6 +177,8 @@ SIGNATURES = {
     "tacex_fem_marker_flow_library": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, C.c_uint64, _d, _d, _d, _d, _d, _d, _i, _i, _d,
                                            _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "tacex_philox4x32": (_i, [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "tacex_camera_model": (_i, [_vp, _vp, _i, _vp, C.c_uint64, C.c_uint32, C.c_uint32, _vp, _i, _i, _i, _i, _vp]),
+    "tacex_camera_noise_draw": (_i, [C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, _i, c_int32_p]),
 }
 
 _lib = None

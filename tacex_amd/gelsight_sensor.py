@@ -145,6 +145,14 @@ class GelSightSensor(SensorBase):
             raise RuntimeError("a grouped sensor takes its height map from the camera depth or set_height_map (one source per group)")
         self._height_map_source = source
 
+    def camera_image(self, model, out: torch.Tensor | None = None) -> torch.Tensor:
+        """The current `data.output["tactile_rgb"]` as the sensor's camera would deliver it: `model` (a `TactileCameraModel` of
+        num_envs frames) applied in one launch on the current stream.  `tactile_rgb` itself is left as it is."""
+        output = self.data.output  # (brings outdated buffers up to date)
+        if "tactile_rgb" not in output:
+            raise RuntimeError('camera_image needs "tactile_rgb" in cfg.data_types')
+        return model(output["tactile_rgb"], out=out)
+
     def _read_camera_depth(self):
         src = self.cfg.sensor_camera_cfg.depth_source if self.cfg.sensor_camera_cfg is not None else None
         if src is not None:
