@@ -870,6 +870,60 @@ int tacex_camera_model(const float* rgb_dev, const float* profiles_dev, int num_
  * `frame` (= frame_offset + b) - the function the kernel calls, compiled for the host, so that a CPU test pins the draws. */
 int tacex_camera_noise_draw(uint64_t seed, uint32_t frame, uint32_t call, uint32_t group, int fixed_pattern, int32_t out[12]);
 
+/* Contact force field of the optical path: an elastic-foundation (Winkler) contact model with regularised Coulomb shear, evaluated
+ * per pixel of the height map and reduced per env and per cell of a coarse tactile grid, in ONE launch on `stream`
+ * (tacex_amd/csrc/contact_field.hip).  B = num_frames, any H, W >= 1.  All per-pixel operations are float32, each rounded on its own
+ * (no fused multiply-add), in the order written; sums are float64, in an order fixed by (H, W) alone and without atomics: the same
+ * input gives the same bits, and an env's outputs do not depend on the batch it is evaluated in.
+ * Inputs: hm_mm_dev (B,H,W) f32 height map [mm]; frame_min_dev (B,) f32 its per-frame minimum and indent_mm_dev (B,) f32 the
+ *   indentation depth [mm], as tacex_height_map_from_depth / tacex_indentation_depth leave them;
+ *   gels_dev (P,4) f32, P = num_gels, row [k_n, k_t, mu, 0] with k_n, k_t in Pa/mm, all >= 0; frame b uses row gel_ids_dev[b]
+ *   ((B,) int32; NULL: row 0).  An id outside [0, P): every output of the env is zero (the whole record too);
+ *   slip_dev (B,5) f32 [dx_mm, dy_mm, dtheta_rad, cx_px, cy_px]: the object's motion over the pad since first contact, about the
+ *   pixel (cx, cy); NULL: all zero (no shear anywhere);
+ *   pixmm: pixel pitch [mm]; a = float32(double(pixmm)^2 * 1e-6) is a pixel's area [m^2].
+ * Per pixel (row i, column j):
+ *     S = (hm - frame_min) - indent                      (TT:441)
+ *     d = S < 0 ? -S : 0                                 [mm]; a NaN gives 0
+ *     p = k_n * d                                        [Pa]
+ *   and, where d > 0 (everything below is 0 / false where d == 0):
+ *     rx = (float(j) - cx) * pixmm,  ry = (float(i) - cy) * pixmm
+ *     ux = dx - dtheta * ry,  uy = dy + dtheta * rx,  n = sqrtf(ux*ux + uy*uy)
+ *     slips = k_t*n >= mu*p
+ *     s = min(k_t*n, mu*p) / n,  tx = ux * s,  ty = uy * s       (tx = ty = 0 where n == 0)
+ *   traction on the pad in the camera frame (x = columns, y = rows, z = optical axis): (tx, ty, -p) [Pa] - the layout and sign of
+ *   tacex_traction_image_from_deformed_mesh; force of the pixel: fx = tx*a, fy = ty*a, fn = p*a, (fx, fy, -fn) [N].
+ * record_dev (B,16) f64.  With the float64 sums over the frame's pixels (float32 terms widened to float64; products with i, j formed in float64)
+ *   and (cx0, cy0) = ((W-1)/2, (H-1)/2), m = double(pixmm) * 1e-3:
+ *   [0..2] (sum fx, sum fy, -sum fn) [N];
+ *   [3..5] torque about the image centre on the pad face, sum r x f with r = ((j-cx0) m, (i-cy0) m, 0) [N m]:
+ *          [3] = -(sum fn*i - cy0 sum fn) m,  [4] = (sum fn*j - cx0 sum fn) m,
+ *          [5] = ((sum fy*j - cx0 sum fy) - (sum fx*i - cy0 sum fx)) m;
+ *   [6] Fn = sum fn;  [7] contact area = count * double(a) [m^2];  [8] count of pixels with d > 0;
+ *   [9], [10] centre of pressure (x, y) = (sum p*j, sum p*i) / sum p [px]; (cx0, cy0) when sum p == 0;
+ *   [11] largest d [mm];  [12] penetrated volume = (sum d) * double(pixmm)^2 [mm^3];  [13] count of slipping pixels;
+ *   [14] principal-axis angle 0.5 atan2(2 m11, m20 - m02) of the pressure distribution, with x = [9], y = [10] and
+ *        m20 = sum p*j*j / sum p - x*x, m02 = sum p*i*i / sum p - y*y, m11 = sum p*j*i / sum p - x*y [px^2]; 0 when sum p == 0;
+ *   [15] sqrt(max(l_min, 0) / l_max), l = (m20+m02)/2 -+ sqrt(((m20-m02)/2)^2 + m11^2); 0 when sum p == 0 or l_max <= 0.
+ * cells_dev (B,grid_rows,grid_cols,3) f32, nullable: the force (sum fx, sum fy, -sum fn) [N] on every cell of a grid laid over the
+ *   image, summed in float64 and rounded once; pixel (i, j) belongs to cell ((i*grid_rows)/H, (j*grid_cols)/W) (integer division).
+ *   The cells of an env sum to [0..2].
+ * image_dev (B,H,W,3) f32 [Pa], nullable: (tx, ty, -p) of every pixel; when given, every pixel is written.
+ * frame_rows_dev (B,4) int32, nullable: the contact rectangles [row lo, row hi, column lo, column hi] that
+ *   tacex_height_map_from_depth / tacex_indentation_depth produce for THESE height maps (nothing outside one has S < 0).  Only the
+ *   rectangle is read; every output is bit-equal to the call without it, and a frame with an empty rectangle reads no pixel.
+ *   (The rectangle is clamped to the image: it can skip pixels, never address outside the frame.)
+ * 16-byte loads along rows are used when hm_mm_dev (and image_dev) are 16-byte aligned and W % 4 == 0; the result is the same bits
+ * otherwise.  One workgroup handles one frame and keeps 8 rows of pixel forces and of per-cell runs in LDS: about
+ * 8 (12 W + 24 grid_cols c) bytes with c = ceil(ceil(W / grid_cols) / 32) (none when cells_dev is NULL).
+ * Returns 2 before any HIP call for a NULL hm_mm_dev, frame_min_dev, indent_mm_dev, gels_dev or record_dev, num_gels <= 0,
+ * num_frames, height or width <= 0, pixmm <= 0 (or NaN), grid_rows outside [1, height] or grid_cols outside [1, width] (checked
+ * with or without cells_dev), and a width / grid_cols pair that needs more than 128 KiB of LDS. */
+int tacex_contact_field(const float* hm_mm_dev, const float* frame_min_dev, const float* indent_mm_dev, const float* gels_dev,
+                        int num_gels, const int32_t* gel_ids_dev, const float* slip_dev, float pixmm, const int32_t* frame_rows_dev,
+                        int grid_rows, int grid_cols, double* record_dev, float* cells_dev, float* image_dev, int num_frames,
+                        int height, int width, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

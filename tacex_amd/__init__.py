@@ -1,10 +1,11 @@
 """tacex_amd - MI355X-native GelSight tactile-image engine behind TacEx's sensor / simulator plugin API."""
 from .camera_model import CameraProfile, TactileCameraModel
+from .contact_field import ContactField, ContactGel, TactileContactModel, slip_from_fots
 from .gelsight_sensor import GelSightSensor
 from .gelsight_sensor_cfg import GelSightSensorCfg
 from .gelsight_sensor_data import GelSightSensorData
 from .gelsight_sensor_group import GelSightSensorGroup
 from .height_map_source import AffineBodyDepthSource, FemSurfaceDepthSource, FemTractionImage, IndenterHeightMapSource, MeshDepthSource, MeshLibraryDepthSource
 
-__all__ = ["AffineBodyDepthSource", "CameraProfile", "GelSightSensor", "GelSightSensorCfg", "GelSightSensorData", "GelSightSensorGroup", "FemSurfaceDepthSource", "FemTractionImage", "IndenterHeightMapSource", "MeshDepthSource",
-           "MeshLibraryDepthSource", "TactileCameraModel"]
+__all__ = ["AffineBodyDepthSource", "CameraProfile", "ContactField", "ContactGel", "GelSightSensor", "GelSightSensorCfg", "GelSightSensorData", "GelSightSensorGroup", "FemSurfaceDepthSource", "FemTractionImage", "IndenterHeightMapSource", "MeshDepthSource",
+           "MeshLibraryDepthSource", "TactileCameraModel", "TactileContactModel", "slip_from_fots"]

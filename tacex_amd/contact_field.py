@@ -1,0 +1,231 @@
+"""Contact force field of the optical path: penalty contact from the height map (`tacex_contact_field`,
+tacex_amd/csrc/contact_field.hip; the contract is that function's comment in include/tacex_hip.h).
+
+    gels = [ContactGel.from_material(youngs=1.2e5, poisson=0.45, thickness_m=0.0045, mu=0.6), ContactGel(k_n=4e4, k_t=1.5e4, mu=0.9)]
+    model = TactileContactModel(gels, num_frames=num_envs, device="cuda:0", pixmm=0.0295, grid=(9, 11))
+    model.randomize()                      # at reset: a gel per env, drawn on the device
+    field = sensor.contact_field(model)    # one launch after the sensor's update, no host synchronisation
+    field.normal_force, field.friction_force, field.centre_of_pressure, field.slip_ratio, field.cells
+
+Every pixel's penetration into the elastomer gives a normal pressure through a stiffness (an elastic foundation), the object's
+tangential motion since first contact a shear traction capped by Coulomb's cone; the launch reduces them per env and per cell of
+a coarse tactile grid."""
+from __future__ import annotations
+
+import math
+from dataclasses import dataclass
+
+import numpy as np
+import torch
+
+from . import _lib
+
+
+@dataclass
+class ContactGel:
+    """One elastomer: normal and tangential foundation stiffness `k_n`, `k_t` [Pa/mm] (pressure per mm of penetration / of tangential
+    displacement) and the friction coefficient `mu` of Coulomb's cone."""
+
+    k_n: float
+    k_t: float = 0.0
+    mu: float = 0.0
+
+    @classmethod
+    def from_material(cls, youngs: float, poisson: float, thickness_m: float, mu: float = 0.0) -> "ContactGel":
+        """The elastic-foundation moduli of a layer of thickness h bonded to a rigid backing: k_n = E (1 - v) / ((1 + v) (1 - 2 v) h)
+        (the constrained modulus over h) and k_t = E / (2 (1 + v) h) (the shear modulus over h), in Pa/mm."""
+        E, v, h = float(youngs), float(poisson), float(thickness_m)
+        if not (math.isfinite(E) and E >= 0 and math.isfinite(h) and h > 0):
+            raise ValueError("ContactGel.from_material: youngs must be finite and >= 0, thickness_m finite and > 0")
+        if not (math.isfinite(v) and v > -1.0):
+            raise ValueError("ContactGel.from_material: poisson must be finite and > -1")
+        if v >= 0.5:
+            raise ValueError(f"ContactGel.from_material: poisson = {v} >= 0.5 - the constrained modulus of an incompressible layer is "
+                             "unbounded; pass the stiffnesses k_n, k_t directly (ContactGel(k_n, k_t, mu)), e.g. from an indentation test")
+        k_n = E * (1 - v) / ((1 + v) * (1 - 2 * v) * h)  # Pa/m
+        k_t = E / (2 * (1 + v) * h)
+        return cls(k_n=k_n * 1e-3, k_t=k_t * 1e-3, mu=mu)
+
+    def row(self) -> np.ndarray:
+        """The (4,) float32 row [k_n, k_t, mu, 0] of `tacex_contact_field`'s gel table."""
+        with np.errstate(over="ignore"):  # a value beyond float32 becomes inf and is refused below
+            r = np.array([self.k_n, self.k_t, self.mu, 0.0], dtype=np.float32)
+        if not np.isfinite(r).all():
+            raise ValueError("ContactGel: k_n, k_t and mu must be finite (in float32)")
+        if (r < 0).any():
+            raise ValueError("ContactGel: k_n, k_t and mu must be >= 0")
+        return r
+
+
+class ContactField:
+    """What one call of a `TactileContactModel` returns.  `record` (B,16) float64 (the slots of `tacex_contact_field`), `cells`
+    (B,rows,cols,3) float32 force per tactile cell [N], `image` (B,H,W,3) float32 traction [Pa] or None.  Forces and tractions are
+    those ON THE PAD in the camera frame (x = columns, y = rows, z = optical axis): the normal component is negative under an
+    indenter, as in `FemTractionImage`.  Every property is a view of `record` or a torch op on it (no synchronisation)."""
+
+    def __init__(self, record: torch.Tensor, cells: torch.Tensor, image: torch.Tensor | None):
+        self.record, self.cells, self.image = record, cells, image
+
+    @property
+    def force(self) -> torch.Tensor:
+        """(B,3) net force on the pad [N]."""
+        return self.record[:, 0:3]
+
+    @property
+    def normal_force(self) -> torch.Tensor:
+        """(B,) Fn >= 0 [N]."""
+        return self.record[:, 6]
+
+    @property
+    def friction_force(self) -> torch.Tensor:
+        """(B,2) net shear force (x, y) on the pad [N]."""
+        return self.record[:, 0:2]
+
+    @property
+    def torque(self) -> torch.Tensor:
+        """(B,3) torque on the pad about the image centre on the pad face [N m]."""
+        return self.record[:, 3:6]
+
+    @property
+    def contact_area(self) -> torch.Tensor:
+        """(B,) [m^2]."""
+        return self.record[:, 7]
+
+    @property
+    def num_contact(self) -> torch.Tensor:
+        return self.record[:, 8]
+
+    @property
+    def centre_of_pressure(self) -> torch.Tensor:
+        """(B,2) (x, y) in pixels; the image centre without contact."""
+        return self.record[:, 9:11]
+
+    @property
+    def max_penetration(self) -> torch.Tensor:
+        """(B,) [mm]."""
+        return self.record[:, 11]
+
+    @property
+    def volume(self) -> torch.Tensor:
+        """(B,) penetrated volume [mm^3]."""
+        return self.record[:, 12]
+
+    @property
+    def num_slipping(self) -> torch.Tensor:
+        return self.record[:, 13]
+
+    @property
+    def slip_ratio(self) -> torch.Tensor:
+        """(B,) slipping pixels / contact pixels: 0 sticking, 1 gross slip; 0 without contact."""
+        return self.record[:, 13] / self.record[:, 8].clamp(min=1.0)
+
+    @property
+    def patch_angle(self) -> torch.Tensor:
+        """(B,) angle of the pressure patch's long axis against the x axis [rad], in (-pi/2, pi/2]."""
+        return self.record[:, 14]
+
+    @property
+    def patch_aspect(self) -> torch.Tensor:
+        """(B,) short / long axis of the pressure patch: 1 round, -> 0 elongated."""
+        return self.record[:, 15]
+
+
+def slip_from_fots(marker_sim) -> torch.Tensor:
+    """The (B,5) slip table [dx_mm, dy_mm, dtheta_rad, cx_px, cy_px] from a `FOTSMarkerSimulator`'s trajectory state
+    [len, x0, y0, th0, xl, yl, thl, n] (contact centroids in mm from the image centre, indenter yaw): the shear and twist since first
+    contact, about the last contact centroid in pixels.  Rows of envs out of contact (len < 1) are zero.  torch ops on the device."""
+    t = marker_sim._traj_state
+    W, H = marker_sim.cfg.tactile_img_res
+    mm2pix = float(marker_sim.cfg.mm_to_pixel)
+    slip = torch.stack((t[:, 4] - t[:, 1], t[:, 5] - t[:, 2], t[:, 6] - t[:, 3], t[:, 4] * mm2pix + W / 2.0, t[:, 5] * mm2pix + H / 2.0), dim=1)
+    return torch.where((t[:, 0] >= 1.0)[:, None], slip, torch.zeros_like(slip)).contiguous()
+
+
+class TactileContactModel:
+    """The contact model of `num_frames` envs.  `gels` (P,4) float32 and `gel_ids` (num_frames,) int32 are device tensors the caller
+    may write in place (ids at reset, like `TactileCameraModel.profile_ids`; an env whose id is outside [0, P) reports zeros).
+    `pixmm`: pixel pitch of the height map [mm]; `grid` = (rows, cols) of the tactile cells laid over the image."""
+
+    def __init__(self, gels, num_frames: int, device, pixmm: float = 0.0295, grid=(9, 11)):
+        if isinstance(gels, ContactGel):
+            gels = [gels]
+        rows = [g.row() if isinstance(g, ContactGel) else None for g in gels]
+        if not rows or any(r is None for r in rows):
+            raise ValueError("TactileContactModel: gels must be a non-empty sequence of ContactGel")
+        if int(num_frames) <= 0:
+            raise ValueError(f"TactileContactModel: num_frames = {num_frames}")
+        if not (math.isfinite(float(pixmm)) and float(pixmm) > 0):
+            raise ValueError(f"TactileContactModel: pixmm = {pixmm}")
+        if len(grid) != 2 or int(grid[0]) < 1 or int(grid[1]) < 1:
+            raise ValueError(f"TactileContactModel: grid = {grid} must be (rows >= 1, cols >= 1)")
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise _lib.TacexHipError(f"TactileContactModel runs on the GPU only (device {self.device}): there is no CPU fallback")
+        self._lib = _lib.load_library()
+        self.num_frames = int(num_frames)
+        self.pixmm = float(pixmm)
+        self.grid = (int(grid[0]), int(grid[1]))
+        self.gels = torch.from_numpy(np.stack(rows)).to(self.device)
+        self.gel_ids = torch.zeros(self.num_frames, dtype=torch.int32, device=self.device)
+
+    @property
+    def num_gels(self) -> int:
+        return int(self.gels.shape[0])
+
+    def randomize(self, env_ids=None, generator=None):
+        """Re-draw the gel ids of `env_ids` (default: all) uniformly from [0, P) on the device."""
+        n = self.num_frames if env_ids is None else len(env_ids)
+        ids = torch.randint(0, self.num_gels, (n,), dtype=torch.int32, device=self.device, generator=generator)
+        if env_ids is None:
+            self.gel_ids.copy_(ids)
+        else:
+            self.gel_ids[torch.as_tensor(env_ids, dtype=torch.long, device=self.device)] = ids
+        return self.gel_ids
+
+    def _vector(self, t, name, shape, dtype):
+        if not isinstance(t, torch.Tensor) or tuple(t.shape) != shape or t.dtype != dtype or not t.is_contiguous():
+            raise ValueError(f"TactileContactModel: {name} must be a contiguous {shape} {dtype} tensor")
+        if t.device != self.gels.device:
+            raise _lib.TacexHipError(f"TactileContactModel: {name} is on {t.device}, the model on {self.gels.device} (no CPU fallback)")
+        return t
+
+    def __call__(self, hm: torch.Tensor, frame_min: torch.Tensor, indent: torch.Tensor, slip: torch.Tensor | None = None,
+                 frame_rows: torch.Tensor | None = None, image: bool | torch.Tensor = False) -> ContactField:
+        """One launch on the current stream.  `hm` (num_frames,H,W) float32 [mm], contiguous, on the model's device; `frame_min`,
+        `indent` (num_frames,) float32 as the sensor's depth pass leaves them; `slip` (num_frames,5) float32 or None (no shear);
+        `frame_rows` (num_frames,4) int32 contact rectangles of THESE height maps or None; `image`: True allocates the traction
+        image, a (num_frames,H,W,3) float32 tensor is written in place, False writes none."""
+        B = self.num_frames
+        if not isinstance(hm, torch.Tensor) or hm.dim() != 3 or hm.shape[0] != B or hm.shape[1] < 1 or hm.shape[2] < 1:
+            raise ValueError(f"TactileContactModel: hm must be a ({B}, H, W) tensor, got "
+                             f"{tuple(hm.shape) if isinstance(hm, torch.Tensor) else type(hm).__name__}")
+        H, W = int(hm.shape[1]), int(hm.shape[2])
+        self._vector(hm, "hm", (B, H, W), torch.float32)
+        self._vector(frame_min, "frame_min", (B,), torch.float32)
+        self._vector(indent, "indent", (B,), torch.float32)
+        if slip is not None:
+            self._vector(slip, "slip", (B, 5), torch.float32)
+        if frame_rows is not None:
+            self._vector(frame_rows, "frame_rows", (B, 4), torch.int32)
+        self._vector(self.gel_ids, "gel_ids", (B,), torch.int32)
+        gels = self.gels
+        if not isinstance(gels, torch.Tensor) or gels.dim() != 2 or gels.shape[0] < 1:
+            raise ValueError("TactileContactModel: gels must stay a (P, 4) float32 tensor")
+        self._vector(gels, "gels", (int(gels.shape[0]), 4), torch.float32)
+        rows, cols = self.grid
+        if rows > H or cols > W:
+            raise ValueError(f"TactileContactModel: grid {self.grid} is larger than the {H} x {W} image")
+        img = None
+        if isinstance(image, torch.Tensor):
+            img = self._vector(image, "image", (B, H, W, 3), torch.float32)
+        elif image:
+            img = torch.empty((B, H, W, 3), dtype=torch.float32, device=hm.device)
+        record = torch.empty((B, 16), dtype=torch.float64, device=hm.device)
+        cells = torch.empty((B, rows, cols, 3), dtype=torch.float32, device=hm.device)
+        with torch.cuda.device(hm.device):
+            rc = self._lib.tacex_contact_field(_lib.ptr(hm), _lib.ptr(frame_min), _lib.ptr(indent), _lib.ptr(gels), int(gels.shape[0]),
+                                               _lib.ptr(self.gel_ids), _lib.ptr(slip), self.pixmm, _lib.ptr(frame_rows), rows, cols,
+                                               _lib.ptr(record), _lib.ptr(cells), _lib.ptr(img), B, H, W,
+                                               _lib.current_stream_handle(hm.device))
+        _lib.check(rc, "tacex_contact_field")
+        return ContactField(record, cells, img)

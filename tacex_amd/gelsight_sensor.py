@@ -153,6 +153,40 @@ class GelSightSensor(SensorBase):
             raise RuntimeError('camera_image needs "tactile_rgb" in cfg.data_types')
         return model(output["tactile_rgb"], out=out)
 
+    def contact_field(self, model, slip: torch.Tensor | None = None, image=False):
+        """The contact force field of the current `data.output["height_map"]`: `model` (a `TactileContactModel` of num_envs frames)
+        evaluated in one launch on the current stream -> `ContactField` (net force and torque, centre of pressure, contact area, slip,
+        per-cell forces, optionally the traction image).  The per-frame minimum, indentation depth and contact rectangles of the
+        indentation-depth provider are reused when they describe this height map; otherwise one `tacex_indentation_depth` fills
+        scratch buffers.  `slip` (num_envs, 5) [dx_mm, dy_mm, dtheta_rad, cx_px, cy_px]; None: `slip_from_fots` of a FOTS marker
+        simulator, no shear without one.  No output of the sensor is touched."""
+        if self._group is not None:
+            raise RuntimeError("contact_field is not available on a grouped sensor: call the TactileContactModel on the group's buffers")
+        hm = self.data.output["height_map"]  # (brings outdated buffers up to date)
+        sim, v = self._fused_targets(), self._height_map_version
+        rows = getattr(sim, "_frame_rows", None)
+        if (sim is not None and rows is not None and sim._frame_min_version == v and getattr(sim, "_indent_version", -1) == v
+                and getattr(sim, "_frame_rows_version", -1) == v and sim._frame_min.device == hm.device
+                and sim._indentation_depth.device == hm.device):
+            fmin, indent = sim._frame_min, sim._indentation_depth
+        else:
+            B, H, W = hm.shape
+            if getattr(self, "_cf_scratch", None) is None:
+                self._cf_scratch = (torch.zeros((B,), device=hm.device), torch.zeros((B,), device=hm.device),
+                                    torch.zeros((B, 4), dtype=torch.int32, device=hm.device))
+            fmin, indent, rows = self._cf_scratch
+            cfg = sim.cfg if sim is not None else self.cfg.optical_sim_cfg
+            with torch.cuda.device(hm.device):
+                rc = _lib.load_library().tacex_indentation_depth(
+                    _lib.ptr(hm), float(getattr(cfg, "gelpad_height", 0.0)), float(getattr(cfg, "gelpad_to_camera_min_distance", 0.0)),
+                    _lib.ptr(fmin), _lib.ptr(indent), _lib.ptr(rows), B, H, W, _lib.current_stream_handle(hm.device))
+            _lib.check(rc, "tacex_indentation_depth")
+        if slip is None and hasattr(self.marker_motion_simulator, "_traj_state"):
+            from .contact_field import slip_from_fots
+
+            slip = slip_from_fots(self.marker_motion_simulator)
+        return model(hm, fmin, indent, slip=slip, frame_rows=rows, image=image)
+
     def _read_camera_depth(self):
         src = self.cfg.sensor_camera_cfg.depth_source if self.cfg.sensor_camera_cfg is not None else None
         if src is not None:
