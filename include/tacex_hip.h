@@ -870,6 +870,72 @@ int tacex_camera_model(const float* rgb_dev, const float* profiles_dev, int num_
  * `frame` (= frame_offset + b) - the function the kernel calls, compiled for the host, so that a CPU test pins the draws. */
 int tacex_camera_noise_draw(uint64_t seed, uint32_t frame, uint32_t call, uint32_t group, int fixed_pattern, int32_t out[12]);
 
+/* Sensor lens model: what the short wide-angle lens of a GelSight and the mounting of one unit do to the rendered frame - radial
+ * and tangential (Brown-Conrady) distortion, a mounting shift, rotation, scale and shear against the pad, vignetting, and a
+ * softness that grows towards the corners - applied to rgb_dev (B,H,W,3) f32 as ONE gather on `stream`
+ * (tacex_amd/csrc/lens_model.hip) into out_dev (B,H,W,3) f32.  B = num_frames, any H, W >= 1; inputs are finite.  Any (B,H,W,3)
+ * f32 image goes through it (tactile_rgb, a marker overlay).  The stage sits between tactile_rgb and tacex_camera_model.
+ * All arithmetic is float32, every operation rounded on its own (no fused multiply-add), in the order written below; the kernel
+ * has no division and no transcendental function.  min / max are C's fminf / fmaxf (a NaN operand gives the other operand).
+ * Profiles: profiles_dev (P,16) f32, P = num_profiles.  Row:
+ *     [0] k1  [1] k2  [2] p1  [3] p2  [4] e00  [5] e01  [6] e10  [7] e11  [8] tx  [9] ty  [10] cx  [11] cy  [12] v1  [13] v2  [14] b0  [15] b2
+ *   k1, k2: radial and p1, p2: tangential distortion coefficients in normalised units (1 = half the frame's width); with the
+ *   formulas below a negative k1 pulls the source position of a corner pixel towards the centre, a positive one pushes it outwards;
+ *   E = A - I: the mounting rotation, scale and shear A minus identity; (tx, ty): the mounting shift [px];
+ *   (cx, cy): the optical centre's offset from the frame centre [px]; v1, v2: vignetting; b0, b2: softness [source px].
+ *   Frame b uses row profile_ids_dev[b] ((B,) int32; NULL: row 0 for every frame).  An id outside [0, P) is the identity profile:
+ *   the all-zero row.
+ * Constants, float32: s = 2.0f / float(W) (the one division, on the host), hw = float(W) * 0.5f, hh = float(H) * 0.5f.
+ * Output pixel (row i, column j), with jf = float(j), if = float(i):
+ *     px = ((jf + 0.5) - hw) - cx              py = ((if + 0.5) - hh) - cy
+ *     xn = px*s   yn = py*s   xx = xn*xn   yy = yn*yn   xy = xn*yn   r2 = xx + yy
+ *     rad = (k1 + k2*r2) * r2
+ *     dx = (xn*rad + (p1 + p1)*xy) + p2*(r2 + (xx + xx))
+ *     dy = (yn*rad + p1*(r2 + (yy + yy))) + (p2 + p2)*xy
+ *     ou = ((e00*px + e01*py) + hw*dx) + tx    ov = ((e10*px + e11*py) + hw*dy) + ty
+ *     u = jf + ou   v = if + ov                 the source position [source px; pixel (i, j) is at (u, v) = (j, i)]
+ *   Softness: if b0 == 0 and b2 == 0:  colour = tap(u, v)
+ *     otherwise  hs = 0.5 * min(max(b0 + b2*r2, 0), 4),  um = u - hs, up = u + hs, vm = v - hs, vp = v + hs,
+ *                colour = (((tap(um, vm) + tap(up, vm)) + tap(um, vp)) + tap(up, vp)) * 0.25    per channel
+ *   tap(u, v), bilinear with edge replicate:
+ *     a u or v that is not finite is replaced by 0
+ *     x0f = floorf(u)  fx = u - x0f  gx = 1 - fx        y0f = floorf(v)  fy = v - y0f  gy = 1 - fy
+ *     x0 = int(min(max(x0f, -1), float(W)))  x1 = x0 + 1, both then clamped to [0, W-1]; y0, y1 likewise with H
+ *     with a = rgb[y0][x0], b = rgb[y0][x1], c = rgb[y1][x0], d = rgb[y1][x1]:   (a*gx + b*fx)*gy + (c*gx + d*fx)*fy    per channel
+ *   Vignetting: g = min(max(1 + (v1 + v2*r2)*r2, 0), 1),   out = g * colour    per channel
+ * The identity profile returns the input bit for bit (u = jf exactly, a tap with zero fractions is (a*1 + b*0)*1 + (..)*0, g = 1;
+ * only a -0 comes out as +0).  A frame depends on its own input and profile alone - not on B or the other frames.
+ * Returns 2 before any HIP call for a NULL rgb_dev, profiles_dev or out_dev, num_profiles < 1, num_frames, height or width <= 0,
+ * out_dev == rgb_dev (a gather cannot run in place - unlike tacex_camera_model), and height x width >= 2^31 or a batch beyond
+ * one launch (2^31 - 1 workgroups). */
+int tacex_lens_model(const float* rgb_dev, const float* profiles_dev, int num_profiles, const int32_t* profile_ids_dev, float* out_dev,
+                     int num_frames, int height, int width, void* stream);
+
+/* tacex_lens_model followed by tacex_camera_model on the gathered colour, in ONE launch: out_dev equals
+ * tacex_camera_model(tacex_lens_model(rgb)) bit for bit, for out_dtype 0 (f32) and 1 (uint8).  The lens arguments are those of
+ * tacex_lens_model (lens_profiles_dev (PL,16), lens_profile_ids_dev), the others those of tacex_camera_model; the Philox
+ * counter is addressed by the group of four consecutive OUTPUT pixels.  Returns 2 for what either of the two refuses
+ * (out_dev == rgb_dev for both dtypes). */
+int tacex_lens_camera_model(const float* rgb_dev, const float* lens_profiles_dev, int num_lens_profiles, const int32_t* lens_profile_ids_dev,
+                            const float* profiles_dev, int num_profiles, const int32_t* profile_ids_dev, uint64_t seed,
+                            uint32_t frame_offset, uint32_t call, void* out_dev, int out_dtype, int num_frames, int height, int width,
+                            void* stream);
+
+/* Points (markers) moved the way tacex_lens_model moves the image.  xy_dev (B,N,2) f64, N = num_points, in ideal image pixels
+ * (x = column, y = row - the convention of marker_motion; a point at (x, y) lies on the centre of pixel (i, j) = (y, x)):
+ * out_dev (B,N,2) f64 is where the lens of frame b's profile shows the point; out_dev may be xy_dev.
+ * The image kernel maps output -> source, a point needs the inverse: with the real-valued displacement (ou, ov)(qx, qy) of the
+ * formulas above (jf = qx, if = qy) evaluated in FLOAT64 (the f32 profile row widened, s = 2.0 / double(W), the same order of
+ * operations), q solves q + displacement(q) = (x, y) by fixed-point iteration from q = (x, y):
+ *     q <- (x, y) - displacement(q),   TACEX_LENS_POINT_ITERATIONS = 24 times, no convergence test.
+ * (The iteration contracts by the displacement's Jacobian norm, about 3 |k1| r2 + 5 |k2| r2^2 + |E|: a third per round in the
+ * corner of a 4:3 frame at k1 = -0.15, where the first guess is 30 px off on 320 columns - below 1e-9 px after 24 rounds.)
+ * Returns 2 before any HIP call for NULL xy_dev, profiles_dev or out_dev, num_profiles < 1, num_frames, num_points, height or
+ * width <= 0. */
+#define TACEX_LENS_POINT_ITERATIONS 24
+int tacex_lens_points(const double* xy_dev, const float* profiles_dev, int num_profiles, const int32_t* profile_ids_dev, double* out_dev,
+                      int num_frames, int num_points, int height, int width, void* stream);
+
 /* Contact force field of the optical path: an elastic-foundation (Winkler) contact model with regularised Coulomb shear, evaluated
  * per pixel of the height map and reduced per env and per cell of a coarse tactile grid, in ONE launch on `stream`
  * (tacex_amd/csrc/contact_field.hip).  B = num_frames, any H, W >= 1.  All per-pixel operations are float32, each rounded on its own

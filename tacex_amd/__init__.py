@@ -6,6 +6,7 @@ from .gelsight_sensor_cfg import GelSightSensorCfg
 from .gelsight_sensor_data import GelSightSensorData
 from .gelsight_sensor_group import GelSightSensorGroup
 from .height_map_source import AffineBodyDepthSource, FemSurfaceDepthSource, FemTractionImage, IndenterHeightMapSource, MeshDepthSource, MeshLibraryDepthSource
+from .lens_model import LensProfile, TactileLensModel
 
-__all__ = ["AffineBodyDepthSource", "CameraProfile", "ContactField", "ContactGel", "GelSightSensor", "GelSightSensorCfg", "GelSightSensorData", "GelSightSensorGroup", "FemSurfaceDepthSource", "FemTractionImage", "IndenterHeightMapSource", "MeshDepthSource",
-           "MeshLibraryDepthSource", "TactileCameraModel", "TactileContactModel", "slip_from_fots"]
+__all__ = ["AffineBodyDepthSource", "CameraProfile", "ContactField", "ContactGel", "GelSightSensor", "GelSightSensorCfg", "GelSightSensorData", "GelSightSensorGroup", "FemSurfaceDepthSource", "FemTractionImage", "IndenterHeightMapSource", "LensProfile", "MeshDepthSource",
+           "MeshLibraryDepthSource", "TactileCameraModel", "TactileContactModel", "TactileLensModel", "slip_from_fots"]

@@ -179,6 +179,9 @@ SIGNATURES = {
     "tacex_philox4x32": (_i, [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "tacex_camera_model": (_i, [_vp, _vp, _i, _vp, C.c_uint64, C.c_uint32, C.c_uint32, _vp, _i, _i, _i, _i, _vp]),
     "tacex_camera_noise_draw": (_i, [C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, _i, c_int32_p]),
+    "tacex_lens_model": (_i, [_vp, _vp, _i, _vp, _vp, _i, _i, _i, _vp]),
+    "tacex_lens_camera_model": (_i, [_vp, _vp, _i, _vp, _vp, _i, _vp, C.c_uint64, C.c_uint32, C.c_uint32, _vp, _i, _i, _i, _i, _vp]),
+    "tacex_lens_points": (_i, [_vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _vp]),
     "tacex_contact_field": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _f, _vp, _i, _i, _vp, _vp, _vp, _i, _i, _i, _vp]),
 }
 

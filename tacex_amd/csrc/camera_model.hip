@@ -20,99 +20,25 @@
 #include <math.h>
 #include <stdint.h>
 
+#include "camera_group.h"
 #include "tacex_hip.h"
 #include "tacex_internal.h"
-#include "tacex_philox.h"
 
 namespace tacex {
-
-// sum of the four bytes of a word (0..1020)
-TACEX_HD inline int32_t camera_byte_sum(uint32_t w) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  return (int32_t)__builtin_amdgcn_sad_u8(w, 0u, 0u);  // v_sad_u8: sum of |byte - 0| in one instruction
-#else
-  return (int32_t)((w & 0xffu) + ((w >> 8) & 0xffu) + ((w >> 16) & 0xffu) + (w >> 24));
-#endif
-}
-
-// The 12 integer draws of one 4-pixel group: sample j = 3 p + c takes word j % 4 of the Philox call with counter
-// (group, j / 4 [+ 4 for the fixed pattern], frame, call [0 for the fixed pattern]); d = byte sum - 510 (mean 0, variance 21845).
-TACEX_HD inline void camera_noise_draw(uint32_t key0, uint32_t key1, uint32_t frame, uint32_t call, uint32_t group, bool fixed_pattern,
-                                       int32_t out[12]) {
-  const uint32_t key[2] = {key0, key1};
-#pragma unroll
-  for (uint32_t q = 0; q < 3; ++q) {
-    const uint32_t ctr[4] = {group, fixed_pattern ? 4u + q : q, frame, fixed_pattern ? 0u : call};
-    uint32_t r[4];
-    philox4x32_10(ctr, key, r);
-#pragma unroll
-    for (int w = 0; w < 4; ++w) out[4 * q + w] = camera_byte_sum(r[w]) - 510;
-  }
-}
-
 namespace {
 
 constexpr int kCameraBlock = 256;
 
+// (the draws, the per-group arithmetic and the stores are in camera_group.h, shared with lens_model.hip)
 struct CameraArgs {
   const float* rgb;          // (B,H,W,3); may alias `out` (float32 output only)
-  const float* profiles;     // (P,16)
-  const int32_t* ids;        // (B,) or nullptr
+  CameraTable cam;           // profiles (P,16), ids (B,) or nullptr, Philox key, frame_offset, call
   void* out;                 // (B,H,W,3) float32 or uint8
   long long npix;            // H W
   unsigned int groups;       // ceil(npix / 4)
   unsigned int blocks_per_frame;
-  int num_profiles;
-  uint32_t key0, key1, frame_offset, call;
 };
 
-struct CameraProfileRow {
-  float m[9], o[3], read, shot, fixed;
-};
-
-__device__ inline CameraProfileRow load_profile(const CameraArgs& a, unsigned int frame) {
-  CameraProfileRow p;
-  const int id = a.ids ? a.ids[frame] : 0;
-  if (id >= 0 && id < a.num_profiles) {
-    const float* __restrict__ row = a.profiles + (size_t)id * 16;
-#pragma unroll
-    for (int k = 0; k < 9; ++k) p.m[k] = row[k];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) p.o[k] = row[9 + k];
-    p.read = row[12]; p.shot = row[13]; p.fixed = row[14];
-  } else {  // an id outside [0, P): the identity profile
-#pragma unroll
-    for (int k = 0; k < 9; ++k) p.m[k] = (k % 4 == 0) ? 1.0f : 0.0f;
-    p.o[0] = p.o[1] = p.o[2] = 0.0f;
-    p.read = p.shot = p.fixed = 0.0f;
-  }
-  return p;
-}
-
-// one group: px[12] (4 pixels x RGB, in place) -> values in [0, 1]
-__device__ inline void camera_group(const CameraArgs& a, const CameraProfileRow& p, uint32_t frame, uint32_t group, float px[12]) {
-  const float S = 0x1.bb688cp-8f;  // float32(1 / sqrt(21845.0)) = 0.006765875, bits 0x3bddb446
-  int32_t d[12], df[12];
-  camera_noise_draw(a.key0, a.key1, frame, a.call, group, false, d);
-  const bool fixed = p.fixed != 0.0f;  // uniform over the workgroup
-  if (fixed) camera_noise_draw(a.key0, a.key1, frame, 0u, group, true, df);
-  const float fs = p.fixed * S, rr = p.read * p.read;
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    const float r = px[3 * q], g = px[3 * q + 1], b = px[3 * q + 2];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      float v = ((p.m[3 * c] * r + p.m[3 * c + 1] * g) + p.m[3 * c + 2] * b) + p.o[c];
-      if (fixed) v = v * (1.0f + fs * (float)df[3 * q + c]);
-      v = fminf(fmaxf(v, 0.0f), 1.0f);
-      const float sig = sqrtf(rr + p.shot * v);
-      v = v + (sig * S) * (float)d[3 * q + c];
-      px[3 * q + c] = fminf(fmaxf(v, 0.0f), 1.0f);
-    }
-  }
-}
-
-__device__ inline uint32_t camera_u8(float v) { return (uint32_t)floorf(255.0f * v + 0.5f); }  // v in [0, 1] -> 0..255
 
 // Vector path: one group per thread, three 16-byte loads, then three 16-byte stores (float32) or one 12-byte store of the packed
 // bytes (uint8).  Requires both base pointers 16-byte aligned and npix % 4 == 0 (every frame then starts 16-byte aligned in the
@@ -122,7 +48,7 @@ __global__ __launch_bounds__(kCameraBlock) void camera_model_vec_kernel(CameraAr
   const unsigned int frame = blockIdx.x / a.blocks_per_frame;
   const unsigned int g = (blockIdx.x - frame * a.blocks_per_frame) * kCameraBlock + threadIdx.x;
   if (g >= a.groups) return;
-  const CameraProfileRow p = load_profile(a, frame);
+  const CameraProfileRow p = load_camera_profile(a.cam, frame);
   const size_t v0 = ((size_t)frame * (size_t)a.npix + (size_t)g * 4) * 3;  // first value of the group in the batch
   const float4* src = reinterpret_cast<const float4*>(a.rgb + v0);
   float px[12];
@@ -131,19 +57,8 @@ __global__ __launch_bounds__(kCameraBlock) void camera_model_vec_kernel(CameraAr
     const float4 t = src[i];
     px[4 * i] = t.x; px[4 * i + 1] = t.y; px[4 * i + 2] = t.z; px[4 * i + 3] = t.w;
   }
-  camera_group(a, p, a.frame_offset + frame, g, px);
-  if constexpr (kU8) {
-    struct alignas(4) Bytes12 { uint32_t x, y, z; };  // one global_store_dwordx3: a wave writes 768 contiguous bytes
-    uint32_t w[3];
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-      w[i] = camera_u8(px[4 * i]) | (camera_u8(px[4 * i + 1]) << 8) | (camera_u8(px[4 * i + 2]) << 16) | (camera_u8(px[4 * i + 3]) << 24);
-    *reinterpret_cast<Bytes12*>(static_cast<uint8_t*>(a.out) + v0) = Bytes12{w[0], w[1], w[2]};
-  } else {
-    float4* dst = reinterpret_cast<float4*>(static_cast<float*>(a.out) + v0);
-#pragma unroll
-    for (int i = 0; i < 3; ++i) dst[i] = make_float4(px[4 * i], px[4 * i + 1], px[4 * i + 2], px[4 * i + 3]);
-  }
+  camera_group(a.cam, p, a.cam.frame_offset + frame, g, px);
+  store_group_vec<kU8>(a.out, v0, px);
 }
 
 // Scalar path: one group per thread, any alignment, any npix (pixels past the frame's end are neither loaded nor stored).
@@ -152,25 +67,15 @@ __global__ __launch_bounds__(kCameraBlock) void camera_model_scalar_kernel(Camer
   const unsigned int frame = blockIdx.x / a.blocks_per_frame;
   const unsigned int g = (blockIdx.x - frame * a.blocks_per_frame) * kCameraBlock + threadIdx.x;
   if (g >= a.groups) return;
-  const CameraProfileRow p = load_profile(a, frame);
+  const CameraProfileRow p = load_camera_profile(a.cam, frame);
   const long long left = a.npix - (long long)g * 4;
   const int n = left < 4 ? (int)left * 3 : 12;  // values of this group inside the frame
   const size_t v0 = ((size_t)frame * (size_t)a.npix + (size_t)g * 4) * 3;
   float px[12];
 #pragma unroll
   for (int i = 0; i < 12; ++i) px[i] = i < n ? a.rgb[v0 + i] : 0.0f;
-  camera_group(a, p, a.frame_offset + frame, g, px);
-  if constexpr (kU8) {
-    uint8_t* dst = static_cast<uint8_t*>(a.out) + v0;
-#pragma unroll
-    for (int i = 0; i < 12; ++i)
-      if (i < n) dst[i] = (uint8_t)camera_u8(px[i]);
-  } else {
-    float* dst = static_cast<float*>(a.out) + v0;
-#pragma unroll
-    for (int i = 0; i < 12; ++i)
-      if (i < n) dst[i] = px[i];
-  }
+  camera_group(a.cam, p, a.cam.frame_offset + frame, g, px);
+  store_group_scalar<kU8>(a.out, v0, px, n);
 }
 
 }  // namespace
@@ -202,9 +107,10 @@ extern "C" int tacex_camera_model(const float* rgb_dev, const float* profiles_de
     return 2;
   }
   CameraArgs a{};
-  a.rgb = rgb_dev; a.profiles = profiles_dev; a.ids = profile_ids_dev; a.out = out_dev;
-  a.npix = npix; a.groups = (unsigned int)groups; a.blocks_per_frame = (unsigned int)bpf; a.num_profiles = num_profiles;
-  a.key0 = (uint32_t)(seed & 0xffffffffull); a.key1 = (uint32_t)(seed >> 32); a.frame_offset = frame_offset; a.call = call;
+  a.rgb = rgb_dev; a.out = out_dev;
+  a.cam.profiles = profiles_dev; a.cam.ids = profile_ids_dev; a.cam.num_profiles = num_profiles;
+  a.cam.key0 = (uint32_t)(seed & 0xffffffffull); a.cam.key1 = (uint32_t)(seed >> 32); a.cam.frame_offset = frame_offset; a.cam.call = call;
+  a.npix = npix; a.groups = (unsigned int)groups; a.blocks_per_frame = (unsigned int)bpf;
   const dim3 grid((unsigned int)(bpf * num_frames)), block(kCameraBlock);
   hipStream_t st = (hipStream_t)stream;
   if (vec && u8) hipLaunchKernelGGL(camera_model_vec_kernel<true>, grid, block, 0, st, a);

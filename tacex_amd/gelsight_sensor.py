@@ -153,6 +153,16 @@ class GelSightSensor(SensorBase):
             raise RuntimeError('camera_image needs "tactile_rgb" in cfg.data_types')
         return model(output["tactile_rgb"], out=out)
 
+    def lens_image(self, lens, camera=None, out: torch.Tensor | None = None) -> torch.Tensor:
+        """The current `data.output["tactile_rgb"]` seen through the sensor's lens: `lens` (a `TactileLensModel` of num_envs frames)
+        applied in one launch on the current stream -> float32.  With `camera` (a `TactileCameraModel`) the camera model runs on the
+        gathered colour in the same launch -> the camera's dtype, what `camera(lens(tactile_rgb))` gives.  `tactile_rgb` itself is
+        left as it is."""
+        output = self.data.output  # (brings outdated buffers up to date)
+        if "tactile_rgb" not in output:
+            raise RuntimeError('lens_image needs "tactile_rgb" in cfg.data_types')
+        return lens(output["tactile_rgb"], out=out, camera=camera)
+
     def contact_field(self, model, slip: torch.Tensor | None = None, image=False):
         """The contact force field of the current `data.output["height_map"]`: `model` (a `TactileContactModel` of num_envs frames)
         evaluated in one launch on the current stream -> `ContactField` (net force and torque, centre of pressure, contact area, slip,
