@@ -990,6 +990,39 @@ int tacex_contact_field(const float* hm_mm_dev, const float* frame_min_dev, cons
                         int grid_rows, int grid_cols, double* record_dev, float* cells_dev, float* image_dev, int num_frames,
                         int height, int width, void* stream);
 
+/* Gel memory of the optical path: the viscoelastic residual imprint of the elastomer.  The height map of this step is rewritten in
+ * place from per-pixel state that remembers past contact, per env, in ONE launch on `stream` (tacex_amd/csrc/gel_memory.hip).
+ * B = num_frames, K = terms (1 or 2 Prony branches, fixed for the life of a state buffer), any H, W >= 1.  All operations are
+ * float32, each rounded on its own (no fused multiply-add), in the order written.
+ *   hm_mm_dev (B,H,W) f32 height map [mm], rewritten in place;  state_dev (B,K,H,W) f32, the branch states m_k, zero after a reset;
+ *   live_dev (B,) int32; coef_dev (P,8) f32, P = num_profiles, row [a1, c1, a2, c2, floor_mm, 0, 0, 0]; frame b uses row
+ *   profile_ids_dev[b] ((B,) int32; NULL: row 0).  An id outside [0, P) is the all-zero row: the map stays as it is and the frame's
+ *   state becomes zero.  The host computes, in float64 and then rounded to float32, a_k = exp(-dt / tau_k) (0 when tau_k == 0) and
+ *   c_k = (1 - a_k) w_k from a profile's time constants tau_k [s], weights w_k >= 0 with w_1 + w_2 <= 1 and the step dt > 0.
+ *   z0_mm = float32((gelpad_to_camera_min_distance + gelpad_height) * 1000), sum and product in double: the pad's rest plane [mm].
+ * Per pixel:
+ *     t = z0 - hm,  d = t > 0 ? t : 0                     penetration [mm]; a NaN gives 0
+ *     m_k' = (a_k * m_k) + (c_k * d)                      k = 1..K: two products and a sum, three roundings
+ *     if d == 0 and m_k' < floor_mm:  m_k' = 0            (the state returns to exactly zero after a release)
+ *     M = m_1' (K = 1),  m_1' + m_2' (K = 2);  r = z0 - M
+ *     hm' = r  if M > 0 and r < hm,  else hm              the imprint never lifts a pixel
+ *   live'[b] = 1 if and only if a state element of frame b is non-zero after the call, else 0.
+ * A frame that enters with live == 0 and has no pixel with d > 0 is left as it is by these statements (zero state, unchanged map):
+ * the kernel moves no state byte for it and leaves live at 0.  live must therefore be 1 for a frame whose state is not all zero.
+ * With sum w <= 1 the imprint is never deeper than the deepest past press; held at d0 for n steps and released for j, a pixel
+ * shows M = sum_k w_k d0 (1 - a_k^n) a_k^j.
+ * Outputs besides hm, state and live: frame_min_dev (B,) f32, indent_mm_dev (B,) f32 and frame_rows_dev (B,4) int32 (nullable) are
+ * exactly what tacex_indentation_depth(hm', gelpad_height_m, gelpad_to_camera_min_distance_m, ...) writes for the rewritten map, for
+ * every geometry (where W % 4 != 0 or H > 2048 the ranges are the whole frame, as there).
+ * One workgroup per frame and no atomics between workgroups: the same inputs give the same bits on every call, alone or in a batch.
+ * 16-byte loads and stores where W % 4 == 0 (hm_mm_dev and state_dev must then be 16-byte aligned), 4-byte ones otherwise.
+ * Returns 2 before any HIP call for a NULL hm_mm_dev, state_dev, live_dev, coef_dev, frame_min_dev or indent_mm_dev, terms not 1 or
+ * 2, num_profiles, num_frames, height or width <= 0, and misaligned buffers at W % 4 == 0. */
+int tacex_gel_memory(float* hm_mm_dev, float* state_dev, int32_t* live_dev, const float* coef_dev, int num_profiles,
+                     const int32_t* profile_ids_dev, float z0_mm, float gelpad_height_m, float gelpad_to_camera_min_distance_m,
+                     float* frame_min_dev, float* indent_mm_dev, int32_t* frame_rows_dev, int num_frames, int height, int width,
+                     int terms, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

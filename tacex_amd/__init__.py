@@ -1,6 +1,7 @@
 """tacex_amd - MI355X-native GelSight tactile-image engine behind TacEx's sensor / simulator plugin API."""
 from .camera_model import CameraProfile, TactileCameraModel
 from .contact_field import ContactField, ContactGel, TactileContactModel, slip_from_fots
+from .gel_memory import GelMemoryProfile, TactileGelMemory
 from .gelsight_sensor import GelSightSensor
 from .gelsight_sensor_cfg import GelSightSensorCfg
 from .gelsight_sensor_data import GelSightSensorData
@@ -8,5 +9,5 @@ from .gelsight_sensor_group import GelSightSensorGroup
 from .height_map_source import AffineBodyDepthSource, FemSurfaceDepthSource, FemTractionImage, IndenterHeightMapSource, MeshDepthSource, MeshLibraryDepthSource
 from .lens_model import LensProfile, TactileLensModel
 
-__all__ = ["AffineBodyDepthSource", "CameraProfile", "ContactField", "ContactGel", "GelSightSensor", "GelSightSensorCfg", "GelSightSensorData", "GelSightSensorGroup", "FemSurfaceDepthSource", "FemTractionImage", "IndenterHeightMapSource", "LensProfile", "MeshDepthSource",
-           "MeshLibraryDepthSource", "TactileCameraModel", "TactileContactModel", "TactileLensModel", "slip_from_fots"]
+__all__ = ["AffineBodyDepthSource", "CameraProfile", "ContactField", "ContactGel", "GelMemoryProfile", "GelSightSensor", "GelSightSensorCfg", "GelSightSensorData", "GelSightSensorGroup", "FemSurfaceDepthSource", "FemTractionImage", "IndenterHeightMapSource", "LensProfile", "MeshDepthSource",
+           "MeshLibraryDepthSource", "TactileCameraModel", "TactileContactModel", "TactileGelMemory", "TactileLensModel", "slip_from_fots"]

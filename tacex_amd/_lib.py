@@ -183,6 +183,7 @@ SIGNATURES = {
     "tacex_lens_camera_model": (_i, [_vp, _vp, _i, _vp, _vp, _i, _vp, C.c_uint64, C.c_uint32, C.c_uint32, _vp, _i, _i, _i, _i, _vp]),
     "tacex_lens_points": (_i, [_vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _vp]),
     "tacex_contact_field": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _f, _vp, _i, _i, _vp, _vp, _vp, _i, _i, _i, _vp]),
+    "tacex_gel_memory": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _f, _f, _f, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
 }
 
 _lib = None

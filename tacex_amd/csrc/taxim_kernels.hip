@@ -23,6 +23,7 @@
 #include "tacex_internal.h"
 #include "taxim_device.h"
 #include "taxim_blur.h"
+#include "frame_rows.h"
 
 namespace tacex {
 
@@ -104,7 +105,7 @@ __global__ __launch_bounds__(1024) void frame_min_kernel(
 // meets the same four columns: their minima stay in registers and reach LDS once.
 // press: indentation depth computed here (indent_out != nullptr, TS:116-129) or given per frame (press_in).
 // ------------------------------------------------------------------------------------------------
-constexpr int kFrameRowsMaxH = 2048;
+// (row / column minima, press depth and ranges: frame_rows.h, shared with the gel memory kernel)
 template <bool FROM_DEPTH>
 __global__ __launch_bounds__(1024) void frame_rows_kernel(
     const float* __restrict__ in, float* __restrict__ hm_out, float* __restrict__ fmin_out,
@@ -124,7 +125,7 @@ __global__ __launch_bounds__(1024) void frame_rows_kernel(
   int* rowmin_i = reinterpret_cast<int*>(rowmin);
   int* colmin_i = reinterpret_cast<int*>(colmin);
   for (int r = threadIdx.x; r < H; r += blockDim.x) rowmin_i[r] = 0x7f800000;  // +inf
-  const bool cols_ok = W <= kFrameRowsMaxH && (blockDim.x % w4) == 0;  // (block-uniform) a thread's float4s all lie in ONE column group
+  const bool cols_ok = frame_rows_cols_ok(W);  // (block-uniform) a thread's float4s all lie in ONE column group
   if (cols_ok)
     for (int c = threadIdx.x; c < W; c += blockDim.x) colmin_i[c] = 0x7f800000;
   float cm[4] = {INFINITY, INFINITY, INFINITY, INFINITY};
@@ -161,15 +162,7 @@ __global__ __launch_bounds__(1024) void frame_rows_kernel(
   };
   // a wave's 64 consecutive float4s lie in at most two rows when a row has >= 64 of them (a few otherwise): reduce inside the wave
   // per row (DPP scan, the minimum lands in lane 63), one LDS atomic per row and wave
-  auto row_minima = [&](float m, int r, int r_first, int r_last) {
-    for (int rr = r_first; rr <= r_last; ++rr) {
-      const float mr = wave_scan_min_lane63(r == rr ? m : INFINITY);
-      if (lane == 63) {
-        if (mr >= 0.0f) atomicMin(&rowmin_i[rr], __float_as_int(mr + 0.0f));  // (+ 0: a -0 must not pass for INT_MIN)
-        else atomicMax(reinterpret_cast<unsigned*>(&rowmin_i[rr]), __float_as_uint(mr));
-      }
-    }
-  };
+  auto row_minima = [&](float m, int r, int r_first, int r_last) { frame_rows_row_minima(rowmin_i, lane, m, r, r_first, r_last); };
   // Batches of NB float4s per thread, their loads issued back to back (clamped index instead of a predicate: one basic block).
 #ifndef TACEX_FRAME_ROWS_NB
 #define TACEX_FRAME_ROWS_NB 4
@@ -215,43 +208,11 @@ __global__ __launch_bounds__(1024) void frame_rows_kernel(
   if (cols_ok) {  // column minima: the same integer atomics on the float pattern as the row minima
     const int cg = (threadIdx.x % w4) * 4;
 #pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      if (cm[k] >= 0.0f) atomicMin(&colmin_i[cg + k], __float_as_int(cm[k] + 0.0f));
-      else atomicMax(reinterpret_cast<unsigned*>(&colmin_i[cg + k]), __float_as_uint(cm[k]));
-    }
+    for (int k = 0; k < 4; ++k) lds_min_f32(&colmin_i[cg + k], cm[k]);
   }
   __syncthreads();
-  if (wave == 0) {
-    float m = INFINITY;
-    for (int r = lane; r < H; r += 64) m = fminf(m, rowmin[r]);
-    m = wave_min(m);
-    float press = 0.0f;
-    if (indent_out) {  // TS:116-129
-      float d = m / 1000.0f - gelpad_dmin;
-      d = d < 0.0f ? 0.0f : d;
-      press = d <= gelpad_h ? (gelpad_h - d) * 1000.0f : 0.0f;
-    } else if (press_in) {
-      press = press_in[b];
-    }
-    int lo = H, hi = -1;
-    for (int r = lane; r < H; r += 64)
-      if (((rowmin[r] - m) - press) < 0.0f) { lo = min(lo, r); hi = max(hi, r); }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { lo = min(lo, __shfl_xor(lo, o, 64)); hi = max(hi, __shfl_xor(hi, o, 64)); }
-    int clo = 0, chi = W - 1;
-    if (cols_ok) {
-      clo = W; chi = -1;
-      for (int c = lane; c < W; c += 64)
-        if (((colmin[c] - m) - press) < 0.0f) { clo = min(clo, c); chi = max(chi, c); }
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) { clo = min(clo, __shfl_xor(clo, o, 64)); chi = max(chi, __shfl_xor(chi, o, 64)); }
-    }
-    if (lane == 0) {
-      fmin_out[b] = m;
-      if (indent_out) indent_out[b] = press;
-      rows_out[4 * b] = lo; rows_out[4 * b + 1] = hi; rows_out[4 * b + 2] = clo; rows_out[4 * b + 3] = chi;
-    }
-  }
+  if (wave == 0)
+    frame_rows_finish(rowmin, colmin, H, W, cols_ok, lane, b, gelpad_h, gelpad_dmin, press_in, fmin_out, indent_out, rows_out);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -979,9 +940,7 @@ hipError_t run_fill_rows(int* rows, int B, int H, int W, hipStream_t st) {  // "
 hipError_t run_frame_rows(const float* in, bool from_depth, float* hm_out, float* fmin, float* indent, uint8_t* cam_u8,
                           const float* press_in, int* rows_out, int B, int H, int W, float near_mm, float far_m, float far_mm,
                           float gelpad_h, float gelpad_dmin, hipStream_t st) {
-  const int w4 = W >> 2;
-  int nt = w4 <= 1024 ? (1024 / w4) * w4 : 1024;  // a multiple of the row's float4 count: every thread keeps to four columns
-  if (nt < 512 || (nt & 63)) nt = 1024;           // (whole waves, enough of them; else the kernel reports every column as contact)
+  const int nt = frame_rows_block_threads(W);
   if (from_depth)
     hipLaunchKernelGGL(frame_rows_kernel<true>, dim3(B), dim3(nt), 0, st, in, hm_out, fmin, indent, cam_u8, press_in, rows_out,
                        H, W, near_mm, far_m, far_mm, gelpad_h, gelpad_dmin);

@@ -56,6 +56,7 @@ class GelSightSensor(SensorBase):
         self._camera_depth_m = None
         self._height_map_version = 0
         self._group = None  # set by GelSightSensorGroup: the member's buffers are views of the group's core sensor
+        self._gel_memory = None  # set_gel_memory: a TactileGelMemory applied to every freshly filled height map
         # SensorBase sets _num_envs / _device, which the simulator constructors read
         super().__init__(self.cfg)
 
@@ -144,6 +145,22 @@ class GelSightSensor(SensorBase):
         if self._group is not None:
             raise RuntimeError("a grouped sensor takes its height map from the camera depth or set_height_map (one source per group)")
         self._height_map_source = source
+
+    def set_gel_memory(self, model):
+        """Attach a `TactileGelMemory` of num_envs frames at the camera resolution (None: detach).  Every update then fills the height
+        map as before (camera depth pass, height-map source or `set_height_map`) and lets the model rewrite it in place with the
+        gel's residual imprint; the provider's frame minimum, indentation depth and contact ranges describe the rewritten map, so
+        `tactile_rgb`, `indentation_depth`, `contact_field()`, `lens_image()` and `camera_image()` all see the imprint.  The depth
+        pass is not deferred into the render while a model is attached; the uint8 `camera_depth` stays the raw camera image.
+        `reset(env_ids)` resets the model's state of those envs.  A caller of `set_height_map` provides a fresh map every step."""
+        if self._group is not None:
+            raise RuntimeError("a grouped sensor has no gel memory of its own: its height map is a view of the group's (one model per group)")
+        if model is not None:
+            Wc, Hc = self.camera_resolution
+            shape = (self._num_envs, Hc, Wc)
+            if (model.num_envs, model.height, model.width) != shape:
+                raise ValueError(f"gel memory is for {(model.num_envs, model.height, model.width)} (num_envs, H, W), the sensor's height map is {shape}")
+        self._gel_memory = model
 
     def camera_image(self, model, out: torch.Tensor | None = None) -> torch.Tensor:
         """The current `data.output["tactile_rgb"]` as the sensor's camera would deliver it: `model` (a `TactileCameraModel` of
@@ -234,6 +251,8 @@ class GelSightSensor(SensorBase):
             self.gelpad_obj.reset(env_ids)
         if env_ids is None:
             env_ids = self._ALL_INDICES
+        if self._gel_memory is not None:
+            self._gel_memory.reset(env_ids)
         self._indentation_depth[env_ids] = 0
         self._data.output["height_map"][env_ids] = 0
         self._height_map_version += 1
@@ -365,7 +384,7 @@ class GelSightSensor(SensorBase):
         """True when the optical simulator renders in this update from exactly the buffers the depth pass fills: the pass is then handed
         to the render (`tacex_taxim_defer_height_map_from_depth`), which runs it chunk by chunk beside the band levels of the previous
         chunk instead of as one launch ahead of them.  `TACEX_DEFER_DEPTH=0` keeps the two launches apart (A/B)."""
-        if _DEFER_DEPTH is False:
+        if _DEFER_DEPTH is False or self._gel_memory is not None:  # (the gel memory rewrites the map between the pass and the render)
             return False
         sim = self.optical_simulator
         if sim is None or "tactile_rgb" not in self.cfg.data_types or not hasattr(sim, "defer_height_map_from_depth"):
@@ -376,6 +395,34 @@ class GelSightSensor(SensorBase):
         return tuple(self._data.output["height_map"].shape[1:]) == (H, W)
 
     def _get_height_map(self, defer: bool = False):
+        if self._gel_memory is None:
+            return self._fill_height_map(defer)
+        # gel memory: the plain fill first, then the model on the map it left - frame minimum, indentation depth and contact ranges are
+        # redone by the same launch for the rewritten map
+        hm = self._fill_height_map(False)
+        cam_current = getattr(self, "_camera_depth_version", -1) == self._height_map_version
+        sim = self._fused_targets()
+        rows = getattr(sim, "_frame_rows", None)
+        if sim is not None:
+            fmin, indent = sim._frame_min, sim._indentation_depth
+        else:
+            if getattr(self, "_gm_scratch", None) is None:
+                self._gm_scratch = (torch.zeros((self._num_envs,), device=hm.device), torch.zeros((self._num_envs,), device=hm.device))
+            fmin, indent = self._gm_scratch
+        cfg = sim.cfg if sim is not None else self.cfg.optical_sim_cfg
+        self._gel_memory.apply(hm, fmin, indent, rows, gelpad_height=float(getattr(cfg, "gelpad_height", 0.0)),
+                               gelpad_to_camera_min_distance=float(getattr(cfg, "gelpad_to_camera_min_distance", 0.0)))
+        self._height_map_version += 1
+        if sim is not None:
+            sim._frame_min_version = self._height_map_version
+            sim._indent_version = self._height_map_version
+            if rows is not None:
+                sim._frame_rows_version = self._height_map_version
+        if cam_current:  # (the camera bytes of this depth image are in place: _get_camera_depth must not run the pass again)
+            self._camera_depth_version = self._height_map_version
+        return hm
+
+    def _fill_height_map(self, defer: bool = False):
         src = getattr(self, "_height_map_source", None)
         if src is not None:  # analytic source: height map, frame minimum and indentation depth in one launch
             hm = self._data.output["height_map"]
