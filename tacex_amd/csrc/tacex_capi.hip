@@ -158,14 +158,17 @@ int tacex_taxim_create(int device_id, const tacex_taxim_params* p, tacex_taxim_c
       // table 0 (V-pass): k-step ks contracts window index u = 4 ks + g; table 1 (H-pass): u = mfma_h_window_col(KS, g, ks)
       // (four consecutive k-steps = four consecutive window columns = one ds_read_b128, the chunks dealt out to the lane
       // groups so that the read is free of LDS bank conflicts); weight = w[u - RA - i + R], 0 outside the band
-      const int K = p->ksize_w[l], R = (K - 1) / 2, RA = (R + 7) & ~7, ks = (16 + 2 * RA) / 4;
-      std::vector<float> tl((size_t)2 * ks * 64, 0.0f);
+      // Both tables are a re-indexing of the zero-padded filter pad[] (mfma_wpad_index), which follows them in the same array:
+      // the WLDS instantiations copy pad[] into LDS and read their weights from there with the same index function.
+      const int K = p->ksize_w[l], R = (K - 1) / 2, RA = (R + 7) & ~7, ks = (16 + 2 * RA) / 4, npad = mfma_wpad_floats(K);
+      std::vector<float> tl((size_t)2 * ks * 64 + npad, 0.0f);
+      float* pad = tl.data() + (size_t)2 * ks * 64;
+      for (int t = 0; t < K; ++t) pad[mfma_wpad_tap0(K) + t] = p->taps_w[l][t];
       for (int tab = 0; tab < 2; ++tab)
         for (int kk = 0; kk < ks; ++kk)
           for (int ln = 0; ln < 64; ++ln) {
             const int u = tab == 0 ? 4 * kk + (ln >> 4) : mfma_h_window_col(ks, ln >> 4, kk);
-            const int t = u - RA - (ln & 15) + R;
-            if (t >= 0 && t < K) tl[((size_t)tab * ks + kk) * 64 + ln] = p->taps_w[l][t];
+            tl[((size_t)tab * ks + kk) * 64 + ln] = pad[mfma_wpad_index(u, ln & 15)];
           }
       rc |= upload(c, tl.data(), tl.size(), &c->levels[l].taps_mfma_dev);
     }
@@ -783,6 +786,12 @@ static bool band_lean() {
   static const bool v = !(getenv("TACEX_BAND_LEAN") && atoi(getenv("TACEX_BAND_LEAN")) == 0);
   return v;
 }
+// TACEX_BAND_WLDS: 1 (default) = the matrix-core levels read their Toeplitz weights from a copy of the level's filter in LDS and fetch the
+// H-pass operands ahead of the barrier (BlurArgs::wlds), 0 = the lane-indexed weight tables from global memory
+static bool band_wlds() {
+  static const bool v = !(getenv("TACEX_BAND_WLDS") && atoi(getenv("TACEX_BAND_WLDS")) == 0);
+  return v;
+}
 
 // The band levels of a pass, chunk by chunk: fork onto the level streams, the deferred depth pass, the early item order, the join.
 // *out: what the last level wrote (nullptr without band levels); *order_done: the tail's item order has been issued.
@@ -852,7 +861,8 @@ static int run_band_levels(tacex_taxim_ctx* c, const Pass& p, const PassState& s
         unread = s.stream_tail && stream_tail_range_aware(c->levels);
       StageTimer t(c, cst, 1 + l);
       HIP_TRY(run_blur_level(c->levels[l], src ? src + b0 * npix : nullptr, q.hm, c->gel_dev, s.sa + b0, s.sb + b0, s.pd + b0, dst + b0 * npix,
-                             s.tmp, last ? q.mask_out : nullptr, q.B, c->H, c->W, c->contact_scale, last ? 0 : 1, l == 0, cst, q.rows, grow, grow_x, lean, unread),
+                             s.tmp, last ? q.mask_out : nullptr, q.B, c->H, c->W, c->contact_scale, last ? 0 : 1, l == 0, cst, q.rows, grow, grow_x, lean, unread,
+                             band_wlds()),
               "blur level");
       grow += (c->levels[l].kh - 1) / 2;
       grow_x += (c->levels[l].kw - 1) / 2;

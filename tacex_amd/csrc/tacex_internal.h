@@ -11,7 +11,8 @@ struct LevelDesc {
   bool same_taps = false;  // taps_w == taps_h element-wise (sigma_w == sigma_h): tuned band kernel eligible
   float* taps_w_dev = nullptr;
   float* taps_h_dev = nullptr;
-  float* taps_mfma_dev = nullptr; // per-lane band weights for blur_mfma_kernel: [V | H][(16 + 2 RA)/4 k-steps][64 lanes]
+  float* taps_mfma_dev = nullptr; // per-lane band weights for blur_mfma_kernel: [V | H][(16 + 2 RA)/4 k-steps][64 lanes], followed by
+                                  // the zero-padded filter they index ([mfma_wpad_floats(K)], mfma_wpad_index) for its WLDS instantiations
   float* taps_pad_dev = nullptr;  // zero-padded taps for the looped band kernel: [16 zeros | K taps | 48 zeros]
 };
 
@@ -58,7 +59,7 @@ hipError_t run_blur_level(const LevelDesc& lv, const float* src, const float* hm
                           const float* sa, const float* sb, const float* pd, float* dst, float* tmp,
                           uint8_t* mask_out, int B, int H, int W, float contact_scale, int restore,
                           bool first, hipStream_t st, const int* rows_ext = nullptr, int ext_grow = 0, int ext_grow_x = 0, bool lean = false,
-                          bool zero_bands_unread = false);
+                          bool zero_bands_unread = false, bool wlds = false);
 bool frame_rows_supported(int H, int W);
 hipError_t run_fill_rows(int* rows, int B, int H, int W, hipStream_t st);
 hipError_t run_frame_rows(const float* in, bool from_depth, float* hm_out, float* fmin, float* indent, uint8_t* cam_u8,
@@ -100,6 +101,14 @@ __host__ __device__ inline int mfma_h_window_col(int KS, int g, int ks) {
 }
 // tile row that lane i (= lane & 15) of the H-pass reads, restores and stores
 __host__ __device__ inline int mfma_h_row(int i) { return (i >= 4 && i < 12) ? 2 * (i - 4) + 1 : 2 * (i < 4 ? i : i - 8); }
+// Band weights of blur_mfma_kernel as a re-indexing of the level's 1-D filter: the weight of window index u (V-pass: 4 ks + g,
+// H-pass: mfma_h_window_col(KS, g, ks)) for tile row / column i = lane & 15 is w[u - RA - i + R], zero outside [0, K).  The
+// zero-padded copy pad[] holds w[0] at mfma_wpad_tap0(K), so that weight = pad[mfma_wpad_index(u, i)] for every u in [0, WIN) and
+// i in [0, 16): 2 RA + 31 entries, rounded up to a multiple of 16 floats.  ONE function for the host table builder
+// (tacex_taxim_create) and for the kernel's LDS reads (WLDS instantiations).
+__host__ __device__ constexpr inline int mfma_wpad_index(int u, int i) { return u - i + 15; }
+__host__ __device__ constexpr inline int mfma_wpad_tap0(int K) { return (((K - 1) / 2 + 7) & ~7) - (K - 1) / 2 + 15; }
+__host__ __device__ constexpr inline int mfma_wpad_floats(int K) { return (2 * (((K - 1) / 2 + 7) & ~7) + 31 + 15) & ~15; }
 
 // fused tail (taxim_tail.hip): trailing small-kernel levels + shading in one LDS-tiled kernel
 int tail_levels(const LevelDesc* lv, int n_levels, int H, int W);

@@ -15,7 +15,7 @@ struct BlurArgs {
   const float* pdepth;  // (B,) P
   float* dst;           // (B,H,W)
   uint8_t* mask_out;    // (B,H,W) nullable
-  const float* taps;    // (K,)
+  const float* taps;    // (K,); MFMA kernel: the level's taps_mfma_dev
   int H, W, B;
   int pitch;            // LDS row pitch in float2 units (even, == 2 mod 32)
   int padx;             // left padding in float2 units (even, >= (K-1)/2)
@@ -30,6 +30,9 @@ struct BlurArgs {
                         // ext_grow / ext_grow_x for a later level's input) fetch nothing and use the +0.0f / "no contact" they would have read
   int zero_bands_unread;  // with `lean`: every reader of dst knows the skipped bands from rows_ext and never loads them - a skipped band
                           // returns without storing its zeros (dst keeps whatever it held there)
+  int wlds;             // MFMA kernel: launch the WLDS instantiation - band weights from the zero-padded filter behind the lane tables in
+                        // `taps`, copied into LDS (host side of the switch; launch_mfma_tiles sets wlds_shared)
+  int wlds_shared;      // WLDS: 1 = one copy of the filter per workgroup behind a barrier, 0 = one per wave, no barrier
 };
 
 bool mfma_supported(int k, bool first, int H, int W);

@@ -987,7 +987,8 @@ bool blur_level_single_kernel(const LevelDesc& lv, bool first, int H, int W) { r
 hipError_t run_blur_level(const LevelDesc& lv, const float* src, const float* hm, const float* gel,
                           const float* sa, const float* sb, const float* pd, float* dst, float* tmp,
                           uint8_t* mask_out, int B, int H, int W, float contact_scale, int restore,
-                          bool first, hipStream_t st, const int* rows_ext, int ext_grow, int ext_grow_x, bool lean, bool zero_bands_unread) {
+                          bool first, hipStream_t st, const int* rows_ext, int ext_grow, int ext_grow_x, bool lean, bool zero_bands_unread,
+                          bool wlds) {
   const BlurRoute route = blur_level_route(lv, first, H, W);
   if (route == kRouteMfma) {
     BlurArgs a{};
@@ -996,7 +997,7 @@ hipError_t run_blur_level(const LevelDesc& lv, const float* src, const float* hm
     a.lean = (lean && a.rows_ext) ? 1 : 0; a.zero_bands_unread = (a.lean && zero_bands_unread) ? 1 : 0;
     a.gel = lv.gel_zero ? nullptr : gel;  // all-zero gel map (GelSight Mini): no gel loads - half of level 0's V-pass reads
     a.dst = dst; a.mask_out = mask_out; a.taps = lv.taps_mfma_dev; a.H = H; a.W = W; a.B = B;
-    a.contact_scale = contact_scale; a.restore = restore;
+    a.contact_scale = contact_scale; a.restore = restore; a.wlds = wlds ? 1 : 0;
     return dispatch_mfma(lv.kw, first, a, st);
   }
   if (route == kRouteBandLoop384 || route == kRouteBandLoop640) {

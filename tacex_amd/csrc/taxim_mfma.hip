@@ -26,6 +26,12 @@ namespace tacex {
 //            and the 16-byte global stores run straight from the accumulators.
 // Band weights per lane (0 outside the band), i = lane & 15:
 //   V: wl[ks] = w[4 ks + g - RA - i + R]    H: wl[ks] = w[KS g + ks - RA - i + R]     (host tables, [2][KS][64])
+// WLDS: the two tables are a re-indexing of ONE zero-padded copy of the filter (mfma_wpad_index, tacex_internal.h), 384 B at
+// K = 61 against 10 KB of tables.  The workgroup copies it into LDS behind `mid` (one or two 4-byte loads per lane) and reads
+// every wl[ks] from there - many lanes per word, a broadcast - so that the V-pass window and the restore are the only vector
+// loads left.  Same f32 weights, same MFMA order: bit-identical.  One copy per WAVE (no barrier: a wave's LDS operations complete
+// in order) where that keeps the workgroups per CU, one per WORKGROUP behind a barrier otherwise (BlurArgs::wlds_shared).  The
+// press depth and, where the registers allow (HPRE), the H-pass weights are fetched ahead of the barrier: neither depends on `mid`.
 // Useful MACs / issued MACs = K / WIN (0.76 at K = 61, 0.69 at 33, 0.53 at 17).
 // ------------------------------------------------------------------------------------------------
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -49,9 +55,10 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 // (stored +0.0f); for the height map the operand J = min(S, 0) = +0.0f is selected / the mask bit cleared by the same predicate
 // (S >= 0 outside the rectangle: it comes from the same float32 expression).  No branch encloses a load, an LDS read or an MFMA:
 // the instruction stream is the one of the full kernel with buffer_load in place of global_load.
-template <int K, bool FIRST, int NTILE, bool GZ, bool LEAN>
+template <int K, bool FIRST, int NTILE, bool GZ, bool LEAN, bool WLDS>
 __global__ __launch_bounds__(640) void blur_mfma_kernel(BlurArgs a) {
   static_assert(GZ || !LEAN, "the lean loads need J = min(S, 0)");
+  static_assert(!WLDS || !TACEX_MFMA_H_CONSEC, "WLDS reads the H weights in the default contraction map");
   constexpr unsigned kNoLoad = 0x80000000u;  // buffer offset beyond every frame: the range check drops the load, the lane reads 0
   constexpr int TH = 16 * NTILE;
   constexpr int R = (K - 1) / 2, RA = (R + 7) & ~7, WIN = 16 + 2 * RA, KS = WIN / 4;
@@ -132,12 +139,50 @@ __global__ __launch_bounds__(640) void blur_mfma_kernel(BlurArgs a) {
     }
   }
 
+  // WLDS: the zero-padded filter (behind the lane tables in a.taps) into LDS behind `mid`; index clamped, not predicated: the
+  // lanes beyond the last entry store that entry again
+  const float* wts = nullptr;
+  if constexpr (WLDS) {
+    constexpr int NP = mfma_wpad_floats(K);
+    float* wcopy = mid + TH * pitch + (a.wlds_shared ? 0 : wid * NP);
+    const float* __restrict__ wpad = a.taps + 2 * KS * 64;
+#pragma unroll
+    for (int j = 0; j < (NP + 63) / 64; ++j) {
+      const int idx = min(lane + 64 * j, NP - 1);
+      wcopy[idx] = wpad[idx];
+    }
+    if (a.wlds_shared) __syncthreads();  // (workgroup-uniform; every wave that got here takes part, whatever its v_need / h_need)
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wts = wcopy + mfma_wpad_index(0, li);
+  }
+  // H-pass operands that do not depend on `mid`: WLDS fetches the press depth ahead of the barrier (behind the V-pass chain).
+  // HPRE: the weights too, where the instantiation stays within 64 VGPRs with them live across the barrier (hipcc 7.x, gfx950: lean
+  // k = 17 / 15 / 9 65 and lean non-first k = 61 67 with them, 61 / 60 without; k = 117 holds 36 of them: 71).  The four restore loads
+  // ahead of the barrier cost 68 / 68 / 78 / 98 VGPRs at k = 17 / 33 / 61 / 117 (16 more registers live through the whole H chain,
+  // which otherwise takes them over from the weights it has used up): not built.
+#ifndef TACEX_MFMA_WLDS_HPRE
+#define TACEX_MFMA_WLDS_HPRE 1  // (A/B hook: 0 = every instantiation reads the H weights behind the barrier)
+#endif
+  constexpr bool HPRE = WLDS && TACEX_MFMA_WLDS_HPRE && (LEAN ? (K == 33 || (K == 61 && FIRST)) : K <= 61);
+  float wh[WLDS ? KS : 1];
+  float pd_pre = 0.0f;
+  auto read_wh = [&]() {
+    static_for<0, KS / 4>([&](auto mc) {
+      constexpr int m = decltype(mc)::value;
+      const float* wq = wts + mfma_h_window_col(KS, g, 4 * m);  // four consecutive k-steps = four consecutive window columns
+      wh[4 * m] = wq[0]; wh[4 * m + 1] = wq[1]; wh[4 * m + 2] = wq[2]; wh[4 * m + 3] = wq[3];
+    });
+  };
+
   // ---- V-pass ----
   {
     float wl[KS];
     static_for<0, KS>([&](auto kc) {
       constexpr int ks = decltype(kc)::value;
-      wl[ks] = a.taps[ks * 64 + lane];
+      if constexpr (WLDS) wl[ks] = wts[4 * ks + g];
+      else wl[ks] = a.taps[ks * 64 + lane];
     });
     f32x4 acc[NTILE][4];
 #pragma unroll
@@ -202,6 +247,10 @@ __global__ __launch_bounds__(640) void blur_mfma_kernel(BlurArgs a) {
       });
     });
     }
+    if constexpr (WLDS) {  // behind the V-pass chain (its weights are dead), ahead of the barrier: the latency overlaps the wait
+      if constexpr (HPRE) read_wh();
+      pd_pre = a.pdepth[frame];
+    }
     // D layout: column (lane & 15), row 4 (lane >> 4) + reg.  The lanes next to the left / right image border also write
     // the mirrored x-padding (torch 'reflect': position -c <- c, (W-1)+c <- (W-1)-c, c = 1..RA), so one barrier suffices.
     const int cx = c0 + 4 * li;
@@ -228,11 +277,13 @@ __global__ __launch_bounds__(640) void blur_mfma_kernel(BlurArgs a) {
   // ---- H-pass + masked restore: per tile, four adjacent 16-column blocks per wave (four independent chains) ----
   {
     float wl[KS];
+    if constexpr (WLDS && !HPRE) read_wh();
     static_for<0, KS>([&](auto kc) {
       constexpr int ks = decltype(kc)::value;
-      wl[ks] = a.taps[((TACEX_MFMA_H_CONSEC ? 0 : KS) + ks) * 64 + lane];
+      if constexpr (WLDS) wl[ks] = wh[ks];
+      else wl[ks] = a.taps[((TACEX_MFMA_H_CONSEC ? 0 : KS) + ks) * 64 + lane];
     });
-    const float thr = -a.pdepth[frame] * a.contact_scale;  // TT:459
+    const float thr = -(WLDS ? pd_pre : a.pdepth[frame]) * a.contact_scale;  // TT:459
     if (!h_need) {  // (wave-uniform) exactly zero output, no contact pixel in these columns
 #pragma unroll
       for (int t = 0; t < NTILE; ++t) {
@@ -331,9 +382,38 @@ static hipError_t launch_mfma_tiles(BlurArgs a, int row0, int nbands, hipStream_
   if (((a.pitch >> 2) & 1) == 0) a.pitch += 4;
   static const size_t lds_pad = getenv("TACEX_MFMA_LDS_PAD") ? (size_t)atoi(getenv("TACEX_MFMA_LDS_PAD")) * 1024 : 0;  // occupancy A/B hook
   const size_t lds = (size_t)TH * a.pitch * sizeof(float) + lds_pad;
-  auto kern = blur_mfma_kernel<K, FIRST, NTILE, GZ, LEAN>;
+  auto kern = blur_mfma_kernel<K, FIRST, NTILE, GZ, LEAN, false>;
   static size_t granted[64] = {};
   if (hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), lds, granted); e != hipSuccess) return e;
+  if constexpr (!TACEX_MFMA_H_CONSEC) {
+    if (a.wlds) {
+      // WLDS: the filter copy behind `mid` - one per wave where the runtime still places as many workgroups on a CU as of the
+      // instantiation without it (and no fewer than with one copy), else one per workgroup (a barrier more), else the lane tables.
+      // Decided once per device and width.
+      auto kern_w = blur_mfma_kernel<K, FIRST, NTILE, GZ, LEAN, true>;
+      const size_t wbytes = (size_t)mfma_wpad_floats(K) * sizeof(float);
+      const size_t lds_w[3] = {0, lds + (size_t)(a.W / 64) * wbytes, lds + wbytes};
+      static size_t granted_w[64] = {};
+      static struct { int W, mode; } plan[64] = {};
+      int dev = 0;
+      if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
+      if (plan[dev].W != a.W) {
+        if (hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(kern_w), lds_w[1], granted_w); e != hipSuccess) return e;
+        int n_old = 0, n_wave = 0, n_wg = 0;
+        hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n_old, reinterpret_cast<const void*>(kern), a.W, lds);
+        if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n_wave, reinterpret_cast<const void*>(kern_w), a.W, lds_w[1]);
+        if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n_wg, reinterpret_cast<const void*>(kern_w), a.W, lds_w[2]);
+        if (e != hipSuccess) return e;
+        plan[dev].mode = (n_wave >= n_old && n_wave >= n_wg) ? 1 : (n_wg >= n_old ? 2 : 0);
+        plan[dev].W = a.W;
+      }
+      if (const int mode = plan[dev].mode) {
+        a.wlds_shared = mode == 2 ? 1 : 0;
+        hipLaunchKernelGGL(kern_w, dim3(nbands * a.B), dim3(a.W), lds_w[mode], st, a);
+        return hipGetLastError();
+      }
+    }
+  }
   hipLaunchKernelGGL(kern, dim3(nbands * a.B), dim3(a.W), lds, st, a);
   return hipGetLastError();
 }
