@@ -128,9 +128,11 @@ __device__ __forceinline__ float atan_unit(float x) {
   return p * x;
 }
 
-// atan(t), t >= 0
+// atan(t), t >= 0.  t == 1 lies exactly on the edge of magnitude bins 61 | 62 ((nb - 1) % 2 == 0) and takes the upper branch:
+// atan_unit(1) rounds to one ulp BELOW pi/4 (bin 61), pi/2 - atan_unit(1) to one ulp above float32(pi/4) - bin 62, which is where
+// the reference's float32 atan(1) = float32(pi/4) > pi/4 puts it (tests/test_taxim_bins_gpu.py, special point "t 1").
 __device__ __forceinline__ float atan_pos(float t) {
-  const bool big = t > 1.0f;
+  const bool big = t >= 1.0f;
   const float p = atan_unit(big ? __builtin_amdgcn_rcpf(t) : t);
   return big ? 1.57079632679489662f - p : p;
 }
