@@ -7,40 +7,16 @@ calls in a row, the variants alternating over `--reps` rounds after a warm-up.  
   - the same model written in torch ops (record sums and cells by index_add; not bit-equal, a cost comparison).
 
   --out FILE   also write the table as markdown."""
-import argparse
-import sys
-from pathlib import Path
+import numpy as np
+import torch
+from _bench_util import COPY_TBS, copy_ms, emit, parse_args, repeated, rounds, table
 
-ap = argparse.ArgumentParser()
-ap.add_argument("--repo", default=str(Path(__file__).resolve().parent.parent))
-ap.add_argument("--frames", type=int, default=2048)
-ap.add_argument("--height", type=int, default=240)
-ap.add_argument("--width", type=int, default=320)
-ap.add_argument("--calls", type=int, default=100)
-ap.add_argument("--reps", type=int, default=5)
-ap.add_argument("--torch-calls", type=int, default=5, help="calls per timing of the torch restatement (it is tens of times slower)")
-ap.add_argument("--out", default=None)
-a = ap.parse_args()
-sys.path.insert(0, a.repo)
-
-import numpy as np  # noqa: E402
-import torch  # noqa: E402
+a = parse_args(calls=100, torch_calls=5, torch_help="calls per timing of the torch restatement (it is tens of times slower)")
 
 from tacex_amd import ContactGel, TactileContactModel, _lib  # noqa: E402
 from tacex_amd.utils.synthetic import PIXMM, dense_contact_depth_maps, synthetic_depth_maps  # noqa: E402
 
-COPY_TBS = 6.29  # measured float4-copy rate of one MI355X (HBM3E, 79 % of the 8.0 TB/s datasheet peak)
 GRID = (9, 11)
-
-
-def timed(fn, calls):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(calls):
-        fn()
-    e1.record()
-    e1.synchronize()
-    return e0.elapsed_time(e1) / calls  # ms per call
 
 
 def depth_pass(hm):
@@ -103,14 +79,8 @@ def main():
         variants[f"{tag}: record + cells + image, whole frames"] = lambda hm=hm, f=fmin, i=ind: model(hm, f, i, slip=slip, image=image)
     hm0 = inputs["dense contact"]
     variants["copy of the height maps (copy_, read + write)"] = lambda: copy_dst.copy_(hm0)
-    for fn in variants.values():
-        timed(fn, 5)
-    ms = {k: [] for k in variants}
-    for _ in range(a.reps):
-        for k, fn in variants.items():
-            ms[k].append(timed(fn, a.calls))
-    read_ms = B * H * W * 4 / (COPY_TBS * 1e12) * 1e3
-    rows_out = [(k, float(np.median(v)), float(min(v)), float(max(v)), read_ms / float(np.median(v))) for k, v in ms.items()]
+    read_ms = copy_ms(B * H * W * 4)
+    rows_out = [(k, v, f"{read_ms / float(np.median(v)):.2f}") for k, v in rounds(variants, a.calls, a.reps, 5).items()]
     # the torch restatement (one gel for every env, allocates its temporaries like the code a user would write)
     ci = (torch.arange(H, device=dev) * GRID[0]) // H
     cj = (torch.arange(W, device=dev) * GRID[1]) // W
@@ -118,10 +88,8 @@ def main():
     for tag, hm in inputs.items():
         fmin, ind, _ = depth_pass(hm)
         fn = lambda hm=hm, f=fmin, i=ind: torch_restatement(hm, f, i, (3.0e4, 1.2e4, 0.6), slip, PIXMM, cell_of_pixel, GRID[0] * GRID[1])  # noqa: E731
-        timed(fn, 1)
-        v = [timed(fn, a.torch_calls) for _ in range(a.reps)]
-        rows_out.append((f"{tag}: torch restatement (force, centre of pressure, counts, cells)", float(np.median(v)), float(min(v)), float(max(v)),
-                         read_ms / float(np.median(v))))
+        v = repeated(fn, a.torch_calls, a.reps, 1)
+        rows_out.append((f"{tag}: torch restatement (force, centre of pressure, counts, cells)", v, f"{read_ms / float(np.median(v)):.2f}"))
     # where the time goes: the raw entry point (outputs allocated once) on the first 256 / 1024 / all frames, without and with cells
     lib = _lib.load_library()
     st = _lib.current_stream_handle(torch.device(dev))
@@ -136,23 +104,18 @@ def main():
                 fn = lambda c=c, r=r, hm=hm, f=fmin, i=ind, nb=nb: lib.tacex_contact_field(  # noqa: E731
                     _lib.ptr(hm), _lib.ptr(f), _lib.ptr(i), _lib.ptr(model.gels), model.num_gels, _lib.ptr(model.gel_ids), _lib.ptr(slip), PIXMM,
                     _lib.ptr(r), GRID[0], GRID[1], _lib.ptr(rec), _lib.ptr(c), 0, nb, H, W, st)
-                timed(fn, 5)
-                row.append(float(np.median([timed(fn, a.calls) for _ in range(3)])))
+                row.append(float(np.median(repeated(fn, a.calls, 3, 5))))
             scale.append(row)
-    lines = ["| case | median ms | min | max | one read of the height maps / median |", "|---|---|---|---|---|"]
-    lines += [f"| {k} | {m:.3f} | {lo:.3f} | {hi:.3f} | {fr:.2f} |" for k, m, lo, hi, fr in rows_out]
+    lines = table(["one read of the height maps / median"], rows_out)
     notes = [info[t] for t in inputs]
     lines += ["", "Raw entry point, outputs allocated once, median of 3 timings, ms:", "",
               "| frames | record only | record only, rectangles | record + cells | record + cells, rectangles |", "|---|---|---|---|---|"]
     lines += [f"| {r[0]} | {r[1]:.3f} | {r[2]:.3f} | {r[3]:.3f} | {r[4]:.3f} |" for r in scale]
-    print("\n".join(lines + [""] + notes), flush=True)
-    if a.out:
-        head = (f"# Contact force field: one call on {B} frames of {W} x {H}, grid {GRID[0]} x {GRID[1]}\n\n{a.calls} calls per timing between two hipEvents, "
-                f"{a.reps} alternating rounds (median, min, max of the rounds), one MI355X; the torch restatement {a.torch_calls} calls per timing.  "
-                f"The last column is derived: one read of the height maps ({B * H * W * 4 / 1e9:.3f} GB) at the {COPY_TBS} TB/s float4-copy rate takes "
-                f"{read_ms:.3f} ms; the column is that time over the measured median (1 = the call costs one read of the height maps).\n\n")
-        Path(a.out).parent.mkdir(parents=True, exist_ok=True)
-        Path(a.out).write_text(head + "\n".join(lines) + "\n\n" + "\n".join(f"- {n}" for n in notes) + "\n")
+    head = (f"# Contact force field: one call on {B} frames of {W} x {H}, grid {GRID[0]} x {GRID[1]}\n\n{a.calls} calls per timing between two hipEvents, "
+            f"{a.reps} alternating rounds (median, min, max of the rounds), one MI355X; the torch restatement {a.torch_calls} calls per timing.  "
+            f"The last column is derived: one read of the height maps ({B * H * W * 4 / 1e9:.3f} GB) at the {COPY_TBS} TB/s float4-copy rate takes "
+            f"{read_ms:.3f} ms; the column is that time over the measured median (1 = the call costs one read of the height maps).\n\n")
+    emit(lines, a.out, head, notes)
 
 
 if __name__ == "__main__":

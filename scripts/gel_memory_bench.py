@@ -11,44 +11,17 @@ The map is rewritten in place, so a timed call works on the previous call's outp
 penetration) and a dead frame stays dead - the traffic per call does not change.
 
   --out FILE   also write the table as markdown."""
-import argparse
-import sys
-from pathlib import Path
+import torch
+from _bench_util import COPY_TBS, copy_ms, emit, parse_args, repeated, rounds, stats, table
 
-ap = argparse.ArgumentParser()
-ap.add_argument("--repo", default=str(Path(__file__).resolve().parent.parent))
-ap.add_argument("--frames", type=int, default=2048)
-ap.add_argument("--height", type=int, default=240)
-ap.add_argument("--width", type=int, default=320)
-ap.add_argument("--calls", type=int, default=50)
-ap.add_argument("--reps", type=int, default=5)
-ap.add_argument("--torch-calls", type=int, default=5)
-ap.add_argument("--sensor-steps", type=int, default=20)
-ap.add_argument("--no-sensor", action="store_true")
-ap.add_argument("--out", default=None)
-a = ap.parse_args()
-sys.path.insert(0, a.repo)
-
-import numpy as np  # noqa: E402
-import torch  # noqa: E402
+a = parse_args(calls=50, torch_calls=5, extra=[("--sensor-steps", dict(type=int, default=20)), ("--no-sensor", dict(action="store_true"))])
 
 from tacex_amd import GelMemoryProfile, TactileGelMemory, _lib  # noqa: E402
 from tacex_amd.gel_memory import rest_plane_mm  # noqa: E402
 from tacex_amd.utils.synthetic import synthetic_depth_maps  # noqa: E402
 
-COPY_TBS = 6.29  # measured float4-copy rate of one MI355X (profiles/contact_field_bench.md)
 GH, GD, DT = 0.0045, 0.024, 1.0 / 60.0
 GELS = [GelMemoryProfile((0.05, 0.4), (0.5, 0.3)), GelMemoryProfile((0.12, 0.8), (0.6, 0.2))]
-
-
-def timed(fn, calls):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(calls):
-        fn()
-    e1.record()
-    e1.synchronize()
-    return e0.elapsed_time(e1) / calls  # ms per call
 
 
 def torch_model(hm, state, a1, c1, floor, z0):
@@ -107,25 +80,19 @@ def main():
     variants["copy of the height maps (copy_, read + write)"] = lambda: dst.copy_(rd)
     bytes_px.update({k: 4 for k in variants if k.startswith("one read")})
     bytes_px["copy of the height maps (copy_, read + write)"] = 8
-    for fn in variants.values():
-        timed(fn, 5)
-    ms = {k: [] for k in variants}
-    for _ in range(a.reps):
-        for k, fn in variants.items():
-            ms[k].append(timed(fn, a.calls))
-    out = [(k, float(np.median(v)), float(min(v)), float(max(v)), bytes_px[k]) for k, v in ms.items()]
+    out = [(k, v, bytes_px[k]) for k, v in rounds(variants, a.calls, a.reps, 5).items()]
     live = {k: int(m.live.sum().item()) for k, m in models.items()}
     # (d) torch ops, K = 1, every frame live
     hm_t, state_t = contact.clone(), torch.zeros((B, H, W), device=dev)
     row = GELS[0].row(DT)
     fn = lambda: torch_model(hm_t, state_t, float(row[0]), float(row[1]), float(row[4]), z0)  # noqa: E731
-    timed(fn, 2)
-    v = [timed(fn, a.torch_calls) for _ in range(a.reps)]
-    out.append(("(d) the model in torch ops, every frame live, K = 1", float(np.median(v)), float(min(v)), float(max(v)), 4 + 4 + 8 + 4))
-    lines = ["| case | median ms | min | max | algorithmic B/px | TB/s over them | share of the float4-copy rate |", "|---|---|---|---|---|---|---|"]
-    for k, m, lo, hi, px in out:
-        rate = B * H * W * px / (m * 1e-3) / 1e12
-        lines.append(f"| {k} | {m:.3f} | {lo:.3f} | {hi:.3f} | {px:g} | {rate:.2f} | {rate / COPY_TBS:.2f} |")
+    out.append(("(d) the model in torch ops, every frame live, K = 1", repeated(fn, a.torch_calls, a.reps, 2), 4 + 4 + 8 + 4))
+
+    def rate(v, px):  # TB/s of the algorithmic bytes over the median
+        return B * H * W * px / (stats(v)[0] * 1e-3) / 1e12
+
+    lines = table(["algorithmic B/px", "TB/s over them", "share of the float4-copy rate"],
+                  [(k, v, f"{px:g}", f"{rate(v, px):.2f}", f"{rate(v, px) / COPY_TBS:.2f}") for k, v, px in out])
     notes = [f"{int(pressed.sum().item())} of {B} frames of the contact batch hold a pressed pixel; live frames after the timed calls: "
              f"(a) {live['a']}, (b) {live['b']} and {live['bs']}, (c) K = 1 {live['c1']}, K = 2 {live['c2']}"]
     # (e) a whole sensor update
@@ -154,23 +121,14 @@ def main():
             sensor(f"(e) sensor update, {data} contact, no model, depth pass not deferred", 0, False, data)
             sensor(f"(e) sensor update, {data} contact, gel memory K = 1", 1, True, data)
             sensor(f"(e) sensor update, {data} contact, gel memory K = 2", 2, True, data)
-        for _, step in sens:
-            timed(step, 3)
-        sm = {tag: [] for tag, _ in sens}
-        for _ in range(a.reps):
-            for tag, step in sens:
-                sm[tag].append(timed(step, a.sensor_steps))
+        sm = rounds(dict(sens), a.sensor_steps, a.reps, 3)
         gelsight_sensor._DEFER_DEPTH = True
-        lines += ["", "| sensor update (one GelSightSensor, tactile_rgb + FOTS markers) | median ms | min | max |", "|---|---|---|---|"]
-        lines += [f"| {tag} | {np.median(v):.3f} | {min(v):.3f} | {max(v):.3f} |" for tag, v in sm.items()]
-    print("\n".join(lines + [""] + notes), flush=True)
-    if a.out:
-        head = (f"# Gel memory: one call on {B} frames of {W} x {H}\n\n{a.calls} calls per timing between two hipEvents, {a.reps} alternating rounds "
-                f"(median, min, max of the rounds), one MI355X; torch ops {a.torch_calls} calls, the sensor {a.sensor_steps} updates per timing.  "
-                f"The height maps are {B * H * W * 4 / 1e9:.3f} GB: one read at the {COPY_TBS} TB/s float4-copy rate takes "
-                f"{B * H * W * 4 / (COPY_TBS * 1e12) * 1e3:.3f} ms.  The rate columns are derived: algorithmic bytes over the median.\n\n")
-        Path(a.out).parent.mkdir(parents=True, exist_ok=True)
-        Path(a.out).write_text(head + "\n".join(lines) + "\n\n" + "\n".join(f"- {n}" for n in notes) + "\n")
+        lines += [""] + table([], list(sm.items()), first="sensor update (one GelSightSensor, tactile_rgb + FOTS markers)")
+    head = (f"# Gel memory: one call on {B} frames of {W} x {H}\n\n{a.calls} calls per timing between two hipEvents, {a.reps} alternating rounds "
+            f"(median, min, max of the rounds), one MI355X; torch ops {a.torch_calls} calls, the sensor {a.sensor_steps} updates per timing.  "
+            f"The height maps are {B * H * W * 4 / 1e9:.3f} GB: one read at the {COPY_TBS} TB/s float4-copy rate takes "
+            f"{copy_ms(B * H * W * 4):.3f} ms.  The rate columns are derived: algorithmic bytes over the median.\n\n")
+    emit(lines, a.out, head, notes)
 
 
 if __name__ == "__main__":

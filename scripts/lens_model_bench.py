@@ -8,45 +8,21 @@ variants alternating over `--reps` rounds after a warm-up.  Beside them, three y
   - one sensor `update()` that renders those 2048 frames (height map from analytic indenters, tactile_rgb), for scale.
 
   --out FILE   also write the table as markdown."""
-import argparse
-import sys
-from pathlib import Path
+import numpy as np
+import torch
+from _bench_util import COPY_TBS, copy_ms, emit, parse_args, repeated, rounds, sensor_update_yardstick, table
 
-ap = argparse.ArgumentParser()
-ap.add_argument("--repo", default=str(Path(__file__).resolve().parent.parent))
-ap.add_argument("--frames", type=int, default=2048)
-ap.add_argument("--height", type=int, default=240)
-ap.add_argument("--width", type=int, default=320)
-ap.add_argument("--calls", type=int, default=200)
-ap.add_argument("--reps", type=int, default=5)
-ap.add_argument("--torch-calls", type=int, default=10, help="calls per timing of the torch restatement (it is many times slower)")
-ap.add_argument("--no-update", action="store_true", help="skip the sensor update() yardstick")
-ap.add_argument("--out", default=None)
-a = ap.parse_args()
-sys.path.insert(0, a.repo)
-
-import numpy as np  # noqa: E402
-import torch  # noqa: E402
+a = parse_args(calls=200, torch_calls=10, torch_help="calls per timing of the torch restatement (it is many times slower)",
+               extra=[("--no-update", dict(action="store_true", help="skip the sensor update() yardstick"))])
 
 from tacex_amd import CameraProfile, LensProfile, TactileCameraModel, TactileLensModel  # noqa: E402
 
-COPY_TBS = 6.29  # measured float4-copy rate of one MI355X (HBM3E, 79 % of the 8.0 TB/s datasheet peak)
 MIX = [[0.92, 0.06, 0.02], [0.03, 0.90, 0.05], [-0.02, 0.08, 1.05]]
 ONE_TAP = [LensProfile(k1=-0.15, k2=0.03, rotation_deg=1.5, scale=1.02, shift_px=(2.5, -1.0), vignette=(-0.25, -0.05)),
            LensProfile(k1=-0.10, k2=0.01, p1=0.004, p2=-0.003, rotation_deg=-0.8, scale=0.99, centre_px=(4.5, -3.25), vignette=(-0.2, -0.1))]
 FOUR_TAPS = [LensProfile(k1=-0.15, k2=0.03, rotation_deg=1.5, scale=1.02, shift_px=(2.5, -1.0), vignette=(-0.25, -0.05), softness=(0.3, 1.2)),
              LensProfile(k1=-0.10, k2=0.01, p1=0.004, p2=-0.003, rotation_deg=-0.8, scale=0.99, centre_px=(4.5, -3.25), vignette=(-0.2, -0.1),
                          softness=(0.5, 0.8))]
-
-
-def timed(fn, calls):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(calls):
-        fn()
-    e1.record()
-    e1.synchronize()
-    return e0.elapsed_time(e1) / calls  # ms per call
 
 
 def torch_restatement(x_nchw, rows, H, W):
@@ -66,29 +42,6 @@ def torch_restatement(x_nchw, rows, H, W):
     grid = torch.stack([(2 * u + 1) / W - 1, (2 * v + 1) / H - 1], -1)  # align_corners=False
     g = (1 + (v1 + v2 * r2) * r2).clamp_(0, 1)
     return torch.nn.functional.grid_sample(x_nchw, grid, mode="bilinear", padding_mode="border", align_corners=False) * g.unsqueeze(1)
-
-
-def update_yardstick(B, H, W):
-    from tacex_amd import GelSightSensor, GelSightSensorCfg, IndenterHeightMapSource
-    from tacex_amd.simulation_approaches.gpu_taxim import TaximSimulatorCfg
-    from tacex_amd.utils.synthetic import PIXMM
-
-    calib = Path(a.repo) / "tacex_amd" / "assets" / "calib" / "gsmini_640x480"
-    cfg = GelSightSensorCfg(
-        num_envs=B, data_types=["tactile_rgb", "height_map"],
-        sensor_camera_cfg=GelSightSensorCfg.SensorCameraCfg(resolution=(W, H), clipping_range=(0.024, 0.029)),
-        optical_sim_cfg=TaximSimulatorCfg(calib_folder_path=str(calib), gelpad_height=0.0045, gelpad_to_camera_min_distance=0.024,
-                                          tactile_img_res=(W, H), device="cuda"),
-        device="cuda")
-    s = GelSightSensor(cfg)
-    src = IndenterHeightMapSource(B, "cuda", pixmm=PIXMM)
-    g = torch.Generator().manual_seed(0)
-    u = torch.rand((B, 4), generator=g)
-    src.set("sphere", cx=(0.3 + 0.4 * u[:, 0]) * W, cy=(0.3 + 0.4 * u[:, 1]) * H, r=(0.15 + 0.2 * u[:, 2]) * H, press_mm=0.2 + 1.3 * u[:, 3])
-    s.set_height_map_source(src)
-    fn = lambda: s.update(0.01, force_recompute=True)  # noqa: E731
-    timed(fn, 5)
-    return [timed(fn, 20) for _ in range(a.reps)]
 
 
 def main():
@@ -120,42 +73,28 @@ def main():
         "fused lens + camera -> float32 (one tap, fixed pattern)": (lambda: lens1(x, out=out_f32, camera=cam_f32), 24),
         "two launches, lens then camera -> float32": (lambda: two(cam_f32, out_f32), 48),
     }
-    for fn, _ in variants.values():
-        timed(fn, 10)
-    ms = {k: [] for k in variants}
-    for _ in range(a.reps):
-        for k, (fn, _) in variants.items():
-            ms[k].append(timed(fn, a.calls))
-    rows = []
-    for k, v in ms.items():
-        floor = variants[k][1] * px / (COPY_TBS * 1e12) * 1e3
-        med = float(np.median(v))
-        rows.append((k, med, float(min(v)), float(max(v)), floor, floor / med))
+
+    def row(k, v, bytes_px):  # (the bytes of a call over the copy rate, ms)
+        floor = copy_ms(bytes_px * px)
+        return (k, v, f"{floor:.3f}", f"{floor / float(np.median(v)):.2f}")
+
+    ms = rounds({k: fn for k, (fn, _) in variants.items()}, a.calls, a.reps, 10)
+    rows = [row(k, v, variants[k][1]) for k, v in ms.items()]
     # the torch restatement (allocates its temporaries, like the code a user would write); channels-last view of the NHWC batch
     x_nchw = x.permute(0, 3, 1, 2)
     lens_rows = lens1.profiles[lens1.profile_ids.long()]
     tfn = lambda: torch_restatement(x_nchw, lens_rows, H, W)  # noqa: E731
-    timed(tfn, 2)
-    v = [timed(tfn, a.torch_calls) for _ in range(a.reps)]
-    floor = 24 * px / (COPY_TBS * 1e12) * 1e3
-    rows.append(("torch restatement, one tap (explicit grid, grid_sample, vignette)", float(np.median(v)), float(min(v)), float(max(v)), floor,
-                 floor / float(np.median(v))))
+    rows.append(row("torch restatement, one tap (explicit grid, grid_sample, vignette)", repeated(tfn, a.torch_calls, a.reps, 2), 24))
     del mid, out_f32, out_u8
     torch.cuda.empty_cache()
     if not a.no_update:
-        v = update_yardstick(B, H, W)
-        rows.append((f"sensor update() rendering the {B} frames (for scale)", float(np.median(v)), float(min(v)), float(max(v)), float("nan"), float("nan")))
-    lines = ["| case | median ms | min | max | bytes / 6.29 TB/s, ms | fraction of the copy rate |", "|---|---|---|---|---|---|"]
-    lines += [f"| {k} | {m:.3f} | {lo:.3f} | {hi:.3f} | {fl:.3f} | {fr:.2f} |" for k, m, lo, hi, fl, fr in rows]
-    print("\n".join(lines), flush=True)
-    if a.out:
-        head = (f"# Sensor lens model: one call on {B} frames of {W} x {H}\n\n{a.calls} calls per timing between two hipEvents, {a.reps} alternating rounds "
-                f"(median, min, max of the rounds), one MI355X; the torch restatement {a.torch_calls} calls per timing, the sensor update 20.  "
-                f"The copy-rate column is derived: the bytes a call must move (12 B / pixel in; 12 out for float32, 3 for uint8; the two launches "
-                f"also write and read the 12 B / pixel between them) over the {COPY_TBS} TB/s float4-copy rate; the fraction is that time over "
-                f"the measured median.\n\n")
-        Path(a.out).parent.mkdir(parents=True, exist_ok=True)
-        Path(a.out).write_text(head + "\n".join(lines) + "\n")
+        rows.append(row(f"sensor update() rendering the {B} frames (for scale)", sensor_update_yardstick(a.repo, B, H, W, a.reps), float("nan")))
+    head = (f"# Sensor lens model: one call on {B} frames of {W} x {H}\n\n{a.calls} calls per timing between two hipEvents, {a.reps} alternating rounds "
+            f"(median, min, max of the rounds), one MI355X; the torch restatement {a.torch_calls} calls per timing, the sensor update 20.  "
+            f"The copy-rate column is derived: the bytes a call must move (12 B / pixel in; 12 out for float32, 3 for uint8; the two launches "
+            f"also write and read the 12 B / pixel between them) over the {COPY_TBS} TB/s float4-copy rate; the fraction is that time over "
+            f"the measured median.\n\n")
+    emit(table(["bytes / 6.29 TB/s, ms", "fraction of the copy rate"], rows), a.out, head)
 
 
 if __name__ == "__main__":

@@ -1,0 +1,94 @@
+"""What the per-env stages of the optical path share (camera_model, lens_model, contact_field, gel_memory): the profile table with
+its ids, the check of a tensor argument, and the constructor preamble.  A stage keeps its own profile class, its own arguments and
+its one launch; DESIGN.md 4.0.12a.4 says how a new stage uses these pieces."""
+from __future__ import annotations
+
+import numpy as np
+import torch
+
+from . import _lib
+
+
+def check_tensor(owner: str, name: str, t, shape, dtype, device, must: str = "must be", on_device=_lib.TacexHipError):
+    """`t` as a launch needs it, or an exception naming `owner` and `name`.  A str in `shape` is a free dimension >= 1.  Not a
+    tensor, another shape or dtype, not contiguous: ValueError; then a tensor on another device than `device`: `on_device`."""
+    ok = isinstance(t, torch.Tensor) and t.dim() == len(shape) and all(
+        n >= 1 if isinstance(want, str) else n == want for n, want in zip(t.shape, shape))
+    if not ok or t.dtype != dtype or not t.is_contiguous():
+        want = "(" + ", ".join(str(s) for s in shape) + ("," if len(shape) == 1 else "") + ")"
+        got = f"{tuple(t.shape)} {t.dtype}" if isinstance(t, torch.Tensor) else type(t).__name__
+        raise ValueError(f"{owner}: {name} {must} a contiguous {want} {dtype} tensor, got {got}")
+    if t.device != device:
+        raise on_device(f"{owner}: {name} is on {t.device}, the model on {device} (no CPU fallback)")
+    return t
+
+
+class ProfileTable:
+    """`rows` (P, C) float32 and `ids` (num_frames,) int32 on one device: the library of a stage and which row each env uses.  Both
+    are plain tensors the caller may write in place; `check()` before a launch refuses what the kernels cannot take."""
+
+    def __init__(self, owner: str, rows_name: str, ids_name: str, rows, num_frames: int, device):
+        self.owner, self.rows_name, self.ids_name = owner, rows_name, ids_name
+        self.num_frames = int(num_frames)
+        self.ids = torch.zeros(self.num_frames, dtype=torch.int32, device=device)
+        self.device = self.ids.device  # (with its index: what a tensor's .device compares equal to)
+        self.rows = None
+        self.assign(rows)
+        self.width = int(self.rows.shape[1])
+
+    def assign(self, rows):
+        """New rows: copied into the storage there is when the shape stays (a captured graph keeps pointing at it)."""
+        rows = torch.as_tensor(rows, dtype=torch.float32)
+        if self.rows is not None and self.rows.shape == rows.shape:
+            self.rows.copy_(rows)
+        else:
+            self.rows = rows.to(self.device, copy=True)  # (its own storage on a CPU device too)
+
+    def randomize(self, env_ids=None, generator=None) -> torch.Tensor:
+        """Re-draw the ids of `env_ids` (default: all) uniformly from [0, P) on the device; returns the id tensor."""
+        n = self.num_frames if env_ids is None else len(env_ids)
+        ids = torch.randint(0, int(self.rows.shape[0]), (n,), dtype=torch.int32, device=self.device, generator=generator)
+        if env_ids is None:
+            self.ids.copy_(ids)
+        else:
+            self.ids[torch.as_tensor(env_ids, dtype=torch.long, device=self.device)] = ids
+        return self.ids
+
+    def check(self):
+        """(ids, rows) for a launch."""
+        check_tensor(self.owner, self.ids_name, self.ids, (self.num_frames,), torch.int32, self.device, must="must stay")
+        check_tensor(self.owner, self.rows_name, self.rows, ("P", self.width), torch.float32, self.device, must="must stay")
+        return self.ids, self.rows
+
+
+class table_attr:
+    """A model's public name for `rows` or `ids` of its `_table` (read and assigned like the plain attribute it was)."""
+
+    def __init__(self, field: str):
+        self.field = field
+
+    def __get__(self, obj, objtype=None):
+        return self if obj is None else getattr(obj._table, self.field)
+
+    def __set__(self, obj, value):
+        setattr(obj._table, self.field, value)
+
+
+def profile_list(owner: str, name: str, profiles, cls) -> list:
+    """One `cls` or a sequence of them -> a non-empty list."""
+    profiles = [profiles] if isinstance(profiles, cls) else list(profiles)
+    if not profiles or not all(isinstance(p, cls) for p in profiles):
+        raise ValueError(f"{owner}: {name} must be a non-empty sequence of {cls.__name__}")
+    return profiles
+
+
+def open_stage(owner: str, rows_name: str, ids_name: str, profiles, cls, num_frames: int, device, row=lambda p: p.row()):
+    """The end of a stage's constructor, after its own arguments: profiles -> rows, num_frames, the device (a stage runs on the
+    GPU only), the library.  Returns (library, ProfileTable); every ValueError comes before the device is looked at."""
+    rows = np.stack([row(p) for p in profile_list(owner, rows_name, profiles, cls)])
+    if int(num_frames) <= 0:
+        raise ValueError(f"{owner}: num_frames = {num_frames}")
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise _lib.TacexHipError(f"{owner} runs on the GPU only (device {device}): there is no CPU fallback")
+    return _lib.load_library(), ProfileTable(owner, rows_name, ids_name, rows, num_frames, device)

@@ -15,7 +15,7 @@ from dataclasses import dataclass, field
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, _stage
 
 _OUT_DTYPES = {torch.float32: 0, torch.uint8: 1}
 
@@ -58,31 +58,22 @@ class TactileCameraModel:
     launches: it is the time coordinate of the noise draws and is incremented by every `__call__` that does not pass its own.
     `frame_offset`: the global index of this model's first env (an env shard renders the frames the whole batch would)."""
 
+    profiles, profile_ids = _stage.table_attr("rows"), _stage.table_attr("ids")
+
     def __init__(self, profiles, num_frames: int, device, seed: int = 0, dtype: torch.dtype = torch.uint8, frame_offset: int = 0):
-        if isinstance(profiles, CameraProfile):
-            profiles = [profiles]
-        rows = [p.row() if isinstance(p, CameraProfile) else None for p in profiles]
-        if not rows or any(r is None for r in rows):
-            raise ValueError("TactileCameraModel: profiles must be a non-empty sequence of CameraProfile")
         if dtype not in _OUT_DTYPES:
             raise ValueError(f"TactileCameraModel: dtype must be torch.uint8 or torch.float32, got {dtype}")
-        if int(num_frames) <= 0:
-            raise ValueError(f"TactileCameraModel: num_frames = {num_frames}")
         if not 0 <= int(seed) < 2 ** 64:
             raise ValueError("TactileCameraModel: seed must fit 64 bits")
         if not 0 <= int(frame_offset) <= 2 ** 32 - int(num_frames):
             raise ValueError("TactileCameraModel: frame_offset + num_frames must fit 32 bits")
+        self._lib, self._table = _stage.open_stage("TactileCameraModel", "profiles", "profile_ids", profiles, CameraProfile, num_frames, device)
         self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise _lib.TacexHipError(f"TactileCameraModel runs on the GPU only (device {self.device}): there is no CPU fallback")
-        self._lib = _lib.load_library()
         self.num_frames = int(num_frames)
         self.seed = int(seed)
         self.dtype = dtype
         self.frame_offset = int(frame_offset)
         self.call = 0
-        self.profiles = torch.from_numpy(np.stack(rows)).to(self.device)
-        self.profile_ids = torch.zeros(self.num_frames, dtype=torch.int32, device=self.device)
 
     @property
     def num_profiles(self) -> int:
@@ -90,42 +81,32 @@ class TactileCameraModel:
 
     def randomize(self, env_ids=None, generator=None):
         """Re-draw the profile ids of `env_ids` (default: all) uniformly from [0, P) on the device."""
-        n = self.num_frames if env_ids is None else len(env_ids)
-        ids = torch.randint(0, self.num_profiles, (n,), dtype=torch.int32, device=self.device, generator=generator)
-        if env_ids is None:
-            self.profile_ids.copy_(ids)
-        else:
-            self.profile_ids[torch.as_tensor(env_ids, dtype=torch.long, device=self.device)] = ids
-        return self.profile_ids
+        return self._table.randomize(env_ids, generator)
 
-    def __call__(self, rgb: torch.Tensor, out: torch.Tensor | None = None, call: int | None = None) -> torch.Tensor:
-        """One launch on the current stream.  `rgb` (num_frames,H,W,3) float32, contiguous, on the model's device; `out` of the same
-        shape and the model's dtype (float32 may be `rgb` itself), allocated when None.  `call` overrides the running counter."""
-        if not isinstance(rgb, torch.Tensor) or rgb.dim() != 4 or rgb.shape[0] != self.num_frames or rgb.shape[3] != 3:
-            raise ValueError(f"TactileCameraModel: rgb must be a ({self.num_frames}, H, W, 3) tensor, got "
-                             f"{tuple(rgb.shape) if isinstance(rgb, torch.Tensor) else type(rgb).__name__}")
-        if rgb.dtype != torch.float32 or not rgb.is_contiguous() or rgb.shape[1] < 1 or rgb.shape[2] < 1:
-            raise ValueError("TactileCameraModel: rgb must be float32, contiguous and non-empty")
-        if rgb.device != self.profiles.device:
-            raise _lib.TacexHipError(f"TactileCameraModel: rgb is on {rgb.device}, the model on {self.profiles.device} (no CPU fallback)")
-        if out is None:
-            out = torch.empty(rgb.shape, dtype=self.dtype, device=rgb.device)
-        elif (not isinstance(out, torch.Tensor) or out.shape != rgb.shape or out.dtype != self.dtype or not out.is_contiguous()
-              or out.device != rgb.device):
-            raise ValueError(f"TactileCameraModel: out must be a contiguous {tuple(rgb.shape)} {self.dtype} tensor on {rgb.device}")
-        ids, prof = self.profile_ids, self.profiles
-        if ids.dtype != torch.int32 or tuple(ids.shape) != (self.num_frames,) or not ids.is_contiguous() or ids.device != rgb.device:
-            raise ValueError(f"TactileCameraModel: profile_ids must stay a ({self.num_frames},) int32 tensor on {rgb.device}")
-        if prof.dtype != torch.float32 or prof.dim() != 2 or prof.shape[1] != 16 or not prof.is_contiguous() or prof.device != rgb.device:
-            raise ValueError(f"TactileCameraModel: profiles must stay a (P, 16) float32 tensor on {rgb.device}")
+    def _tables_and_call(self, call):
+        """(ids, profiles, call) of one launch, this model's or a fused one: the tables as the kernels expect them, `call` or the
+        running counter, which is then advanced."""
+        ids, prof = self._table.check()
         if call is None:
             call = self.call
             self.call = (self.call + 1) & 0xFFFFFFFF
         elif not 0 <= int(call) < 2 ** 32:
             raise ValueError("TactileCameraModel: call must fit 32 bits")
-        with torch.cuda.device(rgb.device):
+        return ids, prof, int(call)
+
+    def __call__(self, rgb: torch.Tensor, out: torch.Tensor | None = None, call: int | None = None) -> torch.Tensor:
+        """One launch on the current stream.  `rgb` (num_frames,H,W,3) float32, contiguous, on the model's device; `out` of the same
+        shape and the model's dtype (float32 may be `rgb` itself), allocated when None.  `call` overrides the running counter."""
+        dev = self._table.device
+        _stage.check_tensor("TactileCameraModel", "rgb", rgb, (self.num_frames, "H", "W", 3), torch.float32, dev)
+        if out is None:
+            out = torch.empty(rgb.shape, dtype=self.dtype, device=dev)
+        else:
+            _stage.check_tensor("TactileCameraModel", "out", out, tuple(rgb.shape), self.dtype, dev)
+        ids, prof, call = self._tables_and_call(call)
+        with torch.cuda.device(dev):
             rc = self._lib.tacex_camera_model(_lib.ptr(rgb), _lib.ptr(prof), int(prof.shape[0]), _lib.ptr(ids), self.seed, self.frame_offset,
-                                              int(call), _lib.ptr(out), _OUT_DTYPES[self.dtype], self.num_frames, int(rgb.shape[1]),
-                                              int(rgb.shape[2]), _lib.current_stream_handle(rgb.device))
+                                              call, _lib.ptr(out), _OUT_DTYPES[self.dtype], self.num_frames, int(rgb.shape[1]),
+                                              int(rgb.shape[2]), _lib.current_stream_handle(dev))
         _lib.check(rc, "tacex_camera_model")
         return out

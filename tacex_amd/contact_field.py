@@ -18,7 +18,7 @@ from dataclasses import dataclass
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, _stage
 
 
 @dataclass
@@ -146,27 +146,18 @@ class TactileContactModel:
     may write in place (ids at reset, like `TactileCameraModel.profile_ids`; an env whose id is outside [0, P) reports zeros).
     `pixmm`: pixel pitch of the height map [mm]; `grid` = (rows, cols) of the tactile cells laid over the image."""
 
+    gels, gel_ids = _stage.table_attr("rows"), _stage.table_attr("ids")
+
     def __init__(self, gels, num_frames: int, device, pixmm: float = 0.0295, grid=(9, 11)):
-        if isinstance(gels, ContactGel):
-            gels = [gels]
-        rows = [g.row() if isinstance(g, ContactGel) else None for g in gels]
-        if not rows or any(r is None for r in rows):
-            raise ValueError("TactileContactModel: gels must be a non-empty sequence of ContactGel")
-        if int(num_frames) <= 0:
-            raise ValueError(f"TactileContactModel: num_frames = {num_frames}")
         if not (math.isfinite(float(pixmm)) and float(pixmm) > 0):
             raise ValueError(f"TactileContactModel: pixmm = {pixmm}")
         if len(grid) != 2 or int(grid[0]) < 1 or int(grid[1]) < 1:
             raise ValueError(f"TactileContactModel: grid = {grid} must be (rows >= 1, cols >= 1)")
+        self._lib, self._table = _stage.open_stage("TactileContactModel", "gels", "gel_ids", gels, ContactGel, num_frames, device)
         self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise _lib.TacexHipError(f"TactileContactModel runs on the GPU only (device {self.device}): there is no CPU fallback")
-        self._lib = _lib.load_library()
         self.num_frames = int(num_frames)
         self.pixmm = float(pixmm)
         self.grid = (int(grid[0]), int(grid[1]))
-        self.gels = torch.from_numpy(np.stack(rows)).to(self.device)
-        self.gel_ids = torch.zeros(self.num_frames, dtype=torch.int32, device=self.device)
 
     @property
     def num_gels(self) -> int:
@@ -174,20 +165,7 @@ class TactileContactModel:
 
     def randomize(self, env_ids=None, generator=None):
         """Re-draw the gel ids of `env_ids` (default: all) uniformly from [0, P) on the device."""
-        n = self.num_frames if env_ids is None else len(env_ids)
-        ids = torch.randint(0, self.num_gels, (n,), dtype=torch.int32, device=self.device, generator=generator)
-        if env_ids is None:
-            self.gel_ids.copy_(ids)
-        else:
-            self.gel_ids[torch.as_tensor(env_ids, dtype=torch.long, device=self.device)] = ids
-        return self.gel_ids
-
-    def _vector(self, t, name, shape, dtype):
-        if not isinstance(t, torch.Tensor) or tuple(t.shape) != shape or t.dtype != dtype or not t.is_contiguous():
-            raise ValueError(f"TactileContactModel: {name} must be a contiguous {shape} {dtype} tensor")
-        if t.device != self.gels.device:
-            raise _lib.TacexHipError(f"TactileContactModel: {name} is on {t.device}, the model on {self.gels.device} (no CPU fallback)")
-        return t
+        return self._table.randomize(env_ids, generator)
 
     def __call__(self, hm: torch.Tensor, frame_min: torch.Tensor, indent: torch.Tensor, slip: torch.Tensor | None = None,
                  frame_rows: torch.Tensor | None = None, image: bool | torch.Tensor = False) -> ContactField:
@@ -195,37 +173,34 @@ class TactileContactModel:
         `indent` (num_frames,) float32 as the sensor's depth pass leaves them; `slip` (num_frames,5) float32 or None (no shear);
         `frame_rows` (num_frames,4) int32 contact rectangles of THESE height maps or None; `image`: True allocates the traction
         image, a (num_frames,H,W,3) float32 tensor is written in place, False writes none."""
-        B = self.num_frames
-        if not isinstance(hm, torch.Tensor) or hm.dim() != 3 or hm.shape[0] != B or hm.shape[1] < 1 or hm.shape[2] < 1:
-            raise ValueError(f"TactileContactModel: hm must be a ({B}, H, W) tensor, got "
-                             f"{tuple(hm.shape) if isinstance(hm, torch.Tensor) else type(hm).__name__}")
+        B, dev = self.num_frames, self._table.device
+
+        def arg(name, t, shape, dtype=torch.float32):
+            return _stage.check_tensor("TactileContactModel", name, t, shape, dtype, dev)
+
+        arg("hm", hm, (B, "H", "W"))
         H, W = int(hm.shape[1]), int(hm.shape[2])
-        self._vector(hm, "hm", (B, H, W), torch.float32)
-        self._vector(frame_min, "frame_min", (B,), torch.float32)
-        self._vector(indent, "indent", (B,), torch.float32)
+        arg("frame_min", frame_min, (B,))
+        arg("indent", indent, (B,))
         if slip is not None:
-            self._vector(slip, "slip", (B, 5), torch.float32)
+            arg("slip", slip, (B, 5))
         if frame_rows is not None:
-            self._vector(frame_rows, "frame_rows", (B, 4), torch.int32)
-        self._vector(self.gel_ids, "gel_ids", (B,), torch.int32)
-        gels = self.gels
-        if not isinstance(gels, torch.Tensor) or gels.dim() != 2 or gels.shape[0] < 1:
-            raise ValueError("TactileContactModel: gels must stay a (P, 4) float32 tensor")
-        self._vector(gels, "gels", (int(gels.shape[0]), 4), torch.float32)
+            arg("frame_rows", frame_rows, (B, 4), torch.int32)
+        gel_ids, gels = self._table.check()
         rows, cols = self.grid
         if rows > H or cols > W:
             raise ValueError(f"TactileContactModel: grid {self.grid} is larger than the {H} x {W} image")
         img = None
         if isinstance(image, torch.Tensor):
-            img = self._vector(image, "image", (B, H, W, 3), torch.float32)
+            img = arg("image", image, (B, H, W, 3))
         elif image:
-            img = torch.empty((B, H, W, 3), dtype=torch.float32, device=hm.device)
-        record = torch.empty((B, 16), dtype=torch.float64, device=hm.device)
-        cells = torch.empty((B, rows, cols, 3), dtype=torch.float32, device=hm.device)
-        with torch.cuda.device(hm.device):
+            img = torch.empty((B, H, W, 3), dtype=torch.float32, device=dev)
+        record = torch.empty((B, 16), dtype=torch.float64, device=dev)
+        cells = torch.empty((B, rows, cols, 3), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
             rc = self._lib.tacex_contact_field(_lib.ptr(hm), _lib.ptr(frame_min), _lib.ptr(indent), _lib.ptr(gels), int(gels.shape[0]),
-                                               _lib.ptr(self.gel_ids), _lib.ptr(slip), self.pixmm, _lib.ptr(frame_rows), rows, cols,
+                                               _lib.ptr(gel_ids), _lib.ptr(slip), self.pixmm, _lib.ptr(frame_rows), rows, cols,
                                                _lib.ptr(record), _lib.ptr(cells), _lib.ptr(img), B, H, W,
-                                               _lib.current_stream_handle(hm.device))
+                                               _lib.current_stream_handle(dev))
         _lib.check(rc, "tacex_contact_field")
         return ContactField(record, cells, img)

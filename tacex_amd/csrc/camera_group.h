@@ -51,7 +51,7 @@ struct CameraProfileRow {
 // the row of `frame` (wave-uniform: a workgroup stays inside one frame)
 __device__ inline CameraProfileRow load_camera_profile(const CameraTable& t, unsigned int frame) {
   CameraProfileRow p;
-  const int id = t.ids ? t.ids[frame] : 0;
+  const int id = t.ids ? t.ids[frame] : 0;  // (written out, not stage_row(): profiles/stage_layer_isa.md)
   if (id >= 0 && id < t.num_profiles) {
     const float* __restrict__ row = t.profiles + (size_t)id * 16;
 #pragma unroll

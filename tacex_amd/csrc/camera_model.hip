@@ -21,6 +21,7 @@
 #include <stdint.h>
 
 #include "camera_group.h"
+#include "stage_args.h"
 #include "tacex_hip.h"
 #include "tacex_internal.h"
 
@@ -85,13 +86,10 @@ extern "C" int tacex_camera_model(const float* rgb_dev, const float* profiles_de
                                   uint64_t seed, uint32_t frame_offset, uint32_t call, void* out_dev, int out_dtype, int num_frames,
                                   int height, int width, void* stream) {
   using namespace tacex;
-  if (!rgb_dev) { set_error("tacex_camera_model: null rgb_dev"); return 2; }
-  if (!profiles_dev) { set_error("tacex_camera_model: null profiles_dev"); return 2; }
-  if (!out_dev) { set_error("tacex_camera_model: null out_dev"); return 2; }
-  if (num_profiles <= 0) { set_error("tacex_camera_model: num_profiles = %d", num_profiles); return 2; }
-  if (num_frames <= 0) { set_error("tacex_camera_model: num_frames = %d", num_frames); return 2; }
-  if (height <= 0) { set_error("tacex_camera_model: height = %d", height); return 2; }
-  if (width <= 0) { set_error("tacex_camera_model: width = %d", width); return 2; }
+  const char* fn = "tacex_camera_model";
+  if (null_arg(fn, "rgb_dev", rgb_dev) || null_arg(fn, "profiles_dev", profiles_dev) || null_arg(fn, "out_dev", out_dev) ||
+      not_positive(fn, "num_profiles", num_profiles) || not_positive(fn, "num_frames", num_frames) ||
+      not_positive(fn, "height", height) || not_positive(fn, "width", width)) return 2;
   if (out_dtype != 0 && out_dtype != 1) { set_error("tacex_camera_model: out_dtype = %d (0: float32, 1: uint8)", out_dtype); return 2; }
   if (out_dtype == 1 && out_dev == (const void*)rgb_dev) {
     set_error("tacex_camera_model: out_dev == rgb_dev needs out_dtype 0 (a uint8 frame cannot overwrite its float32 input)");
@@ -101,17 +99,14 @@ extern "C" int tacex_camera_model(const float* rgb_dev, const float* profiles_de
   const long long npix = (long long)height * width;
   const long long groups = (npix + 3) / 4;
   const bool vec = ((uintptr_t)rgb_dev % 16 == 0) && ((uintptr_t)out_dev % 16 == 0) && (npix % 4 == 0);
-  const long long bpf = (groups + kCameraBlock - 1) / kCameraBlock;  // one group per thread on both paths
-  if (groups > 0x7fffffffll || bpf * num_frames > 0x7fffffffll) {
-    set_error("tacex_camera_model: num_frames x height x width = %d x %d x %d exceeds one launch", num_frames, height, width);
-    return 2;
-  }
+  FrameLaunch fl;  // one group per thread on both paths
+  if (!frame_launch(groups, groups, kCameraBlock, num_frames, &fl)) return refuse_image_launch(fn, num_frames, height, width);
   CameraArgs a{};
   a.rgb = rgb_dev; a.out = out_dev;
   a.cam.profiles = profiles_dev; a.cam.ids = profile_ids_dev; a.cam.num_profiles = num_profiles;
   a.cam.key0 = (uint32_t)(seed & 0xffffffffull); a.cam.key1 = (uint32_t)(seed >> 32); a.cam.frame_offset = frame_offset; a.cam.call = call;
-  a.npix = npix; a.groups = (unsigned int)groups; a.blocks_per_frame = (unsigned int)bpf;
-  const dim3 grid((unsigned int)(bpf * num_frames)), block(kCameraBlock);
+  a.npix = npix; a.groups = (unsigned int)groups; a.blocks_per_frame = fl.blocks_per_frame;
+  const dim3 grid(fl.grid), block(kCameraBlock);
   hipStream_t st = (hipStream_t)stream;
   if (vec && u8) hipLaunchKernelGGL(camera_model_vec_kernel<true>, grid, block, 0, st, a);
   else if (vec) hipLaunchKernelGGL(camera_model_vec_kernel<false>, grid, block, 0, st, a);

@@ -24,6 +24,7 @@
 #include <math.h>
 #include <stdint.h>
 
+#include "stage_args.h"
 #include "tacex_hip.h"
 #include "tacex_internal.h"
 
@@ -104,10 +105,10 @@ __global__ __launch_bounds__(kCfBlock) void contact_field_kernel(ContactArgs a) 
   // ---- the frame's scalars (uniform over the workgroup) ----
   ContactFrame f;
   f.fmin = a.fmin[frame]; f.indent = a.indent[frame];
-  const int id = a.gel_ids ? a.gel_ids[frame] : 0;
-  const bool valid = id >= 0 && id < a.num_gels;
+  const float* g = stage_row(a.gels, a.gel_ids, a.num_gels, 4, frame);
+  const bool valid = g != nullptr;
   f.kn = f.kt = f.mu = 0.0f;
-  if (valid) { const float* g = a.gels + (size_t)id * 4; f.kn = g[0]; f.kt = g[1]; f.mu = g[2]; }
+  if (valid) { f.kn = g[0]; f.kt = g[1]; f.mu = g[2]; }
   f.dx = f.dy = f.dth = f.cx = f.cy = 0.0f;
   if (a.slip) { const float* s = a.slip + (size_t)frame * 5; f.dx = s[0]; f.dy = s[1]; f.dth = s[2]; f.cx = s[3]; f.cy = s[4]; }
   int r0 = 0, r1 = H - 1, c0 = 0, c1 = W - 1;
@@ -341,15 +342,10 @@ extern "C" int tacex_contact_field(const float* hm_mm_dev, const float* frame_mi
                                    const int32_t* frame_rows_dev, int grid_rows, int grid_cols, double* record_dev, float* cells_dev,
                                    float* image_dev, int num_frames, int height, int width, void* stream) {
   using namespace tacex;
-  if (!hm_mm_dev) { set_error("tacex_contact_field: null hm_mm_dev"); return 2; }
-  if (!frame_min_dev) { set_error("tacex_contact_field: null frame_min_dev"); return 2; }
-  if (!indent_mm_dev) { set_error("tacex_contact_field: null indent_mm_dev"); return 2; }
-  if (!gels_dev) { set_error("tacex_contact_field: null gels_dev"); return 2; }
-  if (!record_dev) { set_error("tacex_contact_field: null record_dev"); return 2; }
-  if (num_gels <= 0) { set_error("tacex_contact_field: num_gels = %d", num_gels); return 2; }
-  if (num_frames <= 0) { set_error("tacex_contact_field: num_frames = %d", num_frames); return 2; }
-  if (height <= 0) { set_error("tacex_contact_field: height = %d", height); return 2; }
-  if (width <= 0) { set_error("tacex_contact_field: width = %d", width); return 2; }
+  const char* fn = "tacex_contact_field";
+  if (null_arg(fn, "hm_mm_dev", hm_mm_dev) || null_arg(fn, "frame_min_dev", frame_min_dev) || null_arg(fn, "indent_mm_dev", indent_mm_dev) ||
+      null_arg(fn, "gels_dev", gels_dev) || null_arg(fn, "record_dev", record_dev) || not_positive(fn, "num_gels", num_gels) ||
+      not_positive(fn, "num_frames", num_frames) || not_positive(fn, "height", height) || not_positive(fn, "width", width)) return 2;
   if (!(pixmm > 0.0f)) { set_error("tacex_contact_field: pixmm = %g (must be > 0)", (double)pixmm); return 2; }
   if (grid_rows < 1 || grid_rows > height) { set_error("tacex_contact_field: grid_rows = %d outside [1, height = %d]", grid_rows, height); return 2; }
   if (grid_cols < 1 || grid_cols > width) { set_error("tacex_contact_field: grid_cols = %d outside [1, width = %d]", grid_cols, width); return 2; }

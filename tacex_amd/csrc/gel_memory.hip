@@ -14,6 +14,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "stage_args.h"
 #include "tacex_internal.h"
 #include "taxim_device.h"
 #include "frame_rows.h"
@@ -37,10 +38,8 @@ struct GelArgs {
 struct GelCoef { float a1, c1, a2, c2, floor_mm; };
 
 __device__ __forceinline__ GelCoef gel_coef(const GelArgs& a, int b) {
-  const int id = a.ids ? a.ids[b] : 0;
   GelCoef c{0.0f, 0.0f, 0.0f, 0.0f, 0.0f};  // an id outside [0, P): the all-zero profile
-  if (id >= 0 && id < a.P) {
-    const float* p = a.coef + (size_t)id * 8;
+  if (const float* p = stage_row(a.coef, a.ids, a.P, 8, b)) {
     c.a1 = p[0]; c.c1 = p[1]; c.a2 = p[2]; c.c2 = p[3]; c.floor_mm = p[4];
   }
   return c;
@@ -272,17 +271,12 @@ extern "C" int tacex_gel_memory(float* hm_mm_dev, float* state_dev, int32_t* liv
                                 float gelpad_to_camera_min_distance_m, float* frame_min_dev, float* indent_mm_dev,
                                 int32_t* frame_rows_dev, int num_frames, int height, int width, int terms, void* stream) {
   using namespace tacex;
-  if (!hm_mm_dev) { set_error("tacex_gel_memory: null hm_mm_dev"); return 2; }
-  if (!state_dev) { set_error("tacex_gel_memory: null state_dev"); return 2; }
-  if (!live_dev) { set_error("tacex_gel_memory: null live_dev"); return 2; }
-  if (!coef_dev) { set_error("tacex_gel_memory: null coef_dev"); return 2; }
-  if (!frame_min_dev) { set_error("tacex_gel_memory: null frame_min_dev"); return 2; }
-  if (!indent_mm_dev) { set_error("tacex_gel_memory: null indent_mm_dev"); return 2; }
+  const char* fn = "tacex_gel_memory";
+  if (null_arg(fn, "hm_mm_dev", hm_mm_dev) || null_arg(fn, "state_dev", state_dev) || null_arg(fn, "live_dev", live_dev) ||
+      null_arg(fn, "coef_dev", coef_dev) || null_arg(fn, "frame_min_dev", frame_min_dev) || null_arg(fn, "indent_mm_dev", indent_mm_dev)) return 2;
   if (terms != 1 && terms != 2) { set_error("tacex_gel_memory: terms = %d (must be 1 or 2)", terms); return 2; }
-  if (num_profiles <= 0) { set_error("tacex_gel_memory: num_profiles = %d", num_profiles); return 2; }
-  if (num_frames <= 0) { set_error("tacex_gel_memory: num_frames = %d", num_frames); return 2; }
-  if (height <= 0) { set_error("tacex_gel_memory: height = %d", height); return 2; }
-  if (width <= 0) { set_error("tacex_gel_memory: width = %d", width); return 2; }
+  if (not_positive(fn, "num_profiles", num_profiles) || not_positive(fn, "num_frames", num_frames) || not_positive(fn, "height", height) ||
+      not_positive(fn, "width", width)) return 2;
   const bool vec = width % 4 == 0;
   if (vec && ((uintptr_t)hm_mm_dev % 16 != 0 || (uintptr_t)state_dev % 16 != 0)) {
     set_error("tacex_gel_memory: hm_mm_dev and state_dev must be 16-byte aligned when width %% 4 == 0");

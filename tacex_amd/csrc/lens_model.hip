@@ -24,6 +24,7 @@
 #include <stdint.h>
 
 #include "camera_group.h"
+#include "stage_args.h"
 #include "tacex_hip.h"
 #include "tacex_internal.h"
 
@@ -52,7 +53,7 @@ struct LensArgs {
 
 __device__ inline LensRow load_lens_row(const float* profiles, const int32_t* ids, int num_profiles, unsigned int frame) {
   LensRow L{};  // an id outside [0, P): the identity profile, all zero
-  const int id = ids ? ids[frame] : 0;
+  const int id = ids ? ids[frame] : 0;  // (written out, not stage_row(): profiles/stage_layer_isa.md)
   if (id >= 0 && id < num_profiles) {
     const float* __restrict__ r = profiles + (size_t)id * 16;
     L.k1 = r[0]; L.k2 = r[1]; L.p1 = r[2]; L.p2 = r[3]; L.e00 = r[4]; L.e01 = r[5]; L.e10 = r[6]; L.e11 = r[7];
@@ -223,26 +224,25 @@ __global__ __launch_bounds__(kLensBlock) void lens_points_kernel(PointArgs a) {
   a.out[o] = qx; a.out[o + 1] = qy;
 }
 
+// the checks the three entry points share (`src` is rgb_dev or xy_dev)
+bool lens_refused(const char* fn, const char* src_name, const void* src_dev, const float* profiles_dev, int num_profiles, const void* out_dev,
+                  int num_frames, int height, int width) {
+  return null_arg(fn, src_name, src_dev) || null_arg(fn, "profiles_dev", profiles_dev) || null_arg(fn, "out_dev", out_dev) ||
+         not_positive(fn, "num_profiles", num_profiles) || not_positive(fn, "num_frames", num_frames) ||
+         not_positive(fn, "height", height) || not_positive(fn, "width", width);
+}
+
 // the checks the two image entry points share; fills `a` (all but `cam`) when they pass
 int lens_check_and_fill(const char* fn, const float* rgb_dev, const float* profiles_dev, int num_profiles, const int32_t* profile_ids_dev,
                         void* out_dev, int num_frames, int height, int width, LensArgs* a) {
-  if (!rgb_dev) { set_error("%s: null rgb_dev", fn); return 2; }
-  if (!profiles_dev) { set_error("%s: null profiles_dev", fn); return 2; }
-  if (!out_dev) { set_error("%s: null out_dev", fn); return 2; }
-  if (num_profiles < 1) { set_error("%s: num_profiles = %d", fn, num_profiles); return 2; }
-  if (num_frames <= 0) { set_error("%s: num_frames = %d", fn, num_frames); return 2; }
-  if (height <= 0) { set_error("%s: height = %d", fn, height); return 2; }
-  if (width <= 0) { set_error("%s: width = %d", fn, width); return 2; }
+  if (lens_refused(fn, "rgb_dev", rgb_dev, profiles_dev, num_profiles, out_dev, num_frames, height, width)) return 2;
   if (out_dev == (const void*)rgb_dev) { set_error("%s: out_dev == rgb_dev (a gather cannot run in place)", fn); return 2; }
   const long long npix = (long long)height * width;
   const long long groups = (npix + 3) / 4;
-  const long long bpf = (groups + kLensBlock - 1) / kLensBlock;
-  if (npix > 0x7fffffffll || bpf * num_frames > 0x7fffffffll) {
-    set_error("%s: num_frames x height x width = %d x %d x %d exceeds one launch", fn, num_frames, height, width);
-    return 2;
-  }
+  FrameLaunch fl;
+  if (!frame_launch(groups, npix, kLensBlock, num_frames, &fl)) return refuse_image_launch(fn, num_frames, height, width);
   a->rgb = rgb_dev; a->profiles = profiles_dev; a->ids = profile_ids_dev; a->out = out_dev;
-  a->npix = (unsigned int)npix; a->groups = (unsigned int)groups; a->blocks_per_frame = (unsigned int)bpf;
+  a->npix = (unsigned int)npix; a->groups = (unsigned int)groups; a->blocks_per_frame = fl.blocks_per_frame;
   a->num_profiles = num_profiles; a->H = height; a->W = width;
   a->s = 2.0f / (float)width; a->hw = (float)width * 0.5f; a->hh = (float)height * 0.5f;
   return 0;
@@ -282,10 +282,8 @@ extern "C" int tacex_lens_camera_model(const float* rgb_dev, const float* lens_p
                                        int out_dtype, int num_frames, int height, int width, void* stream) {
   using namespace tacex;
   const char* fn = "tacex_lens_camera_model";
-  if (!lens_profiles_dev) { set_error("%s: null lens_profiles_dev", fn); return 2; }
-  if (num_lens_profiles < 1) { set_error("%s: num_lens_profiles = %d", fn, num_lens_profiles); return 2; }
-  if (!profiles_dev) { set_error("%s: null profiles_dev", fn); return 2; }
-  if (num_profiles < 1) { set_error("%s: num_profiles = %d", fn, num_profiles); return 2; }
+  if (null_arg(fn, "lens_profiles_dev", lens_profiles_dev) || not_positive(fn, "num_lens_profiles", num_lens_profiles) ||
+      null_arg(fn, "profiles_dev", profiles_dev) || not_positive(fn, "num_profiles", num_profiles)) return 2;
   LensArgs a{};
   const int rc = lens_check_and_fill(fn, rgb_dev, lens_profiles_dev, num_lens_profiles, lens_profile_ids_dev, out_dev, num_frames, height,
                                      width, &a);
@@ -301,24 +299,15 @@ extern "C" int tacex_lens_points(const double* xy_dev, const float* profiles_dev
                                  double* out_dev, int num_frames, int num_points, int height, int width, void* stream) {
   using namespace tacex;
   const char* fn = "tacex_lens_points";
-  if (!xy_dev) { set_error("%s: null xy_dev", fn); return 2; }
-  if (!profiles_dev) { set_error("%s: null profiles_dev", fn); return 2; }
-  if (!out_dev) { set_error("%s: null out_dev", fn); return 2; }
-  if (num_profiles < 1) { set_error("%s: num_profiles = %d", fn, num_profiles); return 2; }
-  if (num_frames <= 0) { set_error("%s: num_frames = %d", fn, num_frames); return 2; }
-  if (num_points <= 0) { set_error("%s: num_points = %d", fn, num_points); return 2; }
-  if (height <= 0) { set_error("%s: height = %d", fn, height); return 2; }
-  if (width <= 0) { set_error("%s: width = %d", fn, width); return 2; }
-  const long long bpf = ((long long)num_points + kLensBlock - 1) / kLensBlock;
-  if (bpf * num_frames > 0x7fffffffll) {
-    set_error("%s: num_frames x num_points = %d x %d exceeds one launch", fn, num_frames, num_points);
-    return 2;
-  }
+  if (lens_refused(fn, "xy_dev", xy_dev, profiles_dev, num_profiles, out_dev, num_frames, height, width) ||
+      not_positive(fn, "num_points", num_points)) return 2;
+  FrameLaunch fl;
+  if (!frame_launch(num_points, num_points, kLensBlock, num_frames, &fl)) return refuse_points_launch(fn, num_frames, num_points);
   PointArgs a{};
   a.xy = xy_dev; a.profiles = profiles_dev; a.ids = profile_ids_dev; a.out = out_dev;
-  a.n = (unsigned int)num_points; a.blocks_per_frame = (unsigned int)bpf; a.num_profiles = num_profiles;
+  a.n = (unsigned int)num_points; a.blocks_per_frame = fl.blocks_per_frame; a.num_profiles = num_profiles;
   a.s = 2.0 / (double)width; a.hw = (double)width * 0.5; a.hh = (double)height * 0.5;
-  hipLaunchKernelGGL(lens_points_kernel, dim3((unsigned int)(bpf * num_frames)), dim3(kLensBlock), 0, (hipStream_t)stream, a);
+  hipLaunchKernelGGL(lens_points_kernel, dim3(fl.grid), dim3(kLensBlock), 0, (hipStream_t)stream, a);
   const hipError_t e = hipGetLastError();
   return e == hipSuccess ? 0 : fail_hip(e, "lens_points_kernel");
 }

@@ -19,7 +19,7 @@ from dataclasses import dataclass
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, _stage
 
 
 def rest_plane_mm(gelpad_height: float, gelpad_to_camera_min_distance: float) -> float:
@@ -80,6 +80,8 @@ class TactileGelMemory:
     (num_envs,) int32 - device tensors; the ids may be written in place (at reset) or re-drawn with `randomize()`; an id outside
     [0, P) is the all-zero profile.  The table is rebuilt only when `dt` or `profiles` is assigned."""
 
+    coefficients, profile_ids = _stage.table_attr("rows"), _stage.table_attr("ids")
+
     def __init__(self, num_envs: int, resolution, profiles, terms: int = 1, dt: float = 1.0 / 60.0, device="cuda:0"):
         if int(num_envs) <= 0:
             raise ValueError(f"TactileGelMemory: num_envs = {num_envs}")
@@ -88,27 +90,18 @@ class TactileGelMemory:
         W, H = int(resolution[0]), int(resolution[1])
         if W <= 0 or H <= 0:
             raise ValueError(f"TactileGelMemory: resolution = {tuple(resolution)}")
-        profiles = self._checked(profiles)
-        self.coefficient_table(profiles, dt)  # (every ValueError of the arguments comes before the device is looked at)
+        self._profiles = self._checked(profiles)
+        self._lib, self._table = _stage.open_stage("TactileGelMemory", "coefficients", "profile_ids", self._profiles, GelMemoryProfile,
+                                                   num_envs, device, row=lambda p: p.row(dt))
         self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise _lib.TacexHipError(f"TactileGelMemory runs on the GPU only (device {self.device}): there is no CPU fallback")
-        self._lib = _lib.load_library()
         self.num_envs, self.terms, self.height, self.width = int(num_envs), int(terms), H, W
-        self._profiles, self._dt = profiles, None
-        self.coefficients = None
-        self.dt = dt  # (builds the table)
+        self._dt = float(dt)
         self.state = torch.zeros((self.num_envs, self.terms, H, W), dtype=torch.float32, device=self.device)
         self.live = torch.zeros((self.num_envs,), dtype=torch.int32, device=self.device)
-        self.profile_ids = torch.zeros((self.num_envs,), dtype=torch.int32, device=self.device)
 
     @staticmethod
     def _checked(profiles):
-        if isinstance(profiles, GelMemoryProfile):
-            profiles = [profiles]
-        profiles = list(profiles)
-        if not profiles or not all(isinstance(p, GelMemoryProfile) for p in profiles):
-            raise ValueError("TactileGelMemory: profiles must be a non-empty sequence of GelMemoryProfile")
+        profiles = _stage.profile_list("TactileGelMemory", "profiles", profiles, GelMemoryProfile)
         for p in profiles:
             p.validate()
         return profiles
@@ -119,11 +112,7 @@ class TactileGelMemory:
         return np.stack([p.row(dt) for p in profiles])
 
     def _rebuild(self):
-        table = torch.from_numpy(self.coefficient_table(self._profiles, self._dt))
-        if self.coefficients is not None and self.coefficients.shape == table.shape:
-            self.coefficients.copy_(table)  # (same storage: a captured graph keeps pointing at it)
-        else:
-            self.coefficients = table.to(self.device)
+        self._table.assign(self.coefficient_table(self._profiles, self._dt))  # (same storage when P stays: see ProfileTable.assign)
 
     @property
     def dt(self) -> float:
@@ -151,11 +140,9 @@ class TactileGelMemory:
     def num_profiles(self) -> int:
         return len(self._profiles)
 
-    def randomize(self, generator=None):
-        """Re-draw every env's profile id uniformly from [0, P) on the device."""
-        self.profile_ids.copy_(torch.randint(0, self.num_profiles, (self.num_envs,), dtype=torch.int32, device=self.device,
-                                             generator=generator))
-        return self.profile_ids
+    def randomize(self, env_ids=None, generator=None):
+        """Re-draw the profile ids of `env_ids` (default: all) uniformly from [0, P) on the device."""
+        return self._table.randomize(env_ids, generator)
 
     def reset(self, env_ids=None):
         """Zero the state and the live flag of `env_ids` (default: all); the other envs keep their imprint."""
@@ -176,20 +163,17 @@ class TactileGelMemory:
         step; `frame_min`, `indent` (num_envs,) float32 and `rows` (num_envs, 4) int32 (optional) receive what
         `tacex_indentation_depth` gives for the rewritten map."""
         B, K, H, W = self.state.shape
-        dev = self.state.device
-        if not isinstance(hm, torch.Tensor) or tuple(hm.shape) != (B, H, W) or hm.dtype != torch.float32 or not hm.is_contiguous():
-            raise ValueError(f"TactileGelMemory: hm must be a contiguous ({B}, {H}, {W}) float32 tensor")
-        if hm.device != dev:
-            raise _lib.TacexHipError(f"TactileGelMemory: hm is on {hm.device}, the model on {dev} (no CPU fallback)")
-        for name, t in (("frame_min", frame_min), ("indent", indent)):
-            if not isinstance(t, torch.Tensor) or tuple(t.shape) != (B,) or t.dtype != torch.float32 or not t.is_contiguous() or t.device != dev:
-                raise ValueError(f"TactileGelMemory: {name} must be a contiguous ({B},) float32 tensor on {dev}")
-        if rows is not None and (not isinstance(rows, torch.Tensor) or tuple(rows.shape) != (B, 4) or rows.dtype != torch.int32
-                                 or not rows.is_contiguous() or rows.device != dev):
-            raise ValueError(f"TactileGelMemory: rows must be a contiguous ({B}, 4) int32 tensor on {dev}")
-        ids, coef = self.profile_ids, self.coefficients
-        if ids.dtype != torch.int32 or tuple(ids.shape) != (B,) or not ids.is_contiguous() or ids.device != dev:
-            raise ValueError(f"TactileGelMemory: profile_ids must stay a ({B},) int32 tensor on {dev}")
+        dev = self._table.device
+
+        def arg(name, t, shape, dtype=torch.float32):
+            return _stage.check_tensor("TactileGelMemory", name, t, shape, dtype, dev)
+
+        arg("hm", hm, (B, H, W))
+        arg("frame_min", frame_min, (B,))
+        arg("indent", indent, (B,))
+        if rows is not None:
+            arg("rows", rows, (B, 4), torch.int32)
+        ids, coef = self._table.check()
         with torch.cuda.device(dev):
             rc = self._lib.tacex_gel_memory(_lib.ptr(hm), _lib.ptr(self.state), _lib.ptr(self.live), _lib.ptr(coef), int(coef.shape[0]),
                                             _lib.ptr(ids), rest_plane_mm(gelpad_height, gelpad_to_camera_min_distance),

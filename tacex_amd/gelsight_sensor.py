@@ -162,23 +162,23 @@ class GelSightSensor(SensorBase):
                 raise ValueError(f"gel memory is for {(model.num_envs, model.height, model.width)} (num_envs, H, W), the sensor's height map is {shape}")
         self._gel_memory = model
 
+    def _tactile_rgb(self, caller: str) -> torch.Tensor:
+        output = self.data.output  # (brings outdated buffers up to date)
+        if "tactile_rgb" not in output:
+            raise RuntimeError(f'{caller} needs "tactile_rgb" in cfg.data_types')
+        return output["tactile_rgb"]
+
     def camera_image(self, model, out: torch.Tensor | None = None) -> torch.Tensor:
         """The current `data.output["tactile_rgb"]` as the sensor's camera would deliver it: `model` (a `TactileCameraModel` of
         num_envs frames) applied in one launch on the current stream.  `tactile_rgb` itself is left as it is."""
-        output = self.data.output  # (brings outdated buffers up to date)
-        if "tactile_rgb" not in output:
-            raise RuntimeError('camera_image needs "tactile_rgb" in cfg.data_types')
-        return model(output["tactile_rgb"], out=out)
+        return model(self._tactile_rgb("camera_image"), out=out)
 
     def lens_image(self, lens, camera=None, out: torch.Tensor | None = None) -> torch.Tensor:
         """The current `data.output["tactile_rgb"]` seen through the sensor's lens: `lens` (a `TactileLensModel` of num_envs frames)
         applied in one launch on the current stream -> float32.  With `camera` (a `TactileCameraModel`) the camera model runs on the
         gathered colour in the same launch -> the camera's dtype, what `camera(lens(tactile_rgb))` gives.  `tactile_rgb` itself is
         left as it is."""
-        output = self.data.output  # (brings outdated buffers up to date)
-        if "tactile_rgb" not in output:
-            raise RuntimeError('lens_image needs "tactile_rgb" in cfg.data_types')
-        return lens(output["tactile_rgb"], out=out, camera=camera)
+        return lens(self._tactile_rgb("lens_image"), out=out, camera=camera)
 
     def contact_field(self, model, slip: torch.Tensor | None = None, image=False):
         """The contact force field of the current `data.output["height_map"]`: `model` (a `TactileContactModel` of num_envs frames)

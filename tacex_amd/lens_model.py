@@ -19,7 +19,7 @@ from dataclasses import dataclass
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, _stage
 from .camera_model import _OUT_DTYPES, TactileCameraModel
 
 
@@ -89,22 +89,13 @@ class TactileLensModel:
     caller may write in place (ids at reset, like `TactileCameraModel.profile_ids`; an id outside [0, P) is the identity profile).
     `image_size` (H, W): the frame size `distort_points` assumes; every `__call__` sets it to the size of its image."""
 
+    profiles, profile_ids = _stage.table_attr("rows"), _stage.table_attr("ids")
+
     def __init__(self, profiles, num_frames: int, device, image_size=None):
-        if isinstance(profiles, LensProfile):
-            profiles = [profiles]
-        rows = [p.row() if isinstance(p, LensProfile) else None for p in profiles]
-        if not rows or any(r is None for r in rows):
-            raise ValueError("TactileLensModel: profiles must be a non-empty sequence of LensProfile")
-        if int(num_frames) <= 0:
-            raise ValueError(f"TactileLensModel: num_frames = {num_frames}")
+        self._lib, self._table = _stage.open_stage("TactileLensModel", "profiles", "profile_ids", profiles, LensProfile, num_frames, device)
         self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise _lib.TacexHipError(f"TactileLensModel runs on the GPU only (device {self.device}): there is no CPU fallback")
-        self._lib = _lib.load_library()
         self.num_frames = int(num_frames)
         self.image_size = None if image_size is None else (int(image_size[0]), int(image_size[1]))
-        self.profiles = torch.from_numpy(np.stack(rows)).to(self.device)
-        self.profile_ids = torch.zeros(self.num_frames, dtype=torch.int32, device=self.device)
 
     @property
     def num_profiles(self) -> int:
@@ -112,21 +103,7 @@ class TactileLensModel:
 
     def randomize(self, env_ids=None, generator=None):
         """Re-draw the profile ids of `env_ids` (default: all) uniformly from [0, P) on the device."""
-        n = self.num_frames if env_ids is None else len(env_ids)
-        ids = torch.randint(0, self.num_profiles, (n,), dtype=torch.int32, device=self.device, generator=generator)
-        if env_ids is None:
-            self.profile_ids.copy_(ids)
-        else:
-            self.profile_ids[torch.as_tensor(env_ids, dtype=torch.long, device=self.device)] = ids
-        return self.profile_ids
-
-    def _tables(self, device):
-        ids, prof = self.profile_ids, self.profiles
-        if ids.dtype != torch.int32 or tuple(ids.shape) != (self.num_frames,) or not ids.is_contiguous() or ids.device != device:
-            raise ValueError(f"TactileLensModel: profile_ids must stay a ({self.num_frames},) int32 tensor on {device}")
-        if prof.dtype != torch.float32 or prof.dim() != 2 or prof.shape[1] != 16 or not prof.is_contiguous() or prof.device != device:
-            raise ValueError(f"TactileLensModel: profiles must stay a (P, 16) float32 tensor on {device}")
-        return ids, prof
+        return self._table.randomize(env_ids, generator)
 
     def __call__(self, rgb: torch.Tensor, out: torch.Tensor | None = None, camera: TactileCameraModel | None = None,
                  call: int | None = None) -> torch.Tensor:
@@ -134,52 +111,37 @@ class TactileLensModel:
         the gather alone -> float32.  `camera` a `TactileCameraModel` of the same num_frames: the gather and the camera model in the
         same launch -> the camera's dtype, bit-equal to `camera(lens(rgb))`; the camera's `call` counter is used and advanced as its
         own `__call__` would (`call` overrides it).  `out`: same shape, the result's dtype, never `rgb` itself; allocated when None."""
-        if not isinstance(rgb, torch.Tensor) or rgb.dim() != 4 or rgb.shape[0] != self.num_frames or rgb.shape[3] != 3:
-            raise ValueError(f"TactileLensModel: rgb must be a ({self.num_frames}, H, W, 3) tensor, got "
-                             f"{tuple(rgb.shape) if isinstance(rgb, torch.Tensor) else type(rgb).__name__}")
-        if rgb.dtype != torch.float32 or not rgb.is_contiguous() or rgb.shape[1] < 1 or rgb.shape[2] < 1:
-            raise ValueError("TactileLensModel: rgb must be float32, contiguous and non-empty")
-        if rgb.device != self.profiles.device:
-            raise _lib.TacexHipError(f"TactileLensModel: rgb is on {rgb.device}, the model on {self.profiles.device} (no CPU fallback)")
+        B, dev = self.num_frames, self._table.device
+        _stage.check_tensor("TactileLensModel", "rgb", rgb, (B, "H", "W", 3), torch.float32, dev)
         if camera is not None:
             if not isinstance(camera, TactileCameraModel):
                 raise ValueError(f"TactileLensModel: camera must be a TactileCameraModel, got {type(camera).__name__}")
-            if camera.num_frames != self.num_frames:
-                raise ValueError(f"TactileLensModel: the camera model has {camera.num_frames} frames, the lens model {self.num_frames}")
-            if camera.profiles.device != rgb.device:
-                raise ValueError(f"TactileLensModel: the camera model is on {camera.profiles.device}, rgb on {rgb.device}")
+            if camera.num_frames != B:
+                raise ValueError(f"TactileLensModel: the camera model has {camera.num_frames} frames, the lens model {B}")
+            if camera.profiles.device != dev:
+                raise ValueError(f"TactileLensModel: the camera model is on {camera.profiles.device}, rgb on {dev}")
         elif call is not None:
             raise ValueError("TactileLensModel: call numbers the camera model's noise draws; it needs camera=")
         dtype = torch.float32 if camera is None else camera.dtype
         if out is None:
-            out = torch.empty(rgb.shape, dtype=dtype, device=rgb.device)
-        elif (not isinstance(out, torch.Tensor) or out.shape != rgb.shape or out.dtype != dtype or not out.is_contiguous()
-              or out.device != rgb.device):
-            raise ValueError(f"TactileLensModel: out must be a contiguous {tuple(rgb.shape)} {dtype} tensor on {rgb.device}")
+            out = torch.empty(rgb.shape, dtype=dtype, device=dev)
+        else:
+            _stage.check_tensor("TactileLensModel", "out", out, tuple(rgb.shape), dtype, dev)
         if out.data_ptr() == rgb.data_ptr():
             raise ValueError("TactileLensModel: out must not be rgb (a gather cannot run in place)")
-        ids, prof = self._tables(rgb.device)
-        B, H, W = self.num_frames, int(rgb.shape[1]), int(rgb.shape[2])
+        ids, prof = self._table.check()
+        H, W = int(rgb.shape[1]), int(rgb.shape[2])
         self.image_size = (H, W)
-        stream = _lib.current_stream_handle(rgb.device)
+        stream = _lib.current_stream_handle(dev)
         if camera is None:
-            with torch.cuda.device(rgb.device):
+            with torch.cuda.device(dev):
                 rc = self._lib.tacex_lens_model(_lib.ptr(rgb), _lib.ptr(prof), int(prof.shape[0]), _lib.ptr(ids), _lib.ptr(out), B, H, W, stream)
             _lib.check(rc, "tacex_lens_model")
             return out
-        cids, cprof = camera.profile_ids, camera.profiles
-        if cids.dtype != torch.int32 or tuple(cids.shape) != (B,) or not cids.is_contiguous() or cids.device != rgb.device:
-            raise ValueError(f"TactileCameraModel: profile_ids must stay a ({B},) int32 tensor on {rgb.device}")
-        if cprof.dtype != torch.float32 or cprof.dim() != 2 or cprof.shape[1] != 16 or not cprof.is_contiguous() or cprof.device != rgb.device:
-            raise ValueError(f"TactileCameraModel: profiles must stay a (P, 16) float32 tensor on {rgb.device}")
-        if call is None:
-            call = camera.call
-            camera.call = (camera.call + 1) & 0xFFFFFFFF
-        elif not 0 <= int(call) < 2 ** 32:
-            raise ValueError("TactileLensModel: call must fit 32 bits")
-        with torch.cuda.device(rgb.device):
+        cids, cprof, call = camera._tables_and_call(call)
+        with torch.cuda.device(dev):
             rc = self._lib.tacex_lens_camera_model(_lib.ptr(rgb), _lib.ptr(prof), int(prof.shape[0]), _lib.ptr(ids), _lib.ptr(cprof),
-                                                   int(cprof.shape[0]), _lib.ptr(cids), camera.seed, camera.frame_offset, int(call),
+                                                   int(cprof.shape[0]), _lib.ptr(cids), camera.seed, camera.frame_offset, call,
                                                    _lib.ptr(out), _OUT_DTYPES[camera.dtype], B, H, W, stream)
         _lib.check(rc, "tacex_lens_camera_model")
         return out
@@ -195,6 +157,8 @@ class TactileLensModel:
                 raise ValueError("TactileLensModel: distort_points needs height= and width= (or image_size=) before the first image")
             height = self.image_size[0] if height is None else height
             width = self.image_size[1] if width is None else width
+        dev = self._table.device
+        # (xy is the one argument that need not be contiguous, and a 4-d one may have any float dtype: it is converted below)
         if not isinstance(xy, torch.Tensor) or xy.dim() not in (3, 4) or xy.shape[0] != self.num_frames or xy.shape[-1] != 2 \
                 or (xy.dim() == 4 and xy.shape[1] != 2) or xy.numel() == 0 or not xy.dtype.is_floating_point:
             raise ValueError(f"TactileLensModel: xy must be a ({self.num_frames}, N, 2) float64 or ({self.num_frames}, 2, M, 2) float tensor, got "
@@ -203,19 +167,18 @@ class TactileLensModel:
             raise ValueError(f"TactileLensModel: a ({self.num_frames}, N, 2) xy must be float64, got {xy.dtype}")
         if int(height) < 1 or int(width) < 1:
             raise ValueError(f"TactileLensModel: height x width = {height} x {width}")
-        if xy.device != self.profiles.device:
-            raise _lib.TacexHipError(f"TactileLensModel: xy is on {xy.device}, the model on {self.profiles.device} (no CPU fallback)")
-        if out is not None and (not isinstance(out, torch.Tensor) or out.shape != xy.shape or out.dtype != xy.dtype or not out.is_contiguous()
-                                or out.device != xy.device):
-            raise ValueError(f"TactileLensModel: out must be a contiguous {tuple(xy.shape)} {xy.dtype} tensor on {xy.device}")
-        ids, prof = self._tables(xy.device)
+        if xy.device != dev:
+            raise _lib.TacexHipError(f"TactileLensModel: xy is on {xy.device}, the model on {dev} (no CPU fallback)")
+        if out is not None:
+            _stage.check_tensor("TactileLensModel", "out", out, tuple(xy.shape), xy.dtype, dev)
+        ids, prof = self._table.check()
         direct = xy.dtype == torch.float64 and xy.is_contiguous()
         src = xy if direct else xy.to(torch.float64).contiguous()
         dst = (out if out is not None else torch.empty_like(src)) if direct else src  # a converted copy is moved in place
         n = src.numel() // (2 * self.num_frames)
-        with torch.cuda.device(xy.device):
+        with torch.cuda.device(dev):
             rc = self._lib.tacex_lens_points(_lib.ptr(src), _lib.ptr(prof), int(prof.shape[0]), _lib.ptr(ids), _lib.ptr(dst), self.num_frames,
-                                             n, int(height), int(width), _lib.current_stream_handle(xy.device))
+                                             n, int(height), int(width), _lib.current_stream_handle(dev))
         _lib.check(rc, "tacex_lens_points")
         if direct:
             return dst
