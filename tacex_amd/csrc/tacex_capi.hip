@@ -744,7 +744,26 @@ struct PassState { float* z[2]; float* tmp; const float *sa, *sb, *pd; int n_fus
 // How the band levels of a pass are launched: frames per launch of a level; streams the chunks alternate on (1 = the caller's alone);
 // depth_interleaved: the pass's deferred depth pass runs chunk by chunk on the chunk's stream (false: none, or in full ahead of the levels);
 // order_early: the item order of the streaming tail is issued beside the levels.
-struct LevelPlan { int frames, streams, n_chunks; bool depth_interleaved, order_early; };
+// pipelined: the levels of successive chunks share a launch (run_band_pipeline) - even and odd chunks as two pipelines on the two streams.
+struct LevelPlan { int frames, streams, n_chunks; bool depth_interleaved, order_early, pipelined; };
+
+// TACEX_BAND_LEAN: 1 (default) = lean loads and no stores for skipped bands in the matrix-core levels (BlurArgs::lean), 0 = full loads
+static bool band_lean() {
+  static const bool v = !(getenv("TACEX_BAND_LEAN") && atoi(getenv("TACEX_BAND_LEAN")) == 0);
+  return v;
+}
+// TACEX_BAND_WLDS: 1 (default) = the matrix-core levels read their Toeplitz weights from a copy of the level's filter in LDS and fetch the
+// H-pass operands ahead of the barrier (BlurArgs::wlds), 0 = the lane-indexed weight tables from global memory
+static bool band_wlds() {
+  static const bool v = !(getenv("TACEX_BAND_WLDS") && atoi(getenv("TACEX_BAND_WLDS")) == 0);
+  return v;
+}
+// TACEX_BAND_PIPE: 1 = the levels of successive chunks in one launch (blur_mfma_pipe_kernel) where the two-streams path would run and the level
+// set has a fused kernel, 0 (default) = one launch per level and chunk.  Measured 3 % slower on the headline (profiles/band_pipeline.md).
+static bool band_pipe() {
+  static const bool v = getenv("TACEX_BAND_PIPE") && atoi(getenv("TACEX_BAND_PIPE")) != 0;
+  return v;
+}
 
 static LevelPlan plan_band_levels(const tacex_taxim_ctx* c, const Pass& p, const PassState& s) {
   LevelPlan lp{};
@@ -754,7 +773,7 @@ static LevelPlan plan_band_levels(const tacex_taxim_ctx* c, const Pass& p, const
   // TWO CHUNKS IN FLIGHT: the chunks of a pass are independent until the tail, and a band-level launch of 128-256 frames spends
   // ~14 us of its 40-77 us ramping up and draining (k = 61: 45.5 us for 128 frames, 76.9 for 256).  Chunks therefore run round-robin on the
   // caller's stream and on streams of the context's own - at a chunk size divided by the stream count, so that the frames in flight (and
-  // their three buffers in the Infinity Cache) stay what they were.  Single-kernel (matrix-core) levels only: the two-pass
+  // their three buffers in the Infinity Cache) stay what they were (frames up to 320x240: at 4/5 of it, below).  Single-kernel (matrix-core) levels only: the two-pass
   // fallback shares one scratch image.  Not while profiling: the stage timers bracket launches on the caller's stream.
   static const int lvl_streams_env = getenv("TACEX_LEVEL_STREAMS") ? atoi(getenv("TACEX_LEVEL_STREAMS")) : 2;
   const int lvl_streams = lvl_streams_env > tacex_taxim_ctx::kMaxLvlStreams ? tacex_taxim_ctx::kMaxLvlStreams : lvl_streams_env;
@@ -765,8 +784,25 @@ static LevelPlan plan_band_levels(const tacex_taxim_ctx* c, const Pass& p, const
   for (int l = 0; dual && l < s.n_band; ++l)
     dual = blur_level_single_kernel(c->levels[l], l == 0, c->H, c->W);
   lp.streams = dual ? lvl_streams : 1;
-  if (dual && level_chunk_env() < 0) lp.frames = (lp.frames + lvl_streams - 1) / lvl_streams;  // (an explicit chunk size is taken as given)
+  if (dual && level_chunk_env() < 0) {  // (an explicit chunk size is taken as given)
+    if ((size_t)c->H * c->W <= (size_t)240 * 320) {
+      // Frames up to 320x240: launches of 4/5 of the budget, in a multiple of the stream count - 10 x 205 frames for a 2048-frame pass, 6 x 171
+      // for 1024.  Six alternating pairs against launches of half the budget (128): 748.4 K -> 781.8 K frames/s (+4.5 %, ranges 7.0 / 10.0 K);
+      // 1024 frames +3.7 % with six launches, +0.9 % with five of 205 (the streams get 3 and 2).  profiles/band_pipeline.md.
+      const int target = (lp.frames * 4 + 4) / 5;
+      const int launches = ((p.B + target - 1) / target + lvl_streams - 1) / lvl_streams * lvl_streams;
+      lp.frames = (p.B + launches - 1) / launches;
+    } else {
+      lp.frames = (lp.frames + lvl_streams - 1) / lvl_streams;  // (640x480: 47 and 64 frames measured within 1.5 % of these 32)
+    }
+  }
   lp.n_chunks = (p.B + lp.frames - 1) / lp.frames;
+  // PIPELINED SCHEDULE: under the conditions of the two-streams path, where the level set has a fused kernel that holds the per-level
+  // launches' workgroups per CU (asked once per device and width).  An error of that query leaves the per-level schedule.
+  if (dual && lvl_streams == 2 && band_pipe() && blur_pipe_supported(c->levels, s.n_band, c->H, c->W)) {
+    bool ok = false;
+    if (blur_pipe_resident(c->levels, s.n_band, c->H, c->W, band_lean() && p.rows, band_wlds(), &ok) == hipSuccess && ok) lp.pipelined = true;
+  }
   // A deferred depth pass is interleaved with the band levels only where that pays: chunks alternating on two streams, and chunks of
   // >= 128 frames (the pass runs one workgroup per frame).  Measured (profiles/r05_experiments.md section 15): 320x240 in 128-frame chunks
   // +3.2 % on C3; 640x480 in its 32-frame chunks -11 %, in units of 128-1024 frames -0.5..-4 %.  Otherwise: in full, ahead of the levels.
@@ -781,16 +817,85 @@ static LevelPlan plan_band_levels(const tacex_taxim_ctx* c, const Pass& p, const
   return lp;
 }
 
-// TACEX_BAND_LEAN: 1 (default) = lean loads and no stores for skipped bands in the matrix-core levels (BlurArgs::lean), 0 = full loads
-static bool band_lean() {
-  static const bool v = !(getenv("TACEX_BAND_LEAN") && atoi(getenv("TACEX_BAND_LEAN")) == 0);
-  return v;
+// What a band level of a pass does in every chunk: where it writes, whether it runs lean and may leave its skipped bands unwritten, the rows /
+// columns by which the non-zero range of its input exceeds the contact rows / columns.
+struct BandLevel { float* dst; bool last, lean, unread; int grow, grow_x; };
+static void plan_band_level_calls(const tacex_taxim_ctx* c, const Pass& p, const PassState& s, BandLevel* bl) {
+  int grow = 0, grow_x = 0;
+  for (int l = 0; l < s.n_band; ++l) {
+    BandLevel& b = bl[l];
+    b.last = l == c->n_levels - 1;
+    b.dst = (b.last && p.z_out) ? p.z_out : s.z[l & 1];
+    // LEAN LEVELS (TACEX_BAND_LEAN=0: off): a matrix-core level of a zero gel map that has the contact rectangle loads the height map
+    // and its input inside the (grown) rectangle only.  It may also leave its skipped bands unwritten when EVERY reader of dst is
+    // range-aware - the level buffers then hold stale data there, see PassLayout:
+    //  - the next band level, if it is a lean matrix-core level too: its V-pass loads row yy only for yy in [lo - G, hi + G], G = this
+    //    level's input growth g + its radius R, and this level skips a band [b, b + 15] only if b - R > hi + g or b + 15 + R < lo - g:
+    //    no such yy lies in a skipped band;
+    //  - the streaming tail, handed the rows: it loads zin only on rows in [lo - band_grow, hi + band_grow] (issue_row), band_grow =
+    //    g + R of the last band level: the same two inequalities, so every row it loads lies in a band that was stored.
+    // Never when dst is the caller's (z_out, mask_out: last level of the pyramid), nor ahead of the tiled tail, shade_kernel or a
+    // VALU / generic level: they read every row.
+    b.lean = band_lean() && p.rows && c->levels[l].gel_zero;
+    b.unread = b.lean && b.dst != p.z_out && !b.last;
+    if (b.unread && l + 1 < s.n_band)
+      b.unread = c->levels[l + 1].gel_zero && blur_level_single_kernel(c->levels[l + 1], false, c->H, c->W);
+    else if (b.unread)
+      b.unread = s.stream_tail && stream_tail_range_aware(c->levels);
+    b.grow = grow; b.grow_x = grow_x;
+    grow += (c->levels[l].kh - 1) / 2;
+    grow_x += (c->levels[l].kw - 1) / 2;
+  }
 }
-// TACEX_BAND_WLDS: 1 (default) = the matrix-core levels read their Toeplitz weights from a copy of the level's filter in LDS and fetch the
-// H-pass operands ahead of the barrier (BlurArgs::wlds), 0 = the lane-indexed weight tables from global memory
-static bool band_wlds() {
-  static const bool v = !(getenv("TACEX_BAND_WLDS") && atoi(getenv("TACEX_BAND_WLDS")) == 0);
-  return v;
+
+// PIPELINED SCHEDULE of the band levels (LevelPlan::pipelined, TACEX_BAND_PIPE=1): even and odd chunks form two pipelines on the two streams, and
+// launch step t of a pipeline runs level l of the pipeline's chunk t - l for every l that has one, as the roles of ONE grid
+// (blur_mfma_pipe_kernel): chunks + n_band - 1 launches of several rounds of workgroups per pipeline in place of chunks x n_band launches of
+// one round.  A chunk's deferred depth pass runs in line, ahead of the step that starts the chunk, as in the per-level schedule.
+// WHY THE ROLES OF A LAUNCH, AND THE LAUNCHES IN FLIGHT, NEVER ALIAS: every buffer a level touches is indexed by FRAME - level l reads
+// z[(l - 1) & 1] + b0 npix (level 0: the height map) and writes z[l & 1] + b0 npix, on the frames [b0, b0 + n) of ITS chunk alone, and the
+// per-frame scalars and contact rectangles likewise.  The roles of one launch work on different chunks, the two pipelines on disjoint sets
+// of chunks, so no two of them share a frame.  Level l + 1 of a chunk follows level l of it one launch step later on the same stream.
+static int run_band_pipeline(tacex_taxim_ctx* c, const Pass& p, const PassState& s, const LevelPlan& lp, const BandLevel* bl, const StreamPlan* tail_plan,
+                             bool order_early, bool* order_done) {
+  const size_t npix = (size_t)c->H * c->W;
+  const int P = lp.streams, L = s.n_band, N = lp.n_chunks;
+  auto chunk = [&](int n) { const int b0 = n * lp.frames; return p.slice(b0, p.B - b0 < lp.frames ? p.B - b0 : lp.frames); };
+  const int steps = (N + P - 1) / P + L - 1;
+  for (int t = 0; t < steps; ++t) {
+    for (int j = 0; j < P; ++j) {
+      hipStream_t const pst = j > 0 ? c->lvl_stream[j - 1] : p.stream;
+      PipeLevelCall calls[kPipeMaxRoles] = {};
+      bool any = false;
+      for (int l = 0; l < L; ++l) {
+        const int n = j + (t - l) * P;  // the chunk of role l
+        if (t < l || n >= N) continue;
+        const int b0 = n * lp.frames;
+        const Pass q = chunk(n);
+        const BandLevel& b = bl[l];
+        PipeLevelCall& k = calls[l];
+        k.src = l > 0 ? bl[l - 1].dst + b0 * npix : nullptr; k.hm = q.hm; k.sa = s.sa + b0; k.sb = s.sb + b0; k.pd = s.pd + b0;
+        k.dst = b.dst + b0 * npix; k.mask_out = b.last ? q.mask_out : nullptr; k.B = q.B; k.restore = b.last ? 0 : 1;
+        k.rows_ext = q.rows; k.ext_grow = b.grow; k.ext_grow_x = b.grow_x; k.zero_bands_unread = b.unread;
+        any = true;
+      }
+      if (!any) continue;
+      const int n0 = j + t * P;  // the chunk this step starts
+      if (lp.depth_interleaved && n0 < N) {
+        if (int rc = run_depth_pass(chunk(n0).depth, c->H, c->W, pst)) return rc;
+        if (order_early && n0 == N - 2) {  // (as in the per-level schedule: the other stream's order launch waits for this stream's last depth pass)
+          if (!c->order_evt) HIP_TRY(hipEventCreateWithFlags(&c->order_evt, hipEventDisableTiming), "hipEventCreate");
+          HIP_TRY(hipEventRecord(c->order_evt, pst), "hipEventRecord");
+        } else if (order_early && n0 == N - 1) {
+          HIP_TRY(hipStreamWaitEvent(pst, c->order_evt, 0), "hipStreamWaitEvent");
+          HIP_TRY(run_stream_order(c->levels, c->n_levels, s.n_fused, *tail_plan, p.B, c->H, p.rows, s.band_grow, c->stream_order, pst, order_done),
+                  "stream_order_kernel");
+        }
+      }
+      HIP_TRY(run_blur_pipe(c->levels, L, calls, c->gel_dev, c->H, c->W, c->contact_scale, bl[0].lean, band_wlds(), pst), "blur levels (pipelined)");
+    }
+  }
+  return 0;
 }
 
 // The band levels of a pass, chunk by chunk: fork onto the level streams, the deferred depth pass, the early item order, the join.
@@ -822,8 +927,14 @@ static int run_band_levels(tacex_taxim_ctx* c, const Pass& p, const PassState& s
   if (order_early && !lp.depth_interleaved)  // rows from the caller: ready behind the fork; on the second stream, ahead of its first chunk
     HIP_TRY(run_stream_order(c->levels, c->n_levels, s.n_fused, *tail_plan, p.B, c->H, p.rows, s.band_grow, c->stream_order, c->lvl_stream[0], order_done),
             "stream_order_kernel");
+  BandLevel bl[TACEX_MAX_LEVELS];
+  plan_band_level_calls(c, p, s, bl);
   const float* src = nullptr;
-  for (int b0 = 0, chunk_no = 0; b0 < p.B; b0 += lp.frames, ++chunk_no) {
+  if (lp.pipelined) {
+    if (int rc = run_band_pipeline(c, p, s, lp, bl, tail_plan, order_early, order_done)) return rc;
+    src = bl[s.n_band - 1].dst;
+  }
+  for (int b0 = 0, chunk_no = 0; b0 < p.B && !lp.pipelined; b0 += lp.frames, ++chunk_no) {
     const Pass q = p.slice(b0, p.B - b0 < lp.frames ? p.B - b0 : lp.frames);
     const int lane = dual ? chunk_no % lp.streams : 0;
     hipStream_t const cst = lane > 0 ? c->lvl_stream[lane - 1] : st;  // the chunk's stream
@@ -839,34 +950,14 @@ static int run_band_levels(tacex_taxim_ctx* c, const Pass& p, const PassState& s
       }
     }
     src = nullptr;
-    int grow = 0, grow_x = 0;  // rows / columns by which the non-zero range of the level's input exceeds the contact rows / columns
     for (int l = 0; l < s.n_band; ++l) {
-      const bool last = l == c->n_levels - 1;
-      float* dst = (last && p.z_out) ? p.z_out : s.z[l & 1];
-      // LEAN LEVELS (TACEX_BAND_LEAN=0: off): a matrix-core level of a zero gel map that has the contact rectangle loads the height map
-      // and its input inside the (grown) rectangle only.  It may also leave its skipped bands unwritten when EVERY reader of dst is
-      // range-aware - the level buffers then hold stale data there, see PassLayout:
-      //  - the next band level, if it is a lean matrix-core level too: its V-pass loads row yy only for yy in [lo - G, hi + G], G = this
-      //    level's input growth g + its radius R, and this level skips a band [b, b + 15] only if b - R > hi + g or b + 15 + R < lo - g:
-      //    no such yy lies in a skipped band;
-      //  - the streaming tail, handed the rows: it loads zin only on rows in [lo - band_grow, hi + band_grow] (issue_row), band_grow =
-      //    g + R of the last band level: the same two inequalities, so every row it loads lies in a band that was stored.
-      // Never when dst is the caller's (z_out, mask_out: last level of the pyramid), nor ahead of the tiled tail, shade_kernel or a
-      // VALU / generic level: they read every row.
-      const bool lean = band_lean() && q.rows && c->levels[l].gel_zero;
-      bool unread = lean && dst != p.z_out && !last;
-      if (unread && l + 1 < s.n_band)
-        unread = c->levels[l + 1].gel_zero && blur_level_single_kernel(c->levels[l + 1], false, c->H, c->W);
-      else if (unread)
-        unread = s.stream_tail && stream_tail_range_aware(c->levels);
+      const BandLevel& b = bl[l];
       StageTimer t(c, cst, 1 + l);
-      HIP_TRY(run_blur_level(c->levels[l], src ? src + b0 * npix : nullptr, q.hm, c->gel_dev, s.sa + b0, s.sb + b0, s.pd + b0, dst + b0 * npix,
-                             s.tmp, last ? q.mask_out : nullptr, q.B, c->H, c->W, c->contact_scale, last ? 0 : 1, l == 0, cst, q.rows, grow, grow_x, lean, unread,
-                             band_wlds()),
+      HIP_TRY(run_blur_level(c->levels[l], src ? src + b0 * npix : nullptr, q.hm, c->gel_dev, s.sa + b0, s.sb + b0, s.pd + b0, b.dst + b0 * npix,
+                             s.tmp, b.last ? q.mask_out : nullptr, q.B, c->H, c->W, c->contact_scale, b.last ? 0 : 1, l == 0, cst, q.rows, b.grow, b.grow_x,
+                             b.lean, b.unread, band_wlds()),
               "blur level");
-      grow += (c->levels[l].kh - 1) / 2;
-      grow_x += (c->levels[l].kw - 1) / 2;
-      src = dst;
+      src = b.dst;
     }
   }
   if (dual) {  // the tail (and whatever the caller enqueues next) waits for the odd chunks

@@ -60,6 +60,17 @@ hipError_t run_blur_level(const LevelDesc& lv, const float* src, const float* hm
                           uint8_t* mask_out, int B, int H, int W, float contact_scale, int restore,
                           bool first, hipStream_t st, const int* rows_ext = nullptr, int ext_grow = 0, int ext_grow_x = 0, bool lean = false,
                           bool zero_bands_unread = false, bool wlds = false);
+// Pipelined band levels: level l of chunk s - l for every l in ONE launch (blur_mfma_pipe_kernel, taxim_mfma.hip); what run_blur_level
+// takes per level, per role.  B == 0: the role has no chunk in this launch.
+constexpr int kPipeMaxRoles = 3;
+struct PipeLevelCall {
+  const float* src; const float* hm; const float *sa, *sb, *pd; float* dst; uint8_t* mask_out;
+  int B, restore; const int* rows_ext; int ext_grow, ext_grow_x; bool zero_bands_unread;
+};
+bool blur_pipe_supported(const LevelDesc* lv, int n, int H, int W);
+hipError_t blur_pipe_resident(const LevelDesc* lv, int n, int H, int W, bool lean, bool wlds, bool* ok);
+hipError_t run_blur_pipe(const LevelDesc* lv, int n, const PipeLevelCall* calls, const float* gel, int H, int W, float contact_scale, bool lean,
+                         bool wlds, hipStream_t st);
 bool frame_rows_supported(int H, int W);
 hipError_t run_fill_rows(int* rows, int B, int H, int W, hipStream_t st);
 hipError_t run_frame_rows(const float* in, bool from_depth, float* hm_out, float* fmin, float* indent, uint8_t* cam_u8,

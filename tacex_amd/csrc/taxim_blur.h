@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "tacex_internal.h"
+
 namespace tacex {
 
 struct BlurArgs {
@@ -37,5 +39,12 @@ struct BlurArgs {
 
 bool mfma_supported(int k, bool first, int H, int W);
 hipError_t dispatch_mfma(int k, bool first, const BlurArgs& a, hipStream_t st);
+
+// Pipe kernel (taxim_mfma.hip): level r of one chunk of frames for every r in one launch - roles[r] is that level's argument block as
+// run_blur_level fills it, over its own chunk; B == 0: the role has no chunk in this launch.  All roles: zero gel map, the same `lean`.
+bool mfma_pipe_supported(const int* ks, int n, int H, int W);  // the level set (kernel sizes, level 0 first) has an instantiation
+// *ok: the fused kernel holds as many workgroups per CU on the current device as the per-level launches (asked once per device and width)
+hipError_t mfma_pipe_resident(const int* ks, int n, int H, int W, bool lean, bool wlds, bool* ok);
+hipError_t dispatch_mfma_pipe(const int* ks, int n, int H, int W, bool lean, bool wlds, const BlurArgs* roles, hipStream_t st);
 
 }  // namespace tacex

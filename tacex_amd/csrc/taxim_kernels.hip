@@ -984,22 +984,59 @@ BlurRoute blur_level_route(const LevelDesc& lv, bool first, int H, int W) {
 
 bool blur_level_single_kernel(const LevelDesc& lv, bool first, int H, int W) { return blur_level_route(lv, first, H, W) == kRouteMfma; }
 
+// argument block of a matrix-core level: the one place (run_blur_level and the pipelined schedule, run_blur_pipe)
+static BlurArgs mfma_level_args(const LevelDesc& lv, const float* src, const float* hm, const float* gel, const float* sa, const float* sb,
+                                const float* pd, float* dst, uint8_t* mask_out, int B, int H, int W, float contact_scale, int restore,
+                                const int* rows_ext, int ext_grow, int ext_grow_x, bool lean, bool zero_bands_unread, bool wlds) {
+  BlurArgs a{};
+  a.src = src; a.hm = hm; a.shift_a = sa; a.shift_b = sb; a.pdepth = pd;
+  a.rows_ext = lv.gel_zero ? rows_ext : nullptr; a.ext_grow = ext_grow; a.ext_grow_x = ext_grow_x;  // zero-band / zero-block skipping needs J = min(S, 0)
+  a.lean = (lean && a.rows_ext) ? 1 : 0; a.zero_bands_unread = (a.lean && zero_bands_unread) ? 1 : 0;
+  a.gel = lv.gel_zero ? nullptr : gel;  // all-zero gel map (GelSight Mini): no gel loads - half of level 0's V-pass reads
+  a.dst = dst; a.mask_out = mask_out; a.taps = lv.taps_mfma_dev; a.H = H; a.W = W; a.B = B;
+  a.contact_scale = contact_scale; a.restore = restore; a.wlds = wlds ? 1 : 0;
+  return a;
+}
+
+// Pipelined band levels (blur_mfma_pipe_kernel): the level set lv[0 .. n) - all matrix-core levels of a zero gel map - has a fused kernel ..
+bool blur_pipe_supported(const LevelDesc* lv, int n, int H, int W) {
+  int ks[kPipeMaxRoles];
+  if (n < 1 || n > kPipeMaxRoles) return false;
+  for (int l = 0; l < n; ++l) {
+    if (!lv[l].gel_zero || !blur_level_single_kernel(lv[l], l == 0, H, W)) return false;
+    ks[l] = lv[l].kw;
+  }
+  return mfma_pipe_supported(ks, n, H, W);
+}
+// .. which keeps the workgroups per CU of the per-level launches on the current device ..
+hipError_t blur_pipe_resident(const LevelDesc* lv, int n, int H, int W, bool lean, bool wlds, bool* ok) {
+  int ks[kPipeMaxRoles];
+  for (int l = 0; l < n; ++l) ks[l] = lv[l].kw;
+  return mfma_pipe_resident(ks, n, H, W, lean, wlds, ok);
+}
+// .. and one launch of it: level l over calls[l].B frames (0: the role is idle in this launch)
+hipError_t run_blur_pipe(const LevelDesc* lv, int n, const PipeLevelCall* calls, const float* gel, int H, int W, float contact_scale, bool lean,
+                         bool wlds, hipStream_t st) {
+  int ks[kPipeMaxRoles];
+  BlurArgs roles[kPipeMaxRoles];
+  for (int l = 0; l < n; ++l) {
+    const PipeLevelCall& q = calls[l];
+    ks[l] = lv[l].kw;
+    roles[l] = mfma_level_args(lv[l], q.src, q.hm, gel, q.sa, q.sb, q.pd, q.dst, q.mask_out, q.B, H, W, contact_scale, q.restore, q.rows_ext, q.ext_grow,
+                               q.ext_grow_x, lean, q.zero_bands_unread, wlds);
+  }
+  return dispatch_mfma_pipe(ks, n, H, W, lean, wlds, roles, st);  // (lean: the caller has the contact rectangles of every role's chunk)
+}
+
 hipError_t run_blur_level(const LevelDesc& lv, const float* src, const float* hm, const float* gel,
                           const float* sa, const float* sb, const float* pd, float* dst, float* tmp,
                           uint8_t* mask_out, int B, int H, int W, float contact_scale, int restore,
                           bool first, hipStream_t st, const int* rows_ext, int ext_grow, int ext_grow_x, bool lean, bool zero_bands_unread,
                           bool wlds) {
   const BlurRoute route = blur_level_route(lv, first, H, W);
-  if (route == kRouteMfma) {
-    BlurArgs a{};
-    a.src = src; a.hm = hm; a.shift_a = sa; a.shift_b = sb; a.pdepth = pd;
-    a.rows_ext = lv.gel_zero ? rows_ext : nullptr; a.ext_grow = ext_grow; a.ext_grow_x = ext_grow_x;  // zero-band / zero-block skipping needs J = min(S, 0)
-    a.lean = (lean && a.rows_ext) ? 1 : 0; a.zero_bands_unread = (a.lean && zero_bands_unread) ? 1 : 0;
-    a.gel = lv.gel_zero ? nullptr : gel;  // all-zero gel map (GelSight Mini): no gel loads - half of level 0's V-pass reads
-    a.dst = dst; a.mask_out = mask_out; a.taps = lv.taps_mfma_dev; a.H = H; a.W = W; a.B = B;
-    a.contact_scale = contact_scale; a.restore = restore; a.wlds = wlds ? 1 : 0;
-    return dispatch_mfma(lv.kw, first, a, st);
-  }
+  if (route == kRouteMfma)
+    return dispatch_mfma(lv.kw, first, mfma_level_args(lv, src, hm, gel, sa, sb, pd, dst, mask_out, B, H, W, contact_scale, restore, rows_ext, ext_grow,
+                                                       ext_grow_x, lean, zero_bands_unread, wlds), st);
   if (route == kRouteBandLoop384 || route == kRouteBandLoop640) {
     BlurArgs a{};
     a.src = src; a.hm = hm; a.gel = gel; a.shift_a = sa; a.shift_b = sb; a.pdepth = pd;

@@ -55,8 +55,11 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 // (stored +0.0f); for the height map the operand J = min(S, 0) = +0.0f is selected / the mask bit cleared by the same predicate
 // (S >= 0 outside the rectangle: it comes from the same float32 expression).  No branch encloses a load, an LDS read or an MFMA:
 // the instruction stream is the one of the full kernel with buffer_load in place of global_load.
-template <int K, bool FIRST, int NTILE, bool GZ, bool LEAN, bool WLDS>
-__global__ __launch_bounds__(640) void blur_mfma_kernel(BlurArgs a) {
+// The body is a device function: blur_mfma_kernel runs it over its own grid (block index and count from blockIdx / gridDim),
+// blur_mfma_pipe_kernel (PIPE) runs the bodies of several levels, of different chunks of frames, side by side in sub-ranges of one grid
+// and hands each its role-local block index and block count.
+template <int K, bool FIRST, int NTILE, bool GZ, bool LEAN, bool WLDS, bool PIPE = false>
+__device__ __forceinline__ void blur_mfma_body(const BlurArgs a, int block, int nblocks) {
   static_assert(GZ || !LEAN, "the lean loads need J = min(S, 0)");
   static_assert(!WLDS || !TACEX_MFMA_H_CONSEC, "WLDS reads the H weights in the default contraction map");
   constexpr unsigned kNoLoad = 0x80000000u;  // buffer offset beyond every frame: the range check drops the load, the lane reads 0
@@ -74,7 +77,7 @@ __global__ __launch_bounds__(640) void blur_mfma_kernel(BlurArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   float* mid = reinterpret_cast<float*>(smem_raw);  // TH x pitch, columns padded by RA on both sides
   const int H = a.H, W = a.W, pitch = a.pitch;
-  const int lid = xcd_remap(blockIdx.x, gridDim.x);
+  const int lid = PIPE ? xcd_remap(block, nblocks) : xcd_remap(blockIdx.x, gridDim.x);
   const int frame = lid / a.nbands;
   const int band = lid - frame * a.nbands;
   // the last band of a frame is shifted up when TH does not divide H: its first rows recompute (identically) what the
@@ -165,7 +168,9 @@ __global__ __launch_bounds__(640) void blur_mfma_kernel(BlurArgs a) {
 #ifndef TACEX_MFMA_WLDS_HPRE
 #define TACEX_MFMA_WLDS_HPRE 1  // (A/B hook: 0 = every instantiation reads the H weights behind the barrier)
 #endif
-  constexpr bool HPRE = WLDS && TACEX_MFMA_WLDS_HPRE && (LEAN ? (K == 33 || (K == 61 && FIRST)) : K <= 61);
+  // PIPE (a role of blur_mfma_pipe_kernel): the lean k = 33 level reads them behind the barrier - with both lean levels holding them across it
+  // the fused kernel needs 68 VGPRs, or spills one at 64 (profiles/band_pipeline.md).
+  constexpr bool HPRE = WLDS && TACEX_MFMA_WLDS_HPRE && (LEAN ? ((K == 33 && !PIPE) || (K == 61 && FIRST)) : K <= 61);
   float wh[WLDS ? KS : 1];
   float pd_pre = 0.0f;
   auto read_wh = [&]() {
@@ -372,6 +377,162 @@ __global__ __launch_bounds__(640) void blur_mfma_kernel(BlurArgs a) {
   }
 }
 
+template <int K, bool FIRST, int NTILE, bool GZ, bool LEAN, bool WLDS>
+__global__ __launch_bounds__(640) void blur_mfma_kernel(BlurArgs a) {
+  blur_mfma_body<K, FIRST, NTILE, GZ, LEAN, WLDS>(a, blockIdx.x, gridDim.x);
+}
+
+// PIPE KERNEL: the levels of SUCCESSIVE chunks of frames in one grid.  The levels of one frame depend on each other, the chunks of a pass
+// do not: level 0 of chunk n, level 1 of chunk n - 1, level 2 of chunk n - 2 .. are independent work ("roles").  Role r owns the blocks
+// [first[r], first[r + 1]) of the grid, of which the first nblocks[r] run the body of level r with their role-local index; the rest
+// (each range is padded to a multiple of 8, so that block % 8 - the XCD - is the same in the role as in the grid and xcd_remap keeps
+// the bands of a frame on one XCD) return at once.  A role without a chunk has no blocks.  No workgroup waits for another: order between
+// the launches comes from the stream.  The role is workgroup-uniform, so each body keeps its own barrier.
+struct PipeArgs {
+  BlurArgs role[kPipeMaxRoles];
+  int first[kPipeMaxRoles + 1];
+  int nblocks[kPipeMaxRoles];
+};
+
+template <bool GZ, bool LEAN, bool WLDS, int R, int K, int... KN>
+__device__ __forceinline__ void pipe_role(const PipeArgs& p, int b) {
+  if (b < p.first[R + 1]) {
+    const int lb = b - p.first[R];
+    if (lb < p.nblocks[R]) blur_mfma_body<K, R == 0, 1, GZ, LEAN, WLDS, true>(p.role[R], lb, p.nblocks[R]);
+    return;
+  }
+  if constexpr (sizeof...(KN) > 0) pipe_role<GZ, LEAN, WLDS, R + 1, KN...>(p, b);
+}
+
+template <bool GZ, bool LEAN, bool WLDS, int K0, int... KN>
+// (eight waves per SIMD - 64 VGPRs, six workgroups of five waves per CU like the levels - asked for: left alone the allocator takes 66-68)
+__global__ __launch_bounds__(640, 8) void blur_mfma_pipe_kernel(PipeArgs p) {
+  pipe_role<GZ, LEAN, WLDS, 0, K0, KN...>(p, (int)blockIdx.x);
+}
+
+static void mfma_geometry(int K, BlurArgs* a) {
+  const int RA = ((K - 1) / 2 + 7) & ~7;
+  a->row0 = 0;
+  a->nbands = a->H / 16;
+  a->padx = RA;
+  a->pitch = a->W + 2 * RA + 4;  // (as launch_mfma_tiles)
+  if (((a->pitch >> 2) & 1) == 0) a->pitch += 4;
+}
+
+// Workgroups per CU of a level as launch_mfma_tiles launches it: the most of {lane tables, filter copy per wave, copy per workgroup}.
+// *n_min becomes the lesser of itself and that count.
+template <int K, bool FIRST, bool GZ, bool LEAN>
+static hipError_t level_resident(int W, bool wlds, int* n_min) {
+  BlurArgs g{}; g.H = 16; g.W = W;
+  mfma_geometry(K, &g);
+  const size_t lds = (size_t)16 * g.pitch * sizeof(float), wbytes = (size_t)mfma_wpad_floats(K) * sizeof(float);
+  auto kern = blur_mfma_kernel<K, FIRST, 1, GZ, LEAN, false>;
+  static size_t granted[64] = {};
+  int n = 0;
+  if (hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), lds, granted); e != hipSuccess) return e;
+  if (hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, reinterpret_cast<const void*>(kern), W, lds); e != hipSuccess) return e;
+  if constexpr (!TACEX_MFMA_H_CONSEC) {
+    if (wlds) {
+      auto kern_w = blur_mfma_kernel<K, FIRST, 1, GZ, LEAN, true>;
+      static size_t granted_w[64] = {};
+      if (hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(kern_w), lds + (size_t)(W / 64) * wbytes, granted_w); e != hipSuccess) return e;
+      for (const size_t l : {lds + (size_t)(W / 64) * wbytes, lds + wbytes}) {
+        int m = 0;
+        if (hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&m, reinterpret_cast<const void*>(kern_w), W, l); e != hipSuccess) return e;
+        if (m > n) n = m;
+      }
+    }
+  }
+  if (n < *n_min) *n_min = n;
+  return hipSuccess;
+}
+
+// How a pipe kernel is launched on a device at a width: decided once (PipePlan::W), like the WLDS mode of launch_mfma_tiles.
+// mode 1: every role takes its filter copy per wave; 2: per workgroup where the per-wave copies would not fit the launch's LDS (the
+// largest role's `mid` + one copy), per wave elsewhere; 0: lane tables; -1: the fused kernel would hold fewer workgroups per CU than
+// the per-level launches do - not launched, the caller keeps the per-level schedule.
+struct PipePlan { int W, mode; size_t lds; int shared[kPipeMaxRoles]; };
+
+template <bool GZ, bool LEAN, int K0, int... KN>
+static hipError_t pipe_plan(int W, bool wlds, const PipePlan** out) {
+  constexpr int N = 1 + sizeof...(KN);
+  constexpr int ks[N] = {K0, KN...};
+  static PipePlan plans[64][2] = {};
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
+  PipePlan& pl = plans[dev][wlds ? 1 : 0];
+  *out = &pl;
+  if (pl.W == W) return hipSuccess;
+  // what the per-level launches hold today: the least of the roles
+  int n_ref = 1 << 30, r = 0;
+  hipError_t e = level_resident<K0, true, GZ, LEAN>(W, wlds, &n_ref);
+  ((e = e != hipSuccess ? e : level_resident<KN, false, GZ, LEAN>(W, wlds, &n_ref)), ...);
+  if (e != hipSuccess) return e;
+  size_t mid[N], wb[N], lds_mid = 0, lds_wave = 0, lds_wg = 0;
+  for (r = 0; r < N; ++r) {
+    BlurArgs g{}; g.H = 16; g.W = W;
+    mfma_geometry(ks[r], &g);
+    mid[r] = (size_t)16 * g.pitch * sizeof(float);
+    wb[r] = (size_t)mfma_wpad_floats(ks[r]) * sizeof(float);
+    lds_mid = mid[r] > lds_mid ? mid[r] : lds_mid;
+    lds_wave = mid[r] + (W / 64) * wb[r] > lds_wave ? mid[r] + (W / 64) * wb[r] : lds_wave;
+    lds_wg = mid[r] + wb[r] > lds_wg ? mid[r] + wb[r] : lds_wg;
+  }
+  auto kern = blur_mfma_pipe_kernel<GZ, LEAN, false, K0, KN...>;
+  static size_t granted[64] = {}, granted_w[64] = {};
+  pl.mode = -1;
+  if constexpr (!TACEX_MFMA_H_CONSEC) {
+    if (wlds) {
+      auto kern_w = blur_mfma_pipe_kernel<GZ, LEAN, true, K0, KN...>;
+      if (e = ensure_dynamic_lds(reinterpret_cast<const void*>(kern_w), lds_wave, granted_w); e != hipSuccess) return e;
+      int n_wave = 0, n_wg = 0;
+      e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n_wave, reinterpret_cast<const void*>(kern_w), W, lds_wave);
+      if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n_wg, reinterpret_cast<const void*>(kern_w), W, lds_wg);
+      if (e != hipSuccess) return e;
+      if (n_wave >= n_ref) { pl.mode = 1; pl.lds = lds_wave; }
+      else if (n_wg >= n_ref) { pl.mode = 2; pl.lds = lds_wg; }
+      for (r = 0; r < N; ++r) pl.shared[r] = (pl.mode == 2 && mid[r] + (W / 64) * wb[r] > lds_wg) ? 1 : 0;
+    }
+  }
+  if (pl.mode < 0) {
+    if (e = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), lds_mid, granted); e != hipSuccess) return e;
+    int n_old = 0;
+    if (e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n_old, reinterpret_cast<const void*>(kern), W, lds_mid); e != hipSuccess) return e;
+    if (n_old >= n_ref) { pl.mode = 0; pl.lds = lds_mid; }
+  }
+  pl.W = W;
+  return hipSuccess;
+}
+
+template <bool GZ, bool LEAN, int K0, int... KN>
+static hipError_t launch_pipe(const BlurArgs* roles, int W, bool wlds, hipStream_t st) {
+  constexpr int N = 1 + sizeof...(KN);
+  constexpr int ks[N] = {K0, KN...};
+  const PipePlan* pl = nullptr;
+  if (hipError_t e = pipe_plan<GZ, LEAN, K0, KN...>(W, wlds, &pl); e != hipSuccess) return e;
+  if (pl->mode < 0) return hipErrorInvalidConfiguration;
+  PipeArgs p{};
+  int at = 0;
+  for (int r = 0; r < N; ++r) {
+    p.role[r] = roles[r];
+    mfma_geometry(ks[r], &p.role[r]);
+    p.role[r].wlds_shared = pl->shared[r];
+    p.first[r] = at;
+    p.nblocks[r] = roles[r].B > 0 ? p.role[r].nbands * roles[r].B : 0;
+    at += (p.nblocks[r] + 7) & ~7;
+  }
+  for (int r = N; r <= kPipeMaxRoles; ++r) p.first[r] = at;
+  if (at == 0) return hipSuccess;
+  if constexpr (!TACEX_MFMA_H_CONSEC) {
+    if (pl->mode > 0) {
+      hipLaunchKernelGGL((blur_mfma_pipe_kernel<GZ, LEAN, true, K0, KN...>), dim3(at), dim3(W), pl->lds, st, p);
+      return hipGetLastError();
+    }
+  }
+  hipLaunchKernelGGL((blur_mfma_pipe_kernel<GZ, LEAN, false, K0, KN...>), dim3(at), dim3(W), pl->lds, st, p);
+  return hipGetLastError();
+}
+
 template <int K, bool FIRST, int NTILE, bool GZ, bool LEAN = false>
 static hipError_t launch_mfma_tiles(BlurArgs a, int row0, int nbands, hipStream_t st) {
   constexpr int TH = 16 * NTILE, R = (K - 1) / 2, RA = (R + 7) & ~7;
@@ -466,6 +627,30 @@ hipError_t dispatch_mfma(int k, bool first, const BlurArgs& a, hipStream_t st) {
     case 9: return launch_mfma<9, false>(a, st);
     default: return hipErrorInvalidValue;
   }
+}
+
+// The pipe kernel is instantiated for the default level set of W = 320, {61, 33, 17}, with the zero gel map and 16-row bands; everything
+// else keeps the per-level launches.  Not for {117, 61, 33, 15} (W = 640): its lean instantiations need 66 - 76 VGPRs, and spill 2 - 6 of
+// them when held to 64 (profiles/band_pipeline.md).
+bool mfma_pipe_supported(const int* ks, int n, int H, int W) {
+  if (TACEX_MFMA_H_CONSEC || TACEX_MFMA_NT61 != 1) return false;
+  for (int l = 0; l < n; ++l)
+    if (!mfma_supported(ks[l], l == 0, H, W)) return false;
+  return n == 3 && ks[0] == 61 && ks[1] == 33 && ks[2] == 17;
+}
+
+hipError_t mfma_pipe_resident(const int* ks, int n, int H, int W, bool lean, bool wlds, bool* ok) {
+  *ok = false;
+  if (!mfma_pipe_supported(ks, n, H, W)) return hipErrorInvalidValue;
+  const PipePlan* pl = nullptr;
+  const hipError_t e = lean ? pipe_plan<true, true, 61, 33, 17>(W, wlds, &pl) : pipe_plan<true, false, 61, 33, 17>(W, wlds, &pl);
+  *ok = e == hipSuccess && pl->mode >= 0;
+  return e;
+}
+
+hipError_t dispatch_mfma_pipe(const int* ks, int n, int H, int W, bool lean, bool wlds, const BlurArgs* roles, hipStream_t st) {
+  if (!mfma_pipe_supported(ks, n, H, W)) return hipErrorInvalidValue;
+  return lean ? launch_pipe<true, true, 61, 33, 17>(roles, W, wlds, st) : launch_pipe<true, false, 61, 33, 17>(roles, W, wlds, st);
 }
 
 }  // namespace tacex
