@@ -1023,6 +1023,61 @@ int tacex_gel_memory(float* hm_mm_dev, float* state_dev, int32_t* live_dev, cons
                      float* frame_min_dev, float* indent_mm_dev, int32_t* frame_rows_dev, int num_frames, int height, int width,
                      int terms, void* stream);
 
+/* Relief tile library as a height-map source: every env presses its own tile of a library - a height field sampled bilinearly, on a
+ * flat, spherical or cylindrical carrier, under a pose the caller writes in place - into hm_mm_dev (B,H,W) f32 [mm] in ONE launch on
+ * `stream` (tacex_amd/csrc/relief_source.hip); frame minimum, indentation depth and contact ranges of the map come out of the same
+ * launch.  B = num_frames.  The projection is orthographic, as in tacex_height_map_from_indenters, and the relief is displaced along
+ * the optical axis: a height field without undercuts.  All operations are float32, each rounded on its own (no fused multiply-add),
+ * in the order of the parentheses.
+ * Library: texels_dev f32, all tiles back to back, each row-major; a texel is the relief height [mm] standing proud of the carrier,
+ *   -inf means "no material here" (NaN and +inf are refused by the host layer);
+ *   tiles_i_dev (P,4) int32, P = num_tiles, row [first texel, rows Th, cols Tw, wrap 0/1];
+ *   tiles_f_dev (P,4) f32, row [pitch_mm, top_mm, u0, v0]: the texel pitch, the largest finite texel of the tile, and the anchor in
+ *   texel coordinates - the carrier's origin, by default the tile centre ((Tw-1)/2, (Th-1)/2);
+ *   relief_ids_dev (B,) int32, read on the device (NULL: tile 0 for every frame); an id outside [0, P) gives far clip everywhere and
+ *   the library is not read (like kind < 0 of tacex_height_map_from_indenters).
+ * Pose: pose_dev (B,16) f32, written in place by the caller between steps:
+ *     [0..5] m00 m01 m02 m10 m11 m12   [6] press_mm   [7..9] t0 tx ty   [10] carrier   [11] radius_mm R   [12] gain   [13] du  [14] dv
+ *     [15] 0
+ *   M maps a pixel to texel coordinates; press_mm is how far the relief's highest point sits below the gel top where the carrier is 0;
+ *   (t0, tx, ty) tilt the whole object [mm, mm/px]; carrier 0 plane, 1 sphere, 2 cylinder with its axis along the tile's u (any other
+ *   value: plane); gain scales the relief (>= 0); (du, dv) scroll the texture against the carrier [texels] (rolling).
+ * Per sample at x = column, y = row as float32:
+ *     u = ((m00*x) + (m01*y)) + m02            v = ((m10*x) + (m11*y)) + m12
+ *     s = (u - u0)*pitch                        t = (v - v0)*pitch                 object frame [mm]
+ *     plane:    c = 0
+ *     sphere:   q = (s*s) + (t*t);   c = q <= R*R ? R - sqrtf(max(R*R - q, 0)) : +inf
+ *     cylinder: q = t*t;             the same expression
+ *     uu = u + du;  vv = v + dv
+ *     if !(|uu| < 2^30 && |vv| < 2^30):  h = -inf
+ *     else  fu = floorf(uu), fv = floorf(vv), a = uu - fu, b = vv - fv, i0 = (int)fu, j0 = (int)fv
+ *       wrap:     i0, i0+1, j0, j0+1 taken modulo Tw / Th (non-negative modulo)
+ *       no wrap:  outside 0 <= uu <= float(Tw-1) or 0 <= vv <= float(Th-1):  h = -inf;  otherwise i0 = min(i0, Tw-1),
+ *                 i1 = min(i0+1, Tw-1), j0 and j1 likewise with Th
+ *       with h00 = texel[j0][i0], h01 = texel[j0][i1], h10 = texel[j1][i0], h11 = texel[j1][i1]:
+ *       h = (((h00*(1-a)) + (h01*a))*(1-b)) + (((h10*(1-a)) + (h11*a))*b)
+ *     depth = (((gel_top - press) + c) + (gain*(top - h))) + ((t0 + (tx*x)) + (ty*y))
+ *     d = depth < far_clip ? depth : far_clip                                       a NaN gives far clip
+ *   A sample that touches a -inf texel is no material (0 * -inf = NaN: far clip); a sample whose carrier is +inf is far clip and
+ *   reads no texel.
+ * samples (a host argument) 1: hm = d at (x, y) = (column, row).  samples 4: hm = ((d0 + d1) + (d2 + d3)) * 0.25 of the clamped
+ *   values d at (x-0.25, y-0.25), (x+0.25, y-0.25), (x-0.25, y+0.25), (x+0.25, y+0.25), in this order: the anti-aliasing for stamp
+ *   edges and for tiles finer than the pixel.
+ * Outputs besides hm: frame_min_dev (B,) f32, indent_mm_dev (B,) f32 (nullable) and frame_rows_dev (B,4) int32 (nullable) are
+ *   exactly what tacex_indentation_depth(hm, gelpad_height_m, gelpad_to_camera_min_distance_m, ...) writes for that map (without
+ *   indent_mm_dev the ranges are those of a press depth of 0).
+ * One workgroup per frame and no atomics between workgroups: the same inputs give the same bits on every call, alone or in a batch.
+ * Texel indices are 32-bit: the library holds fewer than 2^31 texels.
+ * Returns 2 before any HIP call, writing nothing, for a NULL texels_dev, tiles_i_dev, tiles_f_dev, pose_dev, hm_mm_dev or
+ * frame_min_dev, num_tiles, num_frames, height or width <= 0, width % 4 != 0, height or width above 2048, samples not 1 or 4, and an
+ * hm_mm_dev that is not 16-byte aligned.  The call was added without a change of TACEX_ABI_VERSION (no existing signature or struct
+ * moved): a caller detects it by looking the symbol up, not by the version. */
+int tacex_height_map_from_relief(const float* texels_dev, const int32_t* tiles_i_dev, const float* tiles_f_dev, int num_tiles,
+                                 const int32_t* relief_ids_dev, const float* pose_dev, float gel_top_mm, float far_clip_mm,
+                                 float gelpad_height_m, float gelpad_to_camera_min_distance_m, float* hm_mm_dev, float* frame_min_dev,
+                                 float* indent_mm_dev, int32_t* frame_rows_dev, int num_frames, int height, int width, int samples,
+                                 void* stream);
+
 #ifdef __cplusplus
 }
 #endif

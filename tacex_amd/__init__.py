@@ -8,6 +8,7 @@ from .gelsight_sensor_data import GelSightSensorData
 from .gelsight_sensor_group import GelSightSensorGroup
 from .height_map_source import AffineBodyDepthSource, FemSurfaceDepthSource, FemTractionImage, IndenterHeightMapSource, MeshDepthSource, MeshLibraryDepthSource
 from .lens_model import LensProfile, TactileLensModel
+from .relief_source import ReliefHeightMapSource, ReliefTile
 
 __all__ = ["AffineBodyDepthSource", "CameraProfile", "ContactField", "ContactGel", "GelMemoryProfile", "GelSightSensor", "GelSightSensorCfg", "GelSightSensorData", "GelSightSensorGroup", "FemSurfaceDepthSource", "FemTractionImage", "IndenterHeightMapSource", "LensProfile", "MeshDepthSource",
-           "MeshLibraryDepthSource", "TactileCameraModel", "TactileContactModel", "TactileGelMemory", "TactileLensModel", "slip_from_fots"]
+           "MeshLibraryDepthSource", "ReliefHeightMapSource", "ReliefTile", "TactileCameraModel", "TactileContactModel", "TactileGelMemory", "TactileLensModel", "slip_from_fots"]

@@ -184,6 +184,7 @@ SIGNATURES = {
     "tacex_lens_points": (_i, [_vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _vp]),
     "tacex_contact_field": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _f, _vp, _i, _i, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "tacex_gel_memory": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _f, _f, _f, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "tacex_height_map_from_relief": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _f, _f, _f, _f, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
 }
 
 _lib = None

@@ -141,7 +141,8 @@ class GelSightSensor(SensorBase):
 
     def set_height_map_source(self, source):
         """Fill the height map from an on-device source (e.g. `IndenterHeightMapSource`) instead of a camera depth image
-        (SURVEY 8f n1).  `source.fill(hm, frame_min, indent, gelpad_height, gelpad_to_camera_min_distance)`."""
+        (SURVEY 8f n1).  `source.fill(hm, frame_min, indent, gelpad_height, gelpad_to_camera_min_distance)`; a source with the
+        attribute `writes_frame_rows = True` (`ReliefHeightMapSource`) is also given `rows=` the Taxim provider's contact ranges."""
         if self._group is not None:
             raise RuntimeError("a grouped sensor takes its height map from the camera depth or set_height_map (one source per group)")
         self._height_map_source = source
@@ -428,13 +429,19 @@ class GelSightSensor(SensorBase):
             hm = self._data.output["height_map"]
             sim = self._fused_targets()
             fmin = sim._frame_min if sim is not None else self._scratch_min()
+            # a source that also writes the contact ranges (`writes_frame_rows`, ReliefHeightMapSource) fills the provider's: the render
+            # then takes its band-lean path instead of recomputing them
+            rows = getattr(sim, "_frame_rows", None) if getattr(src, "writes_frame_rows", False) else None
+            extra = {} if rows is None else {"rows": rows}
             src.fill(hm, fmin, sim._indentation_depth if sim is not None else None,
                      float(sim.cfg.gelpad_height) if sim is not None else 0.0,
-                     float(sim.cfg.gelpad_to_camera_min_distance) if sim is not None else 0.0)
+                     float(sim.cfg.gelpad_to_camera_min_distance) if sim is not None else 0.0, **extra)
             self._height_map_version += 1
             if sim is not None:
                 sim._frame_min_version = self._height_map_version
                 sim._indent_version = self._height_map_version
+                if rows is not None:
+                    sim._frame_rows_version = self._height_map_version
             return hm
         depth = self._read_camera_depth()
         if depth is None:
