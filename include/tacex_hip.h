@@ -1078,6 +1078,69 @@ int tacex_height_map_from_relief(const float* texels_dev, const int32_t* tiles_i
                                  float* indent_mm_dev, int32_t* frame_rows_dev, int num_frames, int height, int width, int samples,
                                  void* stream);
 
+/* Signed-distance volume library as a height-map source: every env presses its own volume of a library - a grid of signed distances
+ * sampled trilinearly and sphere-traced along the optical axis, under a full rigid pose, uniform scale and iso level the caller
+ * writes in place - into hm_mm_dev (B,H,W) f32 [mm] (tacex_amd/csrc/volume_source.hip).  B = num_frames.  Two launches on
+ * `stream`: the marching kernel, then the kernel of tacex_indentation_depth on the map it wrote.  The projection is orthographic, as
+ * in tacex_height_map_from_indenters: a pixel's camera-frame point is X = column*pixmm, Y = row*pixmm, Z = depth [mm].  All
+ * operations are float32, each rounded on its own (no fused multiply-add), in the order of the parentheses; 1/v is the correctly
+ * rounded quotient; "c ? a : b" with a NaN in c's comparison takes b.
+ * Library: voxels_dev f32 (num_voxels), all grids back to back, each (D,Hv,Wv) with index order z, y, x; a voxel is the signed
+ *   distance [object mm] at that grid point, negative inside (the host layer refuses non-finite values);
+ *   volumes_i_dev (P,4) int32, P = num_volumes, row [first voxel, D, Hv, Wv];
+ *   volumes_f_dev (P,8) f32, row [pitch_mm, i0, j0, k0, step_scale, 0, 0, 0]: the voxel pitch, the anchor - the voxel coordinates
+ *   (x, y, z) of the object frame's origin, by default the grid centre ((Wv-1)/2, (Hv-1)/2, (D-1)/2) - and the factor in (0, 1]
+ *   that shortens every step (for fields that are only a lower bound of the distance);
+ *   volume_ids_dev (B,) int32, read on the device (NULL: volume 0 for every frame).
+ * Pose: pose_dev (B,16) f32, written in place by the caller between steps:
+ *     [0..8] R row-major, object -> camera   [9..11] tx ty tz [mm]   [12] scale   [13] level_mm   [14] [15] 0 (not read)
+ *   A camera point P lies at o = R^T (P - t) / scale in the object frame, at q = o / pitch + anchor in voxel coordinates; the
+ *   surface is {sdf = level}: a positive level inflates the object.
+ * Per frame (from the pose row r[0..15] and the volume row), with N = (Wv, Hv, D), anchor = (i0, j0, k0) and a = 0, 1, 2 the
+ * object axes x, y, z:
+ *     g = scale*pitch          inv = 1/g          vox = g                                  one voxel pitch in camera mm
+ *     ax[a] = (r[a]*pixmm)*inv     ay[a] = (r[3+a]*pixmm)*inv     az[a] = r[6+a]*inv
+ *     q0[a] = anchor[a] - ((((r[a]*tx) + (r[3+a]*ty)) + (r[6+a]*tz))*inv)
+ *     par[a] = !(|az[a]| >= 1e-12f)          ia[a] = par[a] ? 0 : 1/az[a]          hmax[a] = float(N[a] - 1)
+ *   The frame is FAR CLIP EVERYWHERE, and the library is not read, when the id is outside [0, P); when the volume row has
+ *   first < 0, an axis < 2 or first + D*Hv*Wv > num_voxels; or unless g > 0, step_scale > 0, |level| < 2^30 and all twelve of
+ *   |ax[a]|, |ay[a]|, |az[a]|, |q0[a]| < 2^30 (a NaN or inf in the pose fails these).
+ * Per pixel at x = column, y = row as float32:
+ *     b[a] = (q0[a] + (x*ax[a])) + (y*ay[a])                                              q[a](z) = b[a] + (z*az[a])
+ *   clipping, starting from lo = near_clip, hi = far_clip, for a = 0, 1, 2 in turn:
+ *     par[a]:   the interval is empty unless b[a] >= 0 && b[a] <= hmax[a]
+ *     else      t1 = (0 - b[a])*ia[a];  t2 = (hmax[a] - b[a])*ia[a];  tn = t1 < t2 ? t1 : t2;  tf = t1 < t2 ? t2 : t1
+ *               lo = tn > lo ? tn : lo;   hi = tf < hi ? tf : hi
+ *   The pixel is far clip, and reads no voxel, when the interval is empty, unless lo <= hi, or unless all |b[a]| < 2^30.
+ *   marching:  z = lo;  for n = 0 .. max_steps-1:
+ *     tap at z: for each a  c = q[a](z);  c = c > 0 ? c : 0;  c = c < hmax[a] ? c : hmax[a];  m[a] = min((int)floorf(c), N[a]-2);
+ *               w[a] = c - float(m[a])          (the upper neighbour m[a]+1 stays in the grid)
+ *       with v[dz][dy][dx] = voxel[first + ((m[2]+dz)*Hv + (m[1]+dy))*Wv + (m[0]+dx)] and lerp(p, q, t) = p + (t*(q - p)):
+ *       x then y then z:  e[dz][dy] = lerp(v[dz][dy][0], v[dz][dy][1], w[0]);  f[dz] = lerp(e[dz][0], e[dz][1], w[1]);
+ *       s = lerp(f[0], f[1], w[2])
+ *     d = ((s - level)*scale)*step_scale
+ *     if d < tol_mm:  depth = z, done            (also a ray that enters its interval inside the object: cut flat by box or near clip)
+ *     z = z + d                                  (d >= tol_mm here: the step is max(d, tol_mm))
+ *     if !(z <= hi):  depth = far_clip, done     (the ray left its interval; a NaN ends here)
+ *     if n == max_steps-1:  depth = d < vox ? z : far_clip          the grazing-ray rule: the last tap was within one voxel
+ *   hm = depth < far_clip ? depth : far_clip
+ * Outputs besides hm: frame_min_dev (B,) f32, indent_mm_dev (B,) f32 (nullable) and frame_rows_dev (B,4) int32 (nullable) are
+ *   exactly what tacex_indentation_depth(hm, gelpad_height_m, gelpad_to_camera_min_distance_m, ...) writes for that map - its
+ *   kernel runs as the second launch (without indent_mm_dev the ranges are those of a press depth of 0).
+ * A workgroup marches a 32 x 8 tile of one frame (four waves of 16 x 4 neighbouring pixels), no atomics and no dependence on the
+ * batch: the same inputs give the same bits on every call, alone or in a batch.  Voxel indices are 32-bit (num_voxels < 2^31),
+ * offsets into hm 64-bit.
+ * Returns 2 before any HIP call, writing nothing, for a NULL voxels_dev, volumes_i_dev, volumes_f_dev, pose_dev, hm_mm_dev or
+ * frame_min_dev, num_voxels, num_volumes, num_frames, height or width <= 0, width % 4 != 0, height or width above 2048, more
+ * tiles than one launch takes, pixmm not > 0, max_steps outside 1..128, tol_mm not > 0, near_clip_mm >= far_clip_mm (or a NaN),
+ * and an hm_mm_dev that is not 16-byte aligned.  The call was added without a change of TACEX_ABI_VERSION (no existing signature
+ * or struct moved): a caller detects it by looking the symbol up, not by the version. */
+int tacex_height_map_from_sdf(const float* voxels_dev, int num_voxels, const int32_t* volumes_i_dev, const float* volumes_f_dev,
+                              int num_volumes, const int32_t* volume_ids_dev, const float* pose_dev, float pixmm, float near_clip_mm,
+                              float far_clip_mm, int max_steps, float tol_mm, float gelpad_height_m,
+                              float gelpad_to_camera_min_distance_m, float* hm_mm_dev, float* frame_min_dev, float* indent_mm_dev,
+                              int32_t* frame_rows_dev, int num_frames, int height, int width, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -9,6 +9,7 @@ from .gelsight_sensor_group import GelSightSensorGroup
 from .height_map_source import AffineBodyDepthSource, FemSurfaceDepthSource, FemTractionImage, IndenterHeightMapSource, MeshDepthSource, MeshLibraryDepthSource
 from .lens_model import LensProfile, TactileLensModel
 from .relief_source import ReliefHeightMapSource, ReliefTile
+from .volume_source import SdfVolume, SdfVolumeSource
 
 __all__ = ["AffineBodyDepthSource", "CameraProfile", "ContactField", "ContactGel", "GelMemoryProfile", "GelSightSensor", "GelSightSensorCfg", "GelSightSensorData", "GelSightSensorGroup", "FemSurfaceDepthSource", "FemTractionImage", "IndenterHeightMapSource", "LensProfile", "MeshDepthSource",
-           "MeshLibraryDepthSource", "ReliefHeightMapSource", "ReliefTile", "TactileCameraModel", "TactileContactModel", "TactileGelMemory", "TactileLensModel", "slip_from_fots"]
+           "MeshLibraryDepthSource", "ReliefHeightMapSource", "ReliefTile", "SdfVolume", "SdfVolumeSource", "TactileCameraModel", "TactileContactModel", "TactileGelMemory", "TactileLensModel", "slip_from_fots"]
