@@ -1,7 +1,10 @@
 """What the per-env stages of the optical path share (camera_model, lens_model, contact_field, gel_memory): the profile table with
 its ids, the check of a tensor argument, and the constructor preamble.  A stage keeps its own profile class, its own arguments and
-its one launch; DESIGN.md 4.0.12a.4 says how a new stage uses these pieces."""
+its one launch; DESIGN.md 4.0.12a.4 says how a new stage uses these pieces.  `LibrarySource` is the base of the height-map sources
+that press one entry of a library per env (relief_source, volume_source)."""
 from __future__ import annotations
+
+import math
 
 import numpy as np
 import torch
@@ -92,3 +95,70 @@ def open_stage(owner: str, rows_name: str, ids_name: str, profiles, cls, num_fra
     if device.type != "cuda":
         raise _lib.TacexHipError(f"{owner} runs on the GPU only (device {device}): there is no CPU fallback")
     return _lib.load_library(), ProfileTable(owner, rows_name, ids_name, rows, num_frames, device)
+
+
+def per_env(v, n: int, device) -> torch.Tensor:
+    """A scalar or per-env tensor argument of a `set_pose` as (n,) float64 on `device`."""
+    v = v.to(device=device, dtype=torch.float64) if isinstance(v, torch.Tensor) else torch.tensor(float(v), dtype=torch.float64, device=device)
+    return v.expand(n) if v.dim() == 0 else v
+
+
+class LibrarySource:
+    """A height-map source (`GelSightSensor.set_height_map_source`) that presses one entry of a library per env under a pose the caller
+    writes in place: a payload tensor (all entries back to back), an int32 table (P, 4) whose first column is an entry's first payload
+    element, a float32 table (P, C) and ids (num_envs,) in a `ProfileTable`, and `pose` (num_envs, 16) float32.  A subclass keeps its
+    profile class, its public names for the four tensors (`_names`; the float table and the ids as `table_attr`), its own constructor
+    checks, `set_pose` and `_launch`, the one call into the library."""
+
+    writes_frame_rows = True  # fill(..., rows=) leaves the contact ranges of tacex_indentation_depth behind
+    _owner = None  # the class name in messages
+    _names = None  # attribute names (payload, int table, float table, ids)
+    _unit = None   # what the payload counts ("texel", "voxel")
+
+    def _open(self, profiles, cls, arrays, int_rows, num_envs: int, device, pixmm: float):
+        """The end of the constructor, after the subclass's own checks: `arrays` are the entries' payloads, `int_rows` what follows
+        the first payload element in each row of the int table.  Every ValueError comes before the device is looked at."""
+        payload, table_i, rows_name, ids_name = self._names
+        if not (math.isfinite(float(pixmm)) and float(pixmm) > 0):
+            raise ValueError(f"{self._owner}: pixmm must be > 0, got {pixmm}")
+        if sum(a.size for a in arrays) >= 2 ** 31:
+            raise ValueError(f"{self._owner}: the library holds 2^31 {self._unit}s or more ({self._unit} indices are 32-bit)")
+        self._lib, self._table = open_stage(self._owner, rows_name, ids_name, profiles, cls, num_envs, device)
+        self.device = self._table.device
+        self.num_envs, self.pixmm = int(num_envs), float(pixmm)
+        self._num_profiles = len(profiles)
+        first = np.concatenate([[0], np.cumsum([a.size for a in arrays])[:-1]])
+        setattr(self, table_i, torch.tensor([[int(f), *r] for f, r in zip(first, int_rows)], dtype=torch.int32, device=self.device))
+        setattr(self, payload, torch.from_numpy(np.concatenate([a.reshape(-1) for a in arrays])).to(self.device))
+        self.pose = torch.zeros((self.num_envs, 16), dtype=torch.float32, device=self.device)
+
+    def randomize(self, env_ids=None, generator=None):
+        """Re-draw the library ids of `env_ids` (default: all) uniformly from [0, P) on the device."""
+        return self._table.randomize(env_ids, generator)
+
+    def fill(self, hm: torch.Tensor, frame_min: torch.Tensor, indent: torch.Tensor | None, gelpad_height: float,
+             gelpad_to_camera_min_distance: float, rows: torch.Tensor | None = None):
+        """hm (B, H, W) mm, frame_min (B,), indent (B,) or None, rows (B, 4) int32 or None - all written on the current stream;
+        frame_min, indent and rows are what `tacex_indentation_depth` gives for the map."""
+        B, P, dev = self.num_envs, self._num_profiles, self.device
+        payload, table_i, rows_name, _ = self._names
+
+        def arg(name, t, shape, dtype=torch.float32, must="must be"):
+            return check_tensor(self._owner, name, t, shape, dtype, dev, must=must)
+
+        arg("hm", hm, (B, "H", "W"))
+        arg("frame_min", frame_min, (B,))
+        if indent is not None:
+            arg("indent", indent, (B,))
+        if rows is not None:
+            arg("rows", rows, (B, 4), torch.int32)
+        arg("pose", self.pose, (B, 16), must="must stay")
+        ints = arg(table_i, getattr(self, table_i), (P, 4), torch.int32, must="must stay")
+        data = arg(payload, getattr(self, payload), ("N",), must="must stay")
+        ids, floats = self._table.check()
+        arg(rows_name, floats, (P, self._table.width), must="must stay")
+        self._launch(data, ints, floats, ids, hm, frame_min, indent, rows, float(gelpad_height), float(gelpad_to_camera_min_distance))
+        return hm
+
+    def _launch(self, data, ints, floats, ids, hm, frame_min, indent, rows, gelpad_height, gelpad_to_camera_min_distance):
+        raise NotImplementedError

@@ -66,49 +66,6 @@ __device__ __forceinline__ float gel_pixel(float hm, float& m1, float& m2, const
   return (M > 0.0f && r < hm) ? r : hm;
 }
 
-// The frame as ONE run of float4s, thread t takes t, t + blockDim, ... in batches of NB whose loads are issued back to back - the
-// walk of frame_rows_kernel: load(q) fetches what float4 q needs (q clamped to the frame), elem(data, q, valid) handles it and
-// returns the lane's minimum (+inf when !valid); the row minima go to LDS here.
-template <int NB, class Load, class Elem>
-__device__ __forceinline__ void gel_walk(int H, int w4, bool cols_ok, int* rowmin_i, int lane, Load load, Elem elem) {
-  using T = decltype(load(0));
-  const int n4 = H * w4;
-  if (cols_ok) {  // rows advance by blockDim / w4 per iteration: no division inside the loop
-    const int rstep = blockDim.x / w4, rt = threadIdx.x / w4;
-    const int w0 = threadIdx.x & ~63;
-    const int rfw = __builtin_amdgcn_readfirstlane(w0 / w4), rlw = __builtin_amdgcn_readfirstlane((w0 + 63) / w4);
-    for (int rb0 = 0; rb0 < H; rb0 += NB * rstep) {  // (wave-uniform trip counts: the wave reductions need every lane)
-      T vb[NB];
-#pragma unroll
-      for (int u = 0; u < NB; ++u) vb[u] = load(min((rb0 + u * rstep) * w4 + (int)threadIdx.x, n4 - 1));
-#pragma unroll
-      for (int u = 0; u < NB; ++u) {
-        const int rb = rb0 + u * rstep;
-        if (rb >= H) break;  // (block-uniform)
-        const int r = rb + rt;
-        const float m = elem(vb[u], rb * w4 + (int)threadIdx.x, r < H);
-        if (rb + rfw < H) frame_rows_row_minima(rowmin_i, lane, m, r < H ? r : -1, rb + rfw, min(rb + rlw, H - 1));
-      }
-    }
-  } else {
-    for (int base0 = 0; base0 < n4; base0 += NB * blockDim.x) {
-      T vb[NB];
-#pragma unroll
-      for (int u = 0; u < NB; ++u) vb[u] = load(min(base0 + u * (int)blockDim.x + (int)threadIdx.x, n4 - 1));
-#pragma unroll
-      for (int u = 0; u < NB; ++u) {
-        const int base = base0 + u * blockDim.x;
-        if (base >= n4) break;  // (block-uniform)
-        const int q = base + threadIdx.x;
-        const bool valid = q < n4;
-        const float m = elem(vb[u], q, valid);
-        const int q0 = base + (threadIdx.x & ~63);
-        if (q0 < n4) frame_rows_row_minima(rowmin_i, lane, m, valid ? q / w4 : -1, q0 / w4, min(q0 + 63, n4 - 1) / w4);
-      }
-    }
-  }
-}
-
 template <int K> struct GelQuad { v4f h, m1, m2; };
 
 // W % 4 == 0 and H <= kFrameRowsMaxH: minima per row and column, the outputs of frame_rows_kernel
@@ -120,40 +77,22 @@ __global__ __launch_bounds__(1024) void gel_memory_rows_kernel(GelArgs a) {
   const int b = blockIdx.x, H = a.H, W = a.W, w4 = W >> 2;
   const size_t npix = (size_t)H * W;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int* rowmin_i = reinterpret_cast<int*>(rowmin);
-  int* colmin_i = reinterpret_cast<int*>(colmin);
   const bool cols_ok = frame_rows_cols_ok(W);
   const float z0 = a.z0;
   v4f* __restrict__ hm4 = reinterpret_cast<v4f*>(a.hm + (size_t)b * npix);
-  float cm[4];
-  auto init_minima = [&]() {
-    for (int r = threadIdx.x; r < H; r += blockDim.x) rowmin_i[r] = 0x7f800000;  // +inf
-    if (cols_ok)
-      for (int c = threadIdx.x; c < W; c += blockDim.x) colmin_i[c] = 0x7f800000;
-    cm[0] = cm[1] = cm[2] = cm[3] = INFINITY;
-  };
-  auto minima_of = [&](const v4f& v) -> float {
-    cm[0] = fminf(cm[0], v[0]); cm[1] = fminf(cm[1], v[1]); cm[2] = fminf(cm[2], v[2]); cm[3] = fminf(cm[3], v[3]);
-    return fminf(fminf(v[0], v[1]), fminf(v[2], v[3]));
-  };
-  auto column_minima = [&]() {
-    if (!cols_ok) return;
-    const int cg = (threadIdx.x % w4) * 4;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) lds_min_f32(&colmin_i[cg + k], cm[k]);
-  };
-  init_minima();
+  FrameMinima mn(rowmin, colmin);
+  mn.init(H, W, cols_ok);
   if (threadIdx.x < 2) flag[threadIdx.x] = 0;
   __syncthreads();
   // pass 1: the map alone
   int pressed = 0;
-  gel_walk<4>(H, w4, cols_ok, rowmin_i, lane, [&](int q) { return hm4[q]; },
-              [&](const v4f& v, int q, bool valid) -> float {
-                if (!valid) return INFINITY;
-                pressed |= gel_pressed(v[0], z0) | gel_pressed(v[1], z0) | gel_pressed(v[2], z0) | gel_pressed(v[3], z0);
-                return minima_of(v);
-              });
-  column_minima();
+  frame_rows_walk<4>(H, w4, cols_ok, mn.rowmin_i, lane, [&](int q) { return hm4[q]; },
+                     [&](const v4f& v, int q, bool valid) -> float {
+                       if (!valid) return INFINITY;
+                       pressed |= gel_pressed(v[0], z0) | gel_pressed(v[1], z0) | gel_pressed(v[2], z0) | gel_pressed(v[3], z0);
+                       return mn.of(v);
+                     });
+  if (cols_ok) mn.columns((threadIdx.x % w4) * 4);
   if (pressed) flag[0] = 1;
   __syncthreads();
   const bool dead = flag[0] == 0 && a.live[b] == 0;  // (block-uniform)
@@ -162,47 +101,37 @@ __global__ __launch_bounds__(1024) void gel_memory_rows_kernel(GelArgs a) {
     const GelCoef c = gel_coef(a, b);
     v4f* __restrict__ s1 = reinterpret_cast<v4f*>(a.state + ((size_t)b * K) * npix);
     v4f* __restrict__ s2 = reinterpret_cast<v4f*>(a.state + ((size_t)b * K + (K - 1)) * npix);
-    init_minima();
+    mn.init(H, W, cols_ok);
     __syncthreads();
     int nz = 0;
-    gel_walk<2>(H, w4, cols_ok, rowmin_i, lane,
-                [&](int q) {
-                  GelQuad<K> g;
-                  g.h = hm4[q]; g.m1 = s1[q];
-                  if (K == 2) g.m2 = s2[q];
-                  return g;
-                },
-                [&](GelQuad<K>& g, int q, bool valid) -> float {
-                  if (!valid) return INFINITY;
-                  v4f o;
-#pragma unroll
-                  for (int k = 0; k < 4; ++k) {
-                    float m1 = g.m1[k], m2 = K == 2 ? g.m2[k] : 0.0f;
-                    o[k] = gel_pixel<K>(g.h[k], m1, m2, c, z0, nz);
-                    g.m1[k] = m1;
-                    if (K == 2) g.m2[k] = m2;
-                  }
-                  hm4[q] = o; s1[q] = g.m1;
-                  if (K == 2) s2[q] = g.m2;
-                  return minima_of(o);
-                });
-    column_minima();
+    frame_rows_walk<2>(H, w4, cols_ok, mn.rowmin_i, lane,
+                       [&](int q) {
+                         GelQuad<K> g;
+                         g.h = hm4[q]; g.m1 = s1[q];
+                         if (K == 2) g.m2 = s2[q];
+                         return g;
+                       },
+                       [&](GelQuad<K>& g, int q, bool valid) -> float {
+                         if (!valid) return INFINITY;
+                         v4f o;
+       #pragma unroll
+                         for (int k = 0; k < 4; ++k) {
+                           float m1 = g.m1[k], m2 = K == 2 ? g.m2[k] : 0.0f;
+                           o[k] = gel_pixel<K>(g.h[k], m1, m2, c, z0, nz);
+                           g.m1[k] = m1;
+                           if (K == 2) g.m2[k] = m2;
+                         }
+                         hm4[q] = o; s1[q] = g.m1;
+                         if (K == 2) s2[q] = g.m2;
+                         return mn.of(o);
+                       });
+    if (cols_ok) mn.columns((threadIdx.x % w4) * 4);
     if (nz) flag[1] = 1;
     __syncthreads();
     if (threadIdx.x == 0) a.live[b] = flag[1];
   }
   if (wave == 0)
     frame_rows_finish(rowmin, colmin, H, W, cols_ok, lane, b, a.gelpad_h, a.gelpad_dmin, nullptr, a.fmin, a.indent, a.rows);
-}
-
-// minimum over the block; valid in every lane of wave 0
-__device__ __forceinline__ float gel_block_min(float m, float* red) {
-  m = wave_min(m);
-  __syncthreads();  // (red may still be read from the previous reduction)
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
-  __syncthreads();
-  float v = (threadIdx.x & 63) < (blockDim.x >> 6) ? red[threadIdx.x & 63] : INFINITY;
-  return wave_min(v);
 }
 
 // Any other geometry (W % 4 != 0: scalar; H > kFrameRowsMaxH: VEC): the frame minimum alone, every row and column reported as
@@ -227,7 +156,7 @@ __global__ __launch_bounds__(1024) void gel_memory_flat_kernel(GelArgs a) {
 #pragma unroll
     for (int k = 0; k < N; ++k) { const float h = lane_of(v, k); pressed |= gel_pressed(h, z0); m = fminf(m, h); }
   }
-  m = gel_block_min(m, red);  // (its barriers also order flag's initialisation)
+  m = frame_block_min(m, red);  // (its barriers also order flag's initialisation)
   if (pressed) flag[0] = 1;
   __syncthreads();
   const bool dead = flag[0] == 0 && a.live[b] == 0;  // (block-uniform)
@@ -251,7 +180,7 @@ __global__ __launch_bounds__(1024) void gel_memory_flat_kernel(GelArgs a) {
       hm[i] = o; s1[i] = p1;
       if (K == 2) s2[i] = p2;
     }
-    m = gel_block_min(m, red);
+    m = frame_block_min(m, red);
     if (nz) flag[1] = 1;
     __syncthreads();
     if (threadIdx.x == 0) a.live[b] = flag[1];

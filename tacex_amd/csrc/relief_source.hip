@@ -122,12 +122,9 @@ __global__ __launch_bounds__(1024) void relief_height_map_kernel(ReliefArgs a) {
   __shared__ float colmin[kFrameRowsMaxH];
   const int b = blockIdx.x, H = a.H, W = a.W, w4 = W >> 2;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int* rowmin_i = reinterpret_cast<int*>(rowmin);
-  int* colmin_i = reinterpret_cast<int*>(colmin);
   const bool cols_ok = frame_rows_cols_ok(W);
-  for (int r = threadIdx.x; r < H; r += blockDim.x) rowmin_i[r] = 0x7f800000;  // +inf
-  if (cols_ok)
-    for (int c = threadIdx.x; c < W; c += blockDim.x) colmin_i[c] = 0x7f800000;
+  FrameMinima mn(rowmin, colmin);
+  mn.init(H, W, cols_ok);
 
   // the frame's tile and pose (blockIdx alone: scalar loads)
   ReliefFrame f;
@@ -155,7 +152,6 @@ __global__ __launch_bounds__(1024) void relief_height_map_kernel(ReliefArgs a) {
     f.gain = p[12]; f.du = p[13]; f.dv = p[14];
   }
   v4f* __restrict__ out4 = reinterpret_cast<v4f*>(a.hm + (size_t)b * ((size_t)H * W));
-  float cm[4] = {INFINITY, INFINITY, INFINITY, INFINITY};
   // one float4 of the frame at columns x .. x + 3 of row y: computed, stored, the lane's minimum returned
   auto group = [&](int q, int x, int y) -> float {
     v4f o;
@@ -167,8 +163,7 @@ __global__ __launch_bounds__(1024) void relief_height_map_kernel(ReliefArgs a) {
       for (int k = 0; k < 4; ++k) o[k] = relief_pixel<SAMPLES>(f, (float)(x + k), yf);
     }
     out4[q] = o;
-    cm[0] = fminf(cm[0], o[0]); cm[1] = fminf(cm[1], o[1]); cm[2] = fminf(cm[2], o[2]); cm[3] = fminf(cm[3], o[3]);
-    return fminf(fminf(o[0], o[1]), fminf(o[2], o[3]));
+    return mn.of(o);
   };
   __syncthreads();
   if (cols_ok) {
@@ -179,10 +174,9 @@ __global__ __launch_bounds__(1024) void relief_height_map_kernel(ReliefArgs a) {
     for (int rb = 0; rb < H; rb += rstep) {  // (block-uniform trip count: the wave reductions need every lane)
       const int r = rb + rt;
       const float m = r < H ? group(rb * w4 + (int)threadIdx.x, x, r) : INFINITY;
-      if (rb + rfw < H) frame_rows_row_minima(rowmin_i, lane, m, r < H ? r : -1, rb + rfw, min(rb + rlw, H - 1));
+      if (rb + rfw < H) frame_rows_row_minima(mn.rowmin_i, lane, m, r < H ? r : -1, rb + rfw, min(rb + rlw, H - 1));
     }
-#pragma unroll
-    for (int k = 0; k < 4; ++k) lds_min_f32(&colmin_i[x + k], cm[k]);
+    mn.columns(x);
   } else {
     // any other row length: float4 q = t, t + blockDim, ...; (x4, y) advance by (sx, sy) with one carry
     const int n4 = H * w4;
@@ -196,7 +190,7 @@ __global__ __launch_bounds__(1024) void relief_height_map_kernel(ReliefArgs a) {
       const float m = valid ? group(q, x4 << 2, y) : INFINITY;
       if (base + w0 < n4) {
         const int ql = min(base + w0 + 63, n4 - 1) - (base + w0);  // the wave's last float4, counted from its first
-        frame_rows_row_minima(rowmin_i, lane, m, valid ? y : -1, yf0, yf0 + (xf0 + ql) / w4);
+        frame_rows_row_minima(mn.rowmin_i, lane, m, valid ? y : -1, yf0, yf0 + (xf0 + ql) / w4);
       }
       x4 += sx; y += sy;
       if (x4 >= w4) { x4 -= w4; ++y; }
@@ -223,13 +217,9 @@ extern "C" int tacex_height_map_from_relief(const float* texels_dev, const int32
       null_arg(fn, "pose_dev", pose_dev) || null_arg(fn, "hm_mm_dev", hm_mm_dev) || null_arg(fn, "frame_min_dev", frame_min_dev)) return 2;
   if (not_positive(fn, "num_tiles", num_tiles) || not_positive(fn, "num_frames", num_frames) || not_positive(fn, "height", height) ||
       not_positive(fn, "width", width)) return 2;
-  if (width % 4 != 0) { set_error("%s: width = %d (must be a multiple of 4)", fn, width); return 2; }
-  if (height > kFrameRowsMaxH || width > kFrameRowsMaxH) {
-    set_error("%s: height x width = %d x %d (at most %d each)", fn, height, width, kFrameRowsMaxH);
-    return 2;
-  }
+  if (not_frame_rows_geometry(fn, height, width)) return 2;
   if (samples != 1 && samples != 4) { set_error("%s: samples = %d (must be 1 or 4)", fn, samples); return 2; }
-  if ((uintptr_t)hm_mm_dev % 16 != 0) { set_error("%s: hm_mm_dev must be 16-byte aligned", fn); return 2; }
+  if (not_aligned16(fn, "hm_mm_dev", hm_mm_dev)) return 2;
   ReliefArgs a{};
   a.texels = texels_dev; a.tiles_i = tiles_i_dev; a.tiles_f = tiles_f_dev; a.ids = relief_ids_dev; a.pose = pose_dev;
   a.hm = hm_mm_dev; a.fmin = frame_min_dev; a.indent = indent_mm_dev; a.rows = frame_rows_dev;

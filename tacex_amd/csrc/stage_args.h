@@ -1,10 +1,11 @@
-// What the per-env stages of the optical path share on the C side (camera_model.hip, lens_model.hip, contact_field.hip,
-// gel_memory.hip): the refusals every entry point opens with, the launch geometry of "blocks stay inside one frame", and the
+// What the per-env stages of the optical path and the library height-map sources share on the C side (camera_model.hip,
+// lens_model.hip, contact_field.hip, gel_memory.hip, relief_source.hip, volume_source.hip): the refusals every entry point opens with, the launch geometry of "blocks stay inside one frame", and the
 // lookup of a frame's row in a profile table.  No arithmetic lives here: the four units are pinned bit for bit on their own.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "frame_rows.h"
 #include "tacex_internal.h"
 
 namespace tacex {
@@ -19,6 +20,20 @@ inline bool null_arg(const char* fn, const char* name, const void* p) {
 inline bool not_positive(const char* fn, const char* name, int v) {
   if (v > 0) return false;
   set_error("%s: %s = %d", fn, name, v);
+  return true;
+}
+
+// The height-map sources whose frame outputs come from the row kernel's statements (relief_source.hip, volume_source.hip): a frame
+// of whole float4 groups whose row and column minima fit LDS, and a map that float4 stores may write.
+inline bool not_frame_rows_geometry(const char* fn, int height, int width) {
+  if (width % 4 != 0) { set_error("%s: width = %d (must be a multiple of 4)", fn, width); return true; }
+  if (height <= kFrameRowsMaxH && width <= kFrameRowsMaxH) return false;
+  set_error("%s: height x width = %d x %d (at most %d each)", fn, height, width, kFrameRowsMaxH);
+  return true;
+}
+inline bool not_aligned16(const char* fn, const char* name, const void* p) {
+  if ((uintptr_t)p % 16 == 0) return false;
+  set_error("%s: %s must be 16-byte aligned", fn, name);
   return true;
 }
 

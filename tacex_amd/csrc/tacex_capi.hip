@@ -525,13 +525,9 @@ struct StageTimer {
 
 // the d.B frames of a depth -> height map pass (GS:581-593 + TS:115-131 + contact row / column ranges)
 static int run_depth_pass(const tacex_taxim_ctx::DepthPass& d, int H, int W, hipStream_t st) {
-  if (d.rows && frame_rows_supported(H, W)) {
-    HIP_TRY(run_frame_rows(d.depth, true, d.hm, d.fmin, d.indent, d.cam_u8, nullptr, d.rows, d.B, H, W, d.near_mm, d.far_m, d.far_mm, d.gelpad_h,
-                           d.gelpad_dmin, st), "frame_rows_kernel<depth>");
-    return 0;
-  }
-  if (d.rows) HIP_TRY(run_fill_rows(d.rows, d.B, H, W, st), "fill_rows_kernel");
-  HIP_TRY(run_frame_min(d.depth, true, d.hm, d.fmin, d.indent, d.cam_u8, d.B, H * W, d.near_mm, d.far_m, d.far_mm, d.gelpad_h, d.gelpad_dmin, st), "frame_min_kernel<depth>");
+  const char* what = "";
+  HIP_TRY(run_frame_outputs(d.depth, true, d.hm, d.fmin, d.indent, d.cam_u8, nullptr, d.rows, d.B, H, W, d.near_mm, d.far_m, d.far_mm, d.gelpad_h,
+                            d.gelpad_dmin, st, &what), what);
   return 0;
 }
 
@@ -593,16 +589,9 @@ int tacex_indentation_depth(const float* hm_mm, float gelpad_h, float gelpad_dmi
                             float* indent_mm, int32_t* frame_rows, int B, int H, int W, void* stream) {
   if (!hm_mm || !frame_min || !indent_mm) { set_error("tacex_indentation_depth: null buffer"); return 2; }
   if (B <= 0) return 0;
-  if (frame_rows && frame_rows_supported(H, W)) {
-    HIP_TRY(run_frame_rows(hm_mm, false, nullptr, frame_min, indent_mm, nullptr, nullptr, frame_rows, B, H, W, 0.f, 0.f, 0.f, gelpad_h,
-                           gelpad_dmin, (hipStream_t)stream),
-            "frame_rows_kernel");
-    return 0;
-  }
-  if (frame_rows) HIP_TRY(run_fill_rows(frame_rows, B, H, W, (hipStream_t)stream), "fill_rows_kernel");
-  HIP_TRY(run_frame_min(hm_mm, false, nullptr, frame_min, indent_mm, nullptr, B, H * W, 0.f, 0.f, 0.f, gelpad_h,
-                        gelpad_dmin, (hipStream_t)stream),
-          "frame_min_kernel");
+  const char* what = "";
+  HIP_TRY(run_frame_outputs(hm_mm, false, nullptr, frame_min, indent_mm, nullptr, nullptr, frame_rows, B, H, W, 0.f, 0.f, 0.f, gelpad_h,
+                            gelpad_dmin, (hipStream_t)stream, &what), what);
   return 0;
 }
 
@@ -1072,13 +1061,10 @@ static int pipeline_impl(tacex_taxim_ctx* c, Pass p) {
     if (can_rows && (p.flags & TACEX_FLAG_HAVE_FRAME_ROWS) && c->frame_rows && p.B <= c->frame_rows_cap) p.rows = c->frame_rows;
   } else {  // one reduction pass over the whole shard
     StageTimer t(c, p.stream, 0);
-    if (can_rows) {
-      int* wr = reinterpret_cast<int*>(static_cast<char*>(p.ws) + PassLayout(c->H, c->W, p.B).rows);
-      HIP_TRY(run_frame_rows(p.hm, false, nullptr, p.frame_min, nullptr, nullptr, p.press, wr, p.B, c->H, c->W, 0.f, 0.f, 0.f, 0.f, 0.f, p.stream), "frame_rows_kernel");
-      p.rows = wr;
-    } else {
-      HIP_TRY(run_frame_min(p.hm, false, nullptr, p.frame_min, nullptr, nullptr, p.B, c->H * c->W, 0.f, 0.f, 0.f, 0.f, 0.f, p.stream), "frame_min_kernel");
-    }
+    int* wr = can_rows ? reinterpret_cast<int*>(static_cast<char*>(p.ws) + PassLayout(c->H, c->W, p.B).rows) : nullptr;
+    const char* what = "";
+    HIP_TRY(run_frame_outputs(p.hm, false, nullptr, p.frame_min, nullptr, nullptr, p.press, wr, p.B, c->H, c->W, 0.f, 0.f, 0.f, 0.f, 0.f, p.stream, &what), what);
+    p.rows = wr;
     p.flags |= TACEX_FLAG_HAVE_FRAME_MIN;
   }
   for (int b0 = 0; b0 < p.B; b0 += cf)

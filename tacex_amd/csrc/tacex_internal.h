@@ -43,9 +43,6 @@ struct ShadeParams {
   float* flat_rgb_dev = nullptr; // (H, W, 3) RGB of the undeformed gel: clip(poly[flat bin pair](x, y) + background), run_stream_flat_image
 };
 
-hipError_t run_frame_min(const float* in, bool from_depth, float* hm_out, float* fmin, float* indent,
-                         uint8_t* cam_u8, int B, int npix, float near_mm, float far_m, float far_mm, float gelpad_h,
-                         float gelpad_dmin, hipStream_t st);
 hipError_t run_indenter_height_map(const float* desc, float* hm, float* fmin, float* indent, int B, int H, int W, float pixmm,
                                    float gel_top_mm, float far_clip_mm, float gelpad_h, float gelpad_dmin, hipStream_t st);
 hipError_t run_press_depth(const float* fmin, const float* press, float* sa, float* sb, float* pd, int B,
@@ -71,11 +68,13 @@ bool blur_pipe_supported(const LevelDesc* lv, int n, int H, int W);
 hipError_t blur_pipe_resident(const LevelDesc* lv, int n, int H, int W, bool lean, bool wlds, bool* ok);
 hipError_t run_blur_pipe(const LevelDesc* lv, int n, const PipeLevelCall* calls, const float* gel, int H, int W, float contact_scale, bool lean,
                          bool wlds, hipStream_t st);
+// Frame minimum, press depth (indent: computed, else press_in) and contact ranges (rows_out, nullable) of B maps, or of B camera
+// depth images on their way to maps (from_depth: hm_out, cam_u8, the clipping values): frame_rows_kernel where ranges are wanted
+// and frame_rows_supported, else fill_rows_kernel (ranges wanted) + frame_min_kernel.  *what: the launch a failure belongs to.
 bool frame_rows_supported(int H, int W);
-hipError_t run_fill_rows(int* rows, int B, int H, int W, hipStream_t st);
-hipError_t run_frame_rows(const float* in, bool from_depth, float* hm_out, float* fmin, float* indent, uint8_t* cam_u8,
-                          const float* press_in, int* rows_out, int B, int H, int W, float near_mm, float far_m, float far_mm,
-                          float gelpad_h, float gelpad_dmin, hipStream_t st);
+hipError_t run_frame_outputs(const float* in, bool from_depth, float* hm_out, float* fmin, float* indent, uint8_t* cam_u8,
+                             const float* press_in, int* rows_out, int B, int H, int W, float near_mm, float far_m, float far_mm,
+                             float gelpad_h, float gelpad_dmin, hipStream_t st, const char** what);
 hipError_t run_shade(const ShadeParams& sp, const float* z, float* rgb, uint8_t* idx_out, int B,
                      hipStream_t st);
 hipError_t run_resize_aa(const float* src, int sh, int sw, float* dst, int dh, int dw, int B, int C, float* tmp,

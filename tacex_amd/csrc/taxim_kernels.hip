@@ -75,21 +75,10 @@ __global__ __launch_bounds__(1024) void frame_min_kernel(
     m = fminf(m, d);
   }
   __shared__ float red[16];
-  m = wave_min(m);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
-  __syncthreads();
-  if (threadIdx.x < 64) {
-    float v = threadIdx.x < (blockDim.x >> 6) ? red[threadIdx.x] : INFINITY;
-    v = wave_min(v);
-    if (threadIdx.x == 0) {
-      fmin_out[b] = v;
-      if (indent_out) {
-        // TS:116-129
-        float d = v / 1000.0f - gelpad_dmin;
-        d = d < 0.0f ? 0.0f : d;
-        indent_out[b] = d <= gelpad_h ? (gelpad_h - d) * 1000.0f : 0.0f;
-      }
-    }
+  m = frame_block_min(m, red);
+  if (threadIdx.x == 0) {
+    fmin_out[b] = m;
+    if (indent_out) indent_out[b] = indentation_from_min(m, gelpad_h, gelpad_dmin);
   }
 }
 
@@ -105,7 +94,7 @@ __global__ __launch_bounds__(1024) void frame_min_kernel(
 // meets the same four columns: their minima stay in registers and reach LDS once.
 // press: indentation depth computed here (indent_out != nullptr, TS:116-129) or given per frame (press_in).
 // ------------------------------------------------------------------------------------------------
-// (row / column minima, press depth and ranges: frame_rows.h, shared with the gel memory kernel)
+// (the walk, row / column minima, press depth and ranges: frame_rows.h, shared with the gel memory and relief kernels)
 template <bool FROM_DEPTH>
 __global__ __launch_bounds__(1024) void frame_rows_kernel(
     const float* __restrict__ in, float* __restrict__ hm_out, float* __restrict__ fmin_out,
@@ -118,19 +107,12 @@ __global__ __launch_bounds__(1024) void frame_rows_kernel(
   const size_t fo = (size_t)b * H * W;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int w4 = W >> 2;
-  // The frame is walked as ONE run of float4s (thread t takes t, t + 1024, ...): every lane of every load is busy (a wave per
-  // row left 48 of 128 lane slots idle at W = 320) and the iterations are independent, so several loads are in flight per
-  // thread.  Row minima through LDS integer atomics on the float pattern (heights are >= 0 or +inf: the patterns order like
-  // the values; a minimum does not depend on the order of its operands, so the result is the same bits as before).
-  int* rowmin_i = reinterpret_cast<int*>(rowmin);
-  int* colmin_i = reinterpret_cast<int*>(colmin);
-  for (int r = threadIdx.x; r < H; r += blockDim.x) rowmin_i[r] = 0x7f800000;  // +inf
+  // Row and column minima through LDS integer atomics on the float pattern (heights are >= 0 or +inf: the patterns order like the
+  // values; a minimum does not depend on the order of its operands, so the result is the same bits in any order).
   const bool cols_ok = frame_rows_cols_ok(W);  // (block-uniform) a thread's float4s all lie in ONE column group
-  if (cols_ok)
-    for (int c = threadIdx.x; c < W; c += blockDim.x) colmin_i[c] = 0x7f800000;
-  float cm[4] = {INFINITY, INFINITY, INFINITY, INFINITY};
+  FrameMinima mn(rowmin, colmin);
+  mn.init(H, W, cols_ok);
   __syncthreads();
-  const int n4 = H * w4;
   const v4f* __restrict__ in4 = reinterpret_cast<const v4f*>(in + fo);
   // one float4 of the frame: conversion (GS:585-590), stores, the lane's minimum and its four column minima
   auto element = [&](v4f v, int q, bool valid) -> float {
@@ -155,61 +137,16 @@ __global__ __launch_bounds__(1024) void frame_rows_kernel(
           reinterpret_cast<uchar4*>(cam_u8 + fo)[q] = c;
         }
       }
-      m = fminf(fminf(v[0], v[1]), fminf(v[2], v[3]));
-      cm[0] = fminf(cm[0], v[0]); cm[1] = fminf(cm[1], v[1]); cm[2] = fminf(cm[2], v[2]); cm[3] = fminf(cm[3], v[3]);
+      m = mn.of(v);
     }
     return m;
   };
-  // a wave's 64 consecutive float4s lie in at most two rows when a row has >= 64 of them (a few otherwise): reduce inside the wave
-  // per row (DPP scan, the minimum lands in lane 63), one LDS atomic per row and wave
-  auto row_minima = [&](float m, int r, int r_first, int r_last) { frame_rows_row_minima(rowmin_i, lane, m, r, r_first, r_last); };
-  // Batches of NB float4s per thread, their loads issued back to back (clamped index instead of a predicate: one basic block).
+  // the walk of the frame in batches of NB float4s per thread (frame_rows.h)
 #ifndef TACEX_FRAME_ROWS_NB
 #define TACEX_FRAME_ROWS_NB 4
 #endif
-  constexpr int NB = TACEX_FRAME_ROWS_NB;
-  if (cols_ok) {
-    // The block size is a multiple of the row's float4 count: float4 q = base + t of a thread lies in row base / w4 + t / w4 and the
-    // rows advance by blockDim / w4 per iteration - no division inside the loop (three of them, ~60 of its ~200 instructions
-    // before; with the ds_bpermute reductions the pass was VALU-bound at 4.6 TB/s).
-    const int rstep = blockDim.x / w4, rt = threadIdx.x / w4;
-    const int w0 = threadIdx.x & ~63;
-    const int rfw = __builtin_amdgcn_readfirstlane(w0 / w4), rlw = __builtin_amdgcn_readfirstlane((w0 + 63) / w4);
-    for (int rb0 = 0; rb0 < H; rb0 += NB * rstep) {  // (wave-uniform trip counts: the wave reductions need every lane)
-      v4f vb[NB];
-#pragma unroll
-      for (int u = 0; u < NB; ++u) vb[u] = in4[min((rb0 + u * rstep) * w4 + (int)threadIdx.x, n4 - 1)];
-#pragma unroll
-      for (int u = 0; u < NB; ++u) {
-        const int rb = rb0 + u * rstep;
-        if (rb >= H) break;  // (block-uniform)
-        const int r = rb + rt;
-        const float m = element(vb[u], rb * w4 + threadIdx.x, r < H);
-        if (rb + rfw < H) row_minima(m, r < H ? r : -1, rb + rfw, min(rb + rlw, H - 1));
-      }
-    }
-  } else {
-    for (int base0 = 0; base0 < n4; base0 += NB * blockDim.x) {
-      v4f vb[NB];
-#pragma unroll
-      for (int u = 0; u < NB; ++u) vb[u] = in4[min(base0 + u * (int)blockDim.x + (int)threadIdx.x, n4 - 1)];
-#pragma unroll
-      for (int u = 0; u < NB; ++u) {
-        const int base = base0 + u * blockDim.x;
-        if (base >= n4) break;  // (block-uniform)
-        const int q = base + threadIdx.x;
-        const bool valid = q < n4;
-        const float m = element(vb[u], q, valid);
-        const int q0 = base + (threadIdx.x & ~63);
-        if (q0 < n4) row_minima(m, valid ? q / w4 : -1, q0 / w4, min(q0 + 63, n4 - 1) / w4);
-      }
-    }
-  }
-  if (cols_ok) {  // column minima: the same integer atomics on the float pattern as the row minima
-    const int cg = (threadIdx.x % w4) * 4;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) lds_min_f32(&colmin_i[cg + k], cm[k]);
-  }
+  frame_rows_walk<TACEX_FRAME_ROWS_NB>(H, w4, cols_ok, mn.rowmin_i, lane, [&](int q) { return in4[q]; }, element);
+  if (cols_ok) mn.columns((threadIdx.x % w4) * 4);
   __syncthreads();
   if (wave == 0)
     frame_rows_finish(rowmin, colmin, H, W, cols_ok, lane, b, gelpad_h, gelpad_dmin, press_in, fmin_out, indent_out, rows_out);
@@ -277,20 +214,10 @@ __global__ __launch_bounds__(1024) void indenter_height_map_kernel(const Indente
     if (x >= W) { x -= W; ++y; }
   }
   __shared__ float red[16];
-  m = wave_min(m);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
-  __syncthreads();
-  if (threadIdx.x < 64) {
-    float v = threadIdx.x < (blockDim.x >> 6) ? red[threadIdx.x] : INFINITY;
-    v = wave_min(v);
-    if (threadIdx.x == 0) {
-      fmin_out[b] = v;
-      if (indent_out) {  // TS:116-129
-        float dd = v / 1000.0f - gelpad_dmin;
-        dd = dd < 0.0f ? 0.0f : dd;
-        indent_out[b] = dd <= gelpad_h ? (gelpad_h - dd) * 1000.0f : 0.0f;
-      }
-    }
+  m = frame_block_min(m, red);
+  if (threadIdx.x == 0) {
+    fmin_out[b] = m;
+    if (indent_out) indent_out[b] = indentation_from_min(m, gelpad_h, gelpad_dmin);
   }
 }
 
@@ -926,39 +853,43 @@ static hipError_t dispatch_band(int k, bool first, const BlurArgs& a, hipStream_
   }
 }
 
-// min (+ conversion / indentation) AND the contact row range of every frame; false when the geometry is not supported
-// (the caller then runs run_frame_min and treats every row as contact)
+// true when the geometry has a row kernel (frame_rows_kernel: the minimum AND the contact ranges of every frame)
 bool frame_rows_supported(int H, int W) { return (W % 4) == 0 && H <= kFrameRowsMaxH; }
 __global__ void fill_rows_kernel(int* rows, int B, int H, int W) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b < B) { rows[4 * b] = 0; rows[4 * b + 1] = H - 1; rows[4 * b + 2] = 0; rows[4 * b + 3] = W - 1; }
 }
-hipError_t run_fill_rows(int* rows, int B, int H, int W, hipStream_t st) {  // "every row / column may hold contact" (geometry without a row kernel)
-  hipLaunchKernelGGL(fill_rows_kernel, dim3((B + 255) / 256), dim3(256), 0, st, rows, B, H, W);
-  return hipGetLastError();
-}
-hipError_t run_frame_rows(const float* in, bool from_depth, float* hm_out, float* fmin, float* indent, uint8_t* cam_u8,
-                          const float* press_in, int* rows_out, int B, int H, int W, float near_mm, float far_m, float far_mm,
-                          float gelpad_h, float gelpad_dmin, hipStream_t st) {
-  const int nt = frame_rows_block_threads(W);
-  if (from_depth)
-    hipLaunchKernelGGL(frame_rows_kernel<true>, dim3(B), dim3(nt), 0, st, in, hm_out, fmin, indent, cam_u8, press_in, rows_out,
-                       H, W, near_mm, far_m, far_mm, gelpad_h, gelpad_dmin);
-  else
-    hipLaunchKernelGGL(frame_rows_kernel<false>, dim3(B), dim3(nt), 0, st, in, hm_out, fmin, indent, cam_u8, press_in, rows_out,
-                       H, W, near_mm, far_m, far_mm, gelpad_h, gelpad_dmin);
-  return hipGetLastError();
-}
-
-hipError_t run_frame_min(const float* in, bool from_depth, float* hm_out, float* fmin, float* indent,
-                         uint8_t* cam_u8, int B, int npix, float near_mm, float far_m, float far_mm, float gelpad_h,
-                         float gelpad_dmin, hipStream_t st) {
+// The frame outputs of B maps (from_depth: of B camera depth images, converted on the way): minimum, press depth and, where
+// rows_out is given, the contact ranges.  The ONE route choice: the row kernel where ranges are wanted and the geometry has one, else
+// "every row / column may hold contact" and the minimum kernel.  *what names the launch that was issued last - the one a failure
+// belongs to (the labels of the entry points' error texts).
+hipError_t run_frame_outputs(const float* in, bool from_depth, float* hm_out, float* fmin, float* indent, uint8_t* cam_u8,
+                             const float* press_in, int* rows_out, int B, int H, int W, float near_mm, float far_m, float far_mm,
+                             float gelpad_h, float gelpad_dmin, hipStream_t st, const char** what) {
+  if (rows_out && frame_rows_supported(H, W)) {
+    const int nt = frame_rows_block_threads(W);
+    *what = from_depth ? "frame_rows_kernel<depth>" : "frame_rows_kernel";
+    if (from_depth)
+      hipLaunchKernelGGL(frame_rows_kernel<true>, dim3(B), dim3(nt), 0, st, in, hm_out, fmin, indent, cam_u8, press_in, rows_out,
+                         H, W, near_mm, far_m, far_mm, gelpad_h, gelpad_dmin);
+    else
+      hipLaunchKernelGGL(frame_rows_kernel<false>, dim3(B), dim3(nt), 0, st, in, hm_out, fmin, indent, cam_u8, press_in, rows_out,
+                         H, W, near_mm, far_m, far_mm, gelpad_h, gelpad_dmin);
+    return hipGetLastError();
+  }
+  if (rows_out) {
+    *what = "fill_rows_kernel";
+    hipLaunchKernelGGL(fill_rows_kernel, dim3((B + 255) / 256), dim3(256), 0, st, rows_out, B, H, W);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  *what = from_depth ? "frame_min_kernel<depth>" : "frame_min_kernel";
   if (from_depth)
     hipLaunchKernelGGL(frame_min_kernel<true>, dim3(B), dim3(1024), 0, st, in, hm_out, fmin, indent, cam_u8,
-                       npix, near_mm, far_m, far_mm, gelpad_h, gelpad_dmin);
+                       H * W, near_mm, far_m, far_mm, gelpad_h, gelpad_dmin);
   else
     hipLaunchKernelGGL(frame_min_kernel<false>, dim3(B), dim3(1024), 0, st, in, hm_out, fmin, indent, cam_u8,
-                       npix, near_mm, far_m, far_mm, gelpad_h, gelpad_dmin);
+                       H * W, near_mm, far_m, far_mm, gelpad_h, gelpad_dmin);
   return hipGetLastError();
 }
 

@@ -154,8 +154,7 @@ extern "C" int tacex_height_map_from_sdf(const float* voxels_dev, int num_voxels
       null_arg(fn, "frame_min_dev", frame_min_dev)) return 2;
   if (not_positive(fn, "num_voxels", num_voxels) || not_positive(fn, "num_volumes", num_volumes) ||
       not_positive(fn, "num_frames", num_frames) || not_positive(fn, "height", height) || not_positive(fn, "width", width)) return 2;
-  if (width % 4 != 0) { set_error("%s: width = %d (must be a multiple of 4)", fn, width); return 2; }
-  if (height > 2048 || width > 2048) { set_error("%s: height x width = %d x %d (at most 2048 each)", fn, height, width); return 2; }
+  if (not_frame_rows_geometry(fn, height, width)) return 2;
   if (!(pixmm > 0.0f)) { set_error("%s: pixmm = %g (must be > 0)", fn, (double)pixmm); return 2; }
   if (max_steps < 1 || max_steps > 128) { set_error("%s: max_steps = %d (must be 1..128)", fn, max_steps); return 2; }
   if (!(tol_mm > 0.0f)) { set_error("%s: tol_mm = %g (must be > 0)", fn, (double)tol_mm); return 2; }
@@ -163,7 +162,7 @@ extern "C" int tacex_height_map_from_sdf(const float* voxels_dev, int num_voxels
     set_error("%s: near_clip_mm = %g, far_clip_mm = %g (near must be below far)", fn, (double)near_clip_mm, (double)far_clip_mm);
     return 2;
   }
-  if ((uintptr_t)hm_mm_dev % 16 != 0) { set_error("%s: hm_mm_dev must be 16-byte aligned", fn); return 2; }
+  if (not_aligned16(fn, "hm_mm_dev", hm_mm_dev)) return 2;
   SdfArgs a{};
   a.tiles_x = (width + kSdfTileW - 1) / kSdfTileW;
   a.tiles = a.tiles_x * ((height + kSdfTileH - 1) / kSdfTileH);
@@ -175,13 +174,9 @@ extern "C" int tacex_height_map_from_sdf(const float* voxels_dev, int num_voxels
   hipLaunchKernelGGL(sdf_height_map_kernel, dim3((unsigned int)(a.tiles * num_frames)), dim3(256), 0, st, a);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail_hip(e, "sdf_height_map_kernel");
-  // frame minimum, indentation depth, contact ranges: the statements of tacex_indentation_depth (W % 4 == 0 and H <= 2048 here)
-  if (frame_rows_dev) {
-    e = run_frame_rows(hm_mm_dev, false, nullptr, frame_min_dev, indent_mm_dev, nullptr, nullptr, frame_rows_dev, num_frames, height,
-                       width, 0.f, 0.f, 0.f, gelpad_height_m, gelpad_to_camera_min_distance_m, st);
-    return e == hipSuccess ? 0 : fail_hip(e, "frame_rows_kernel");
-  }
-  e = run_frame_min(hm_mm_dev, false, nullptr, frame_min_dev, indent_mm_dev, nullptr, num_frames, height * width, 0.f, 0.f, 0.f,
-                    gelpad_height_m, gelpad_to_camera_min_distance_m, st);
-  return e == hipSuccess ? 0 : fail_hip(e, "frame_min_kernel");
+  // frame minimum, indentation depth, contact ranges: the statements of tacex_indentation_depth (the row kernel's geometry here)
+  const char* what = "";
+  e = run_frame_outputs(hm_mm_dev, false, nullptr, frame_min_dev, indent_mm_dev, nullptr, nullptr, frame_rows_dev, num_frames, height, width,
+                        0.f, 0.f, 0.f, gelpad_height_m, gelpad_to_camera_min_distance_m, st, &what);
+  return e == hipSuccess ? 0 : fail_hip(e, what);
 }

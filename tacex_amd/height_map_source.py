@@ -49,6 +49,44 @@ class IndenterHeightMapSource:
         _lib.check(rc, "tacex_height_map_from_indenters")
 
 
+def _bounding_sphere(verts: torch.Tensor) -> list:
+    """[cx, cy, cz, r] of a (V, 3) mesh: the centre of its bounding box and the farthest vertex from it, a hair wider."""
+    v = verts.double().cpu()
+    c = 0.5 * (v.min(0).values + v.max(0).values)
+    return [float(c[0]), float(c[1]), float(c[2]), float((v - c).norm(dim=1).max()) * 1.0001]
+
+
+def _init_pinhole(self, num_envs: int, dev, resolution, intrinsics, clipping_range):
+    """The pinhole camera of the rigid-mesh sources and the tensors the caller updates in place: image size, intrinsics, clipping
+    range, `pos` (num_envs, 3), `quat` (num_envs, 4, wxyz), `depth` (num_envs, H, W)."""
+    self.W, self.H = int(resolution[0]), int(resolution[1])
+    self.fx, self.fy, self.cx, self.cy = (float(v) for v in intrinsics)
+    self.near, self.far = float(clipping_range[0]), float(clipping_range[1])
+    self.pos = torch.zeros((num_envs, 3), dtype=torch.float32, device=dev)
+    self.pos[:, 2] = 1.0  # out of range until the caller places the object
+    self.quat = torch.zeros((num_envs, 4), dtype=torch.float32, device=dev)
+    self.quat[:, 0] = 1.0
+    self.depth = torch.empty((num_envs, self.H, self.W), dtype=torch.float32, device=dev)
+
+
+class _DepthFill:
+    """`fill` of every source that renders a depth image (`self()` -> `self.depth`, clipping range `near` / `far`)."""
+
+    def fill(self, hm: torch.Tensor, frame_min: torch.Tensor, indent: torch.Tensor | None, gelpad_height: float,
+             gelpad_to_camera_min_distance: float):
+        """hm (B, H, W) mm, frame_min (B,), indent (B,) or None: the render above, then the depth -> height-map pass
+        (`tacex_height_map_from_depth` with this source's clipping range), both on the current stream."""
+        if tuple(hm.shape) != tuple(self.depth.shape):
+            raise RuntimeError(f"height map has shape {tuple(hm.shape)}, the source renders {tuple(self.depth.shape)}")
+        depth = self()
+        B, H, W = hm.shape
+        with torch.cuda.device(hm.device):
+            rc = self._lib.tacex_height_map_from_depth(
+                _lib.ptr(depth), self.near, self.far, float(gelpad_height), float(gelpad_to_camera_min_distance), _lib.ptr(hm),
+                _lib.ptr(frame_min), _lib.ptr(indent), 0, 0, B, H, W, _lib.current_stream_handle(hm.device))
+        _lib.check(rc, "tacex_height_map_from_depth")
+
+
 class MeshDepthSource:
     """Camera depth of a rigid triangle mesh per env (arbitrary indenters): a callable for
     `cfg.sensor_camera_cfg.depth_source` that stands in for the IsaacLab TiledCamera read-out of the reference
@@ -65,17 +103,8 @@ class MeshDepthSource:
         self.tris = torch.as_tensor(tris, dtype=torch.int32).reshape(-1, 3).contiguous().to(dev)
         if self.tris.numel() == 0 or int(self.tris.min()) < 0 or int(self.tris.max()) >= self.verts.shape[0]:
             raise ValueError("MeshDepthSource: triangle indices out of range")
-        self.W, self.H = int(resolution[0]), int(resolution[1])
-        self.fx, self.fy, self.cx, self.cy = (float(v) for v in intrinsics)
-        self.near, self.far = float(clipping_range[0]), float(clipping_range[1])
-        self.pos = torch.zeros((num_envs, 3), dtype=torch.float32, device=dev)
-        self.pos[:, 2] = 1.0  # out of range until the caller places the object
-        self.quat = torch.zeros((num_envs, 4), dtype=torch.float32, device=dev)
-        self.quat[:, 0] = 1.0
-        self.depth = torch.empty((num_envs, self.H, self.W), dtype=torch.float32, device=dev)
-        v = self.verts.double().cpu()
-        c = 0.5 * (v.min(0).values + v.max(0).values)
-        self._bsphere = (C.c_float * 4)(float(c[0]), float(c[1]), float(c[2]), float((v - c).norm(dim=1).max()) * 1.0001)
+        _init_pinhole(self, num_envs, dev, resolution, intrinsics, clipping_range)
+        self._bsphere = (C.c_float * 4)(*_bounding_sphere(self.verts))
         self._lib = _lib.load_library()
 
     def __call__(self) -> torch.Tensor:
@@ -90,7 +119,7 @@ class MeshDepthSource:
         return self.depth
 
 
-class MeshLibraryDepthSource:
+class MeshLibraryDepthSource(_DepthFill):
     """Camera depth of a rigid triangle mesh per env, each env rendering ITS OWN mesh of a library (`tacex_depth_from_mesh_library`,
     one HIP launch plus one for meshes of more than 1024 triangles): the TiledCamera read-out of a scene whose envs hold different
     objects (a multi-asset spawner).  Same calling contract as `MeshDepthSource`: `source()` -> (num_envs, H, W) float32 depth in metres,
@@ -112,9 +141,7 @@ class MeshLibraryDepthSource:
             t = torch.as_tensor(t, dtype=torch.int32).reshape(-1, 3).cpu()
             if t.numel() == 0 or int(t.min()) < 0 or int(t.max()) >= v.shape[0]:
                 raise ValueError(f"MeshLibraryDepthSource: mesh {k}: triangle indices out of range")
-            vd = v.double()
-            c = 0.5 * (vd.min(0).values + vd.max(0).values)  # (the bounding sphere of MeshDepthSource)
-            spheres.append([float(c[0]), float(c[1]), float(c[2]), float((vd - c).norm(dim=1).max()) * 1.0001])
+            spheres.append(_bounding_sphere(v))
             table.append([sum(len(x) for x in tris), t.shape[0]])
             verts.append(v)
             tris.append(t + base)
@@ -125,15 +152,8 @@ class MeshLibraryDepthSource:
         self.mesh_tris = torch.tensor(table, dtype=torch.int32, device=dev)
         self.mesh_spheres = torch.tensor(spheres, dtype=torch.float32, device=dev)
         self._max_tris = max(n for _, n in table)
-        self.W, self.H = int(resolution[0]), int(resolution[1])
-        self.fx, self.fy, self.cx, self.cy = (float(v) for v in intrinsics)
-        self.near, self.far = float(clipping_range[0]), float(clipping_range[1])
-        self.pos = torch.zeros((num_envs, 3), dtype=torch.float32, device=dev)
-        self.pos[:, 2] = 1.0  # out of range until the caller places the object
-        self.quat = torch.zeros((num_envs, 4), dtype=torch.float32, device=dev)
-        self.quat[:, 0] = 1.0
+        _init_pinhole(self, num_envs, dev, resolution, intrinsics, clipping_range)
         self.mesh_ids = torch.zeros((num_envs,), dtype=torch.int32, device=dev)
-        self.depth = torch.empty((num_envs, self.H, self.W), dtype=torch.float32, device=dev)
         self._lib = _lib.load_library()
 
     def __call__(self) -> torch.Tensor:
@@ -147,20 +167,6 @@ class MeshLibraryDepthSource:
                 _lib.current_stream_handle(self.depth.device))
         _lib.check(rc, "tacex_depth_from_mesh_library")
         return self.depth
-
-    def fill(self, hm: torch.Tensor, frame_min: torch.Tensor, indent: torch.Tensor | None, gelpad_height: float,
-             gelpad_to_camera_min_distance: float):
-        """hm (B, H, W) mm, frame_min (B,), indent (B,) or None: the render above, then the depth -> height-map pass
-        (`tacex_height_map_from_depth` with this source's clipping range), both on the current stream."""
-        if tuple(hm.shape) != tuple(self.depth.shape):
-            raise RuntimeError(f"height map has shape {tuple(hm.shape)}, the source renders {tuple(self.depth.shape)}")
-        depth = self()
-        B, H, W = hm.shape
-        with torch.cuda.device(hm.device):
-            rc = self._lib.tacex_height_map_from_depth(
-                _lib.ptr(depth), self.near, self.far, float(gelpad_height), float(gelpad_to_camera_min_distance), _lib.ptr(hm),
-                _lib.ptr(frame_min), _lib.ptr(indent), 0, 0, B, H, W, _lib.current_stream_handle(hm.device))
-        _lib.check(rc, "tacex_height_map_from_depth")
 
 
 def contact_face_triangles(points, tets, optical_axis_w, min_cos: float = 0.5) -> np.ndarray:
@@ -209,30 +215,16 @@ class _SimCamera:
         return rot[0]
 
 
-class _SimCameraDepthSource(_SimCamera):
+class _SimCameraDepthSource(_SimCamera, _DepthFill):
     """What `FemSurfaceDepthSource` and `AffineBodyDepthSource` share: the sensor camera over a `UipcSim` (`_SimCamera`), the ordering behind
-    a step on a side stream, and `fill`.  A subclass supplies `_render(sim)`, the one launch that writes `self.depth` from the simulation
-    state."""
+    a step on a side stream, and `fill` (`_DepthFill`).  A subclass supplies `_render(sim)`, the one launch that writes `self.depth` from
+    the simulation state."""
 
     def __call__(self) -> torch.Tensor:
         sim = self._sim
         sim.wait_for_step()  # a step enqueued on a side stream (UipcSim.step_done) is ordered before the render
         self._render(sim)
         return self.depth
-
-    def fill(self, hm: torch.Tensor, frame_min: torch.Tensor, indent: torch.Tensor | None, gelpad_height: float,
-             gelpad_to_camera_min_distance: float):
-        """hm (B, H, W) mm, frame_min (B,), indent (B,) or None: the render above, then the depth -> height-map pass
-        (`tacex_height_map_from_depth` with this source's clipping range), both on the current stream."""
-        if tuple(hm.shape) != tuple(self.depth.shape):
-            raise RuntimeError(f"height map has shape {tuple(hm.shape)}, the source renders {tuple(self.depth.shape)}")
-        depth = self()
-        B, H, W = hm.shape
-        with torch.cuda.device(hm.device):
-            rc = self._lib.tacex_height_map_from_depth(
-                _lib.ptr(depth), self.near, self.far, float(gelpad_height), float(gelpad_to_camera_min_distance), _lib.ptr(hm),
-                _lib.ptr(frame_min), _lib.ptr(indent), 0, 0, B, H, W, _lib.current_stream_handle(hm.device))
-        _lib.check(rc, "tacex_height_map_from_depth")
 
 
 class _FemContactFace:

@@ -16,6 +16,7 @@ The projection is orthographic, as in `IndenterHeightMapSource`, and the relief 
 without undercuts."""
 from __future__ import annotations
 
+import functools
 import math
 from dataclasses import dataclass
 
@@ -77,7 +78,7 @@ class ReliefTile:
         return np.asarray([self.pitch_mm, self.top_mm, u0, v0], dtype=np.float32)
 
 
-class ReliefHeightMapSource:
+class ReliefHeightMapSource(_stage.LibrarySource):
     """A relief tile per env as the sensor's height-map source (`GelSightSensor.set_height_map_source`).  It owns the library - `texels`
     (all tiles back to back), `tiles_i` (P, 4) int32 [first texel, rows, cols, wrap], `tiles_f` (P, 4) float32 [pitch_mm, top_mm, u0,
     v0] - and two tensors the caller writes in place between steps: `pose` (num_envs, 16) float32 (`POSE_FIELDS`; `set_pose` fills it
@@ -85,7 +86,7 @@ class ReliefHeightMapSource:
     nothing).  `samples` = 4 averages four sub-pixel samples: the anti-aliasing for stamp edges and tiles finer than the pixel.
     The projection is orthographic and the relief is displaced along the optical axis: a height field without undercuts."""
 
-    writes_frame_rows = True  # fill(..., rows=) leaves the contact ranges of tacex_indentation_depth behind
+    _owner, _unit, _names = "ReliefHeightMapSource", "texel", ("texels", "tiles_i", "tiles_f", "relief_ids")
     tiles_f, relief_ids = _stage.table_attr("rows"), _stage.table_attr("ids")
 
     def __init__(self, tiles, num_envs: int, device, pixmm: float = 0.0295, gel_top_mm: float = 28.5, far_clip_mm: float = 29.0,
@@ -94,30 +95,15 @@ class ReliefHeightMapSource:
         heights = [t.validate() for t in tiles]
         if samples not in (1, 4):
             raise ValueError(f"ReliefHeightMapSource: samples = {samples} (must be 1 or 4)")
-        if not (math.isfinite(float(pixmm)) and float(pixmm) > 0):
-            raise ValueError(f"ReliefHeightMapSource: pixmm must be > 0, got {pixmm}")
-        if sum(h.size for h in heights) >= 2 ** 31:
-            raise ValueError("ReliefHeightMapSource: the library holds 2^31 texels or more (texel indices are 32-bit)")
-        self._lib, self._table = _stage.open_stage("ReliefHeightMapSource", "tiles_f", "relief_ids", tiles, ReliefTile, num_envs, device)
-        self.device = self._table.device
-        self.tiles = tuple(tiles)
-        self.num_envs, self.samples = int(num_envs), int(samples)
-        self.pixmm, self.gel_top_mm, self.far_clip_mm = float(pixmm), float(gel_top_mm), float(far_clip_mm)
-        first = np.concatenate([[0], np.cumsum([h.size for h in heights])[:-1]])
-        self.tiles_i = torch.tensor([[int(f), h.shape[0], h.shape[1], int(t.wrap)] for f, h, t in zip(first, heights, tiles)],
-                                    dtype=torch.int32, device=self.device)
-        self.texels = torch.from_numpy(np.concatenate([h.reshape(-1) for h in heights])).to(self.device)
-        self.pose = torch.zeros((self.num_envs, 16), dtype=torch.float32, device=self.device)
+        self._open(tiles, ReliefTile, heights, [(h.shape[0], h.shape[1], int(t.wrap)) for h, t in zip(heights, tiles)], num_envs, device, pixmm)
+        self.tiles, self.samples = tuple(tiles), int(samples)
+        self.gel_top_mm, self.far_clip_mm = float(gel_top_mm), float(far_clip_mm)
         self.pose[:, 0] = self.pose[:, 4] = 1.0  # (identity M, plane carrier; gain 1)
         self.pose[:, 12] = 1.0
 
     @property
     def num_tiles(self) -> int:
         return len(self.tiles)
-
-    def randomize(self, env_ids=None, generator=None):
-        """Re-draw the tile ids of `env_ids` (default: all) uniformly from [0, P) on the device."""
-        return self._table.randomize(env_ids, generator)
 
     def set_pose(self, cx_px, cy_px, yaw, press_mm, scale=1.0, tilt=(0, 0), carrier="plane", radius_mm=0.0, gain=1.0,
                  shift_texels=(0, 0), env_ids=slice(None)):
@@ -133,11 +119,7 @@ class ReliefHeightMapSource:
         ids = self.relief_ids[env_ids].long().clamp(0, self.num_tiles - 1)
         row = self.tiles_f[ids].double()
         n = ids.shape[0]
-
-        def per_env(v):
-            v = v.to(device=dev, dtype=torch.float64) if isinstance(v, torch.Tensor) else torch.tensor(float(v), dtype=torch.float64, device=dev)
-            return v.expand(n) if v.dim() == 0 else v
-
+        per_env = functools.partial(_stage.per_env, n=n, device=dev)
         cx, cy, yaw, scale = per_env(cx_px), per_env(cy_px), per_env(yaw), per_env(scale)
         tx, ty = per_env(tilt[0]), per_env(tilt[1])
         k = self.pixmm / (row[:, 0] * scale)
@@ -149,31 +131,12 @@ class ReliefHeightMapSource:
                 per_env(shift_texels[1]), torch.zeros(n, dtype=torch.float64, device=dev)]
         self.pose[env_ids] = torch.stack(cols, dim=1).float()
 
-    def fill(self, hm: torch.Tensor, frame_min: torch.Tensor, indent: torch.Tensor | None, gelpad_height: float,
-             gelpad_to_camera_min_distance: float, rows: torch.Tensor | None = None):
-        """hm (B, H, W) mm, frame_min (B,), indent (B,) or None, rows (B, 4) int32 or None - all written in one launch on the
-        current stream; frame_min, indent and rows are what `tacex_indentation_depth` gives for the map."""
-        B, dev = self.num_envs, self.device
-
-        def arg(name, t, shape, dtype=torch.float32, must="must be"):
-            return _stage.check_tensor("ReliefHeightMapSource", name, t, shape, dtype, dev, must=must)
-
-        arg("hm", hm, (B, "H", "W"))
-        arg("frame_min", frame_min, (B,))
-        if indent is not None:
-            arg("indent", indent, (B,))
-        if rows is not None:
-            arg("rows", rows, (B, 4), torch.int32)
-        arg("pose", self.pose, (B, 16), must="must stay")
-        arg("tiles_i", self.tiles_i, (self.num_tiles, 4), torch.int32, must="must stay")
-        arg("texels", self.texels, ("N",), must="must stay")
-        ids, tiles_f = self._table.check()
-        arg("tiles_f", tiles_f, (self.num_tiles, 4), must="must stay")
-        with torch.cuda.device(dev):
+    def _launch(self, texels, tiles_i, tiles_f, ids, hm, frame_min, indent, rows, gelpad_height, gelpad_to_camera_min_distance):
+        dev = self.device
+        with torch.cuda.device(dev):  # (one launch)
             rc = self._lib.tacex_height_map_from_relief(
-                _lib.ptr(self.texels), _lib.ptr(self.tiles_i), _lib.ptr(tiles_f), self.num_tiles, _lib.ptr(ids), _lib.ptr(self.pose),
-                self.gel_top_mm, self.far_clip_mm, float(gelpad_height), float(gelpad_to_camera_min_distance), _lib.ptr(hm),
-                _lib.ptr(frame_min), _lib.ptr(indent), _lib.ptr(rows), B, int(hm.shape[1]), int(hm.shape[2]), self.samples,
+                _lib.ptr(texels), _lib.ptr(tiles_i), _lib.ptr(tiles_f), self.num_tiles, _lib.ptr(ids), _lib.ptr(self.pose),
+                self.gel_top_mm, self.far_clip_mm, gelpad_height, gelpad_to_camera_min_distance, _lib.ptr(hm), _lib.ptr(frame_min),
+                _lib.ptr(indent), _lib.ptr(rows), self.num_envs, int(hm.shape[1]), int(hm.shape[2]), self.samples,
                 _lib.current_stream_handle(dev))
         _lib.check(rc, "tacex_height_map_from_relief")
-        return hm

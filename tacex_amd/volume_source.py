@@ -16,6 +16,7 @@ the clip planes, one trilinear tap per step.
 The projection is orthographic, as in `IndenterHeightMapSource`: X = column * pixmm, Y = row * pixmm, Z = depth [mm]."""
 from __future__ import annotations
 
+import functools
 import math
 from dataclasses import dataclass
 
@@ -98,7 +99,7 @@ class SdfVolume:
         return np.resize(picked, (count, 3)).astype(np.float32)
 
 
-class SdfVolumeSource:
+class SdfVolumeSource(_stage.LibrarySource):
     """A signed-distance volume per env as the sensor's height-map source (`GelSightSensor.set_height_map_source`).  It owns the
     library - `voxels` (all grids back to back), `volumes_i` (P, 4) int32 [first voxel, D, Hv, Wv], `volumes_f` (P, 8) float32
     [pitch_mm, i0, j0, k0, step_scale, 0, 0, 0], `surface_points` (P, K, 3) for `set_pose(press_mm=)` - and two tensors the caller
@@ -107,34 +108,24 @@ class SdfVolumeSource:
     outside [0, P) presses nothing).  The surface is {sdf = level_mm}: a positive level inflates the object.  Rays are marched
     between `near_clip_mm` and `far_clip_mm` for at most `max_steps` taps and stop within `tol_mm` of the surface."""
 
-    writes_frame_rows = True  # fill(..., rows=) leaves the contact ranges of tacex_indentation_depth behind
+    _owner, _unit, _names = "SdfVolumeSource", "voxel", ("voxels", "volumes_i", "volumes_f", "volume_ids")
     volumes_f, volume_ids = _stage.table_attr("rows"), _stage.table_attr("ids")
 
     def __init__(self, volumes, num_envs: int, device, pixmm: float = 0.0295, gel_top_mm: float = 28.5, near_clip_mm: float = 24.0,
                  far_clip_mm: float = 29.0, max_steps: int = 32, tol_mm: float = 1e-4):
         volumes = _stage.profile_list("SdfVolumeSource", "volumes", volumes, SdfVolume)
         grids = [v.validate() for v in volumes]
-        if not (math.isfinite(float(pixmm)) and float(pixmm) > 0):
-            raise ValueError(f"SdfVolumeSource: pixmm must be > 0, got {pixmm}")
         if not 1 <= int(max_steps) <= 128:
             raise ValueError(f"SdfVolumeSource: max_steps = {max_steps} (must be 1..128)")
         if not float(tol_mm) > 0:
             raise ValueError(f"SdfVolumeSource: tol_mm must be > 0, got {tol_mm}")
         if not float(near_clip_mm) < float(far_clip_mm):
             raise ValueError(f"SdfVolumeSource: near_clip_mm = {near_clip_mm} must lie below far_clip_mm = {far_clip_mm}")
-        if sum(g.size for g in grids) >= 2 ** 31:
-            raise ValueError("SdfVolumeSource: the library holds 2^31 voxels or more (voxel indices are 32-bit)")
-        self._lib, self._table = _stage.open_stage("SdfVolumeSource", "volumes_f", "volume_ids", volumes, SdfVolume, num_envs, device)
-        self.device = self._table.device
-        self.volumes = tuple(volumes)
-        self.num_envs, self.max_steps = int(num_envs), int(max_steps)
-        self.pixmm, self.gel_top_mm, self.tol_mm = float(pixmm), float(gel_top_mm), float(tol_mm)
+        self._open(volumes, SdfVolume, grids, [g.shape for g in grids], num_envs, device, pixmm)
+        self.volumes, self.max_steps = tuple(volumes), int(max_steps)
+        self.gel_top_mm, self.tol_mm = float(gel_top_mm), float(tol_mm)
         self.near_clip_mm, self.far_clip_mm = float(near_clip_mm), float(far_clip_mm)
-        first = np.concatenate([[0], np.cumsum([g.size for g in grids])[:-1]])
-        self.volumes_i = torch.tensor([[int(f), *g.shape] for f, g in zip(first, grids)], dtype=torch.int32, device=self.device)
-        self.voxels = torch.from_numpy(np.concatenate([g.reshape(-1) for g in grids])).to(self.device)
         self._surface_points = None
-        self.pose = torch.zeros((self.num_envs, 16), dtype=torch.float32, device=self.device)
         self.pose[:, 0] = self.pose[:, 4] = self.pose[:, 8] = self.pose[:, 12] = 1.0  # (identity R, scale 1)
         self.pose[:, 11] = 2.0 * self.far_clip_mm  # (until set_pose: beyond far clip)
 
@@ -148,10 +139,6 @@ class SdfVolumeSource:
         if self._surface_points is None:
             self._surface_points = torch.from_numpy(np.stack([v.surface_points() for v in self.volumes])).to(self.device)
         return self._surface_points
-
-    def randomize(self, env_ids=None, generator=None):
-        """Re-draw the volume ids of `env_ids` (default: all) uniformly from [0, P) on the device."""
-        return self._table.randomize(env_ids, generator)
 
     def set_pose(self, cx_px, cy_px, quat_wxyz, press_mm=None, z_mm=None, scale=1.0, level_mm=0.0, env_ids=slice(None)):
         """Place the volume of `env_ids` (default: all): its anchor at pixel (cx_px, cy_px), turned by `quat_wxyz` (object -> camera;
@@ -167,11 +154,7 @@ class SdfVolumeSource:
         dev = self.device
         ids = self.volume_ids[env_ids].long().clamp(0, self.num_volumes - 1)
         n = ids.shape[0]
-
-        def per_env(v):
-            v = v.to(device=dev, dtype=torch.float64) if isinstance(v, torch.Tensor) else torch.tensor(float(v), dtype=torch.float64, device=dev)
-            return v.expand(n) if v.dim() == 0 else v
-
+        per_env = functools.partial(_stage.per_env, n=n, device=dev)
         q = quat_wxyz.to(device=dev, dtype=torch.float64) if isinstance(quat_wxyz, torch.Tensor) else torch.tensor(
             [float(c) for c in quat_wxyz], dtype=torch.float64, device=dev)
         q = (q.expand(n, 4) if q.dim() == 1 else q)
@@ -190,31 +173,12 @@ class SdfVolumeSource:
         cols = [per_env(cx_px) * self.pixmm, per_env(cy_px) * self.pixmm, tz, scale, level, zero, zero]
         self.pose[env_ids] = torch.cat([R, torch.stack(cols, dim=1)], dim=1).float()
 
-    def fill(self, hm: torch.Tensor, frame_min: torch.Tensor, indent: torch.Tensor | None, gelpad_height: float,
-             gelpad_to_camera_min_distance: float, rows: torch.Tensor | None = None):
-        """hm (B, H, W) mm, frame_min (B,), indent (B,) or None, rows (B, 4) int32 or None - written by two launches on the current
-        stream; frame_min, indent and rows are what `tacex_indentation_depth` gives for the map."""
-        B, dev = self.num_envs, self.device
-
-        def arg(name, t, shape, dtype=torch.float32, must="must be"):
-            return _stage.check_tensor("SdfVolumeSource", name, t, shape, dtype, dev, must=must)
-
-        arg("hm", hm, (B, "H", "W"))
-        arg("frame_min", frame_min, (B,))
-        if indent is not None:
-            arg("indent", indent, (B,))
-        if rows is not None:
-            arg("rows", rows, (B, 4), torch.int32)
-        arg("pose", self.pose, (B, 16), must="must stay")
-        arg("volumes_i", self.volumes_i, (self.num_volumes, 4), torch.int32, must="must stay")
-        arg("voxels", self.voxels, ("N",), must="must stay")
-        ids, volumes_f = self._table.check()
-        arg("volumes_f", volumes_f, (self.num_volumes, 8), must="must stay")
-        with torch.cuda.device(dev):
+    def _launch(self, voxels, volumes_i, volumes_f, ids, hm, frame_min, indent, rows, gelpad_height, gelpad_to_camera_min_distance):
+        dev = self.device
+        with torch.cuda.device(dev):  # (two launches: the march, then the frame outputs of the map)
             rc = self._lib.tacex_height_map_from_sdf(
-                _lib.ptr(self.voxels), int(self.voxels.shape[0]), _lib.ptr(self.volumes_i), _lib.ptr(volumes_f), self.num_volumes,
-                _lib.ptr(ids), _lib.ptr(self.pose), self.pixmm, self.near_clip_mm, self.far_clip_mm, self.max_steps, self.tol_mm,
-                float(gelpad_height), float(gelpad_to_camera_min_distance), _lib.ptr(hm), _lib.ptr(frame_min), _lib.ptr(indent),
-                _lib.ptr(rows), B, int(hm.shape[1]), int(hm.shape[2]), _lib.current_stream_handle(dev))
+                _lib.ptr(voxels), int(voxels.shape[0]), _lib.ptr(volumes_i), _lib.ptr(volumes_f), self.num_volumes, _lib.ptr(ids),
+                _lib.ptr(self.pose), self.pixmm, self.near_clip_mm, self.far_clip_mm, self.max_steps, self.tol_mm, gelpad_height,
+                gelpad_to_camera_min_distance, _lib.ptr(hm), _lib.ptr(frame_min), _lib.ptr(indent), _lib.ptr(rows), self.num_envs,
+                int(hm.shape[1]), int(hm.shape[2]), _lib.current_stream_handle(dev))
         _lib.check(rc, "tacex_height_map_from_sdf")
-        return hm

@@ -38,7 +38,7 @@ SHAPES = {
 
 
 def columns_route(H, W):
-    """The block-size rule of run_frame_rows and the cols_ok test of frame_rows_kernel, restated."""
+    """The block-size rule of frame_rows_block_threads and the cols_ok test of frame_rows_kernel, restated."""
     if W % 4 != 0 or H > 2048:
         return "full"
     w4 = W // 4
