@@ -25,174 +25,18 @@
 // the step bound.  Pair candidates are rebuilt once per Newton iteration at reach 2.8 d_hat, which no pair
 // outside can cross into d_hat within one bounded step, so the line search's energies are exact.  (The CU-resident kernel of the
 // prescribed-indenter scenes keeps ALL per-vertex state in registers and is at its register limit: this scene got a kernel of its own.)
+// The scene's tables, closest points, barrier and CCD, the evaluation of a pair, the candidate cull, the contact record and the friction
+// law are fem_ball_pairs.h's, shared with the force report (fem_ball_contact_forces.h); here: the kernel and the two row kernels.
 
 #pragma once
-#include "fem_device.h"
+#include "fem_ball_pairs.h"  // BallDev, closest points, barrier, CCD, ball_pair_eval, ball_cull, the contact record, friction law
 
 namespace tacex {
 
-struct BallDev {
-  int nv = 0, nt = 0, npt = 0, nsv = 0;
-  const double* Y = nullptr;      // (nv,4) [1, X]
-  const int* tri = nullptr;       // (nt,3)
-  const double* area = nullptr;   // (nv) vertex areas
-  const int* ptri = nullptr;      // (npt,3) pad surface triangles
-  const int* psv = nullptr;       // (nsv) pad surface vertices
-  const double* parea = nullptr;  // (V) pad vertex areas (0: interior)
-  double S[16] = {};              // 4 x 4 moment matrix
-  double kv = 0.0, gh = 0.0, dhat = 0.0, kappa = 0.0;
-  // edge-edge pairs: pad surface edges x ball edges (unique edges of the two triangle lists), the area each edge stands for (a third of its
-  // triangles' rest areas) and its squared rest length (the mollifier's threshold); ee = 0 switches the pair kind off
-  int npe = 0, nbe = 0, ee = 0;
-  const int* pedge = nullptr;      // (npe,2)
-  const double* pearea = nullptr;  // (npe)
-  const double* pelen2 = nullptr;  // (npe)
-  const int* bedge = nullptr;      // (nbe,2)
-  const double* bearea = nullptr;  // (nbe)
-  const double* belen2 = nullptr;  // (nbe)
-  int ground = 0;
-  int kinematic = 0;  // AffineBodyConstitutionCfg.kinematic (uipc_object.py:70-73, 463-466: `is_fixed`): the body's rows are not unknowns - the
-                      // caller moves q between steps, the pad sees it through the pairs (both ways) and their friction
-};
-
-constexpr int kBallMaxCand = 512;     // candidate pad vertices / pad triangles / ball vertices per env
-constexpr double kBallReach = 2.0;    // additive CCD on pairs closer than kBallReach * d_hat
-constexpr double kBallKeep = 0.1;     // ... which may keep this fraction of their gap
-constexpr int kBallFlagOverflow = 16; // step_info flag: a candidate / pair list overflowed (the scene is outside what this slice handles)
-
-// (kBallMaxPairs, kBallMaxActive, kBallRec, kBallMaxFric and the env's workspace block, ball_ws_doubles: fem_layout.h)
 // dynamic LDS: x (V,3) | p (V + 4,3) | H.p accumulators = H.p (V,3) | z (V,3) | r (V + 4,3) | d (V + 4,3) (doubles) || chain factors (V,15)
 // (floats) || chain successor / predecessor (V each, u16): every vector of the PCG loop, 104 KB at 495 vertices
 __host__ __device__ inline size_t ball_lds_bytes(int V) {
   return ((((size_t)18 * V + 36) * sizeof(double) + (size_t)15 * V * sizeof(float) + (size_t)2 * V * sizeof(unsigned short)) + 15) & ~(size_t)15;
-}
-
-// closest point of triangle (a, b, c) to p: barycentric coordinates, distance, unit vector from the closest point to p
-// (Ericson 5.1.5, regions in the book's order - oracle/abd_oracle.py point_triangle)
-__device__ __forceinline__ void pt_closest(const double p[3], const double a[3], const double b[3], const double c[3], double beta[3], double& d,
-                                           double n[3]) {
-  const double ab[3] = {b[0] - a[0], b[1] - a[1], b[2] - a[2]}, ac[3] = {c[0] - a[0], c[1] - a[1], c[2] - a[2]};
-  const double ap[3] = {p[0] - a[0], p[1] - a[1], p[2] - a[2]};
-  const double d1 = ab[0] * ap[0] + ab[1] * ap[1] + ab[2] * ap[2], d2 = ac[0] * ap[0] + ac[1] * ap[1] + ac[2] * ap[2];
-  const double bp[3] = {p[0] - b[0], p[1] - b[1], p[2] - b[2]};
-  const double d3 = ab[0] * bp[0] + ab[1] * bp[1] + ab[2] * bp[2], d4 = ac[0] * bp[0] + ac[1] * bp[1] + ac[2] * bp[2];
-  const double cp[3] = {p[0] - c[0], p[1] - c[1], p[2] - c[2]};
-  const double d5 = ab[0] * cp[0] + ab[1] * cp[1] + ab[2] * cp[2], d6 = ac[0] * cp[0] + ac[1] * cp[1] + ac[2] * cp[2];
-  const double vc = d1 * d4 - d3 * d2, vb = d5 * d2 - d1 * d6, va = d3 * d6 - d5 * d4;
-  double s, u;
-  if (d1 <= 0.0 && d2 <= 0.0) { s = 0.0; u = 0.0; }
-  else if (d3 >= 0.0 && d4 <= d3) { s = 1.0; u = 0.0; }
-  else if (vc <= 0.0 && d1 >= 0.0 && d3 <= 0.0) { s = d1 / (d1 - d3); u = 0.0; }
-  else if (d6 >= 0.0 && d5 <= d6) { s = 0.0; u = 1.0; }
-  else if (vb <= 0.0 && d2 >= 0.0 && d6 <= 0.0) { s = 0.0; u = d2 / (d2 - d6); }
-  else if (va <= 0.0 && (d4 - d3) >= 0.0 && (d5 - d6) >= 0.0) { u = (d4 - d3) / ((d4 - d3) + (d5 - d6)); s = 1.0 - u; }
-  else { const double den = 1.0 / (va + vb + vc); s = vb * den; u = vc * den; }
-  beta[0] = 1.0 - s - u; beta[1] = s; beta[2] = u;
-  const double r0 = ap[0] - s * ab[0] - u * ac[0], r1 = ap[1] - s * ab[1] - u * ac[1], r2 = ap[2] - s * ab[2] - u * ac[2];
-  d = sqrt(r0 * r0 + r1 * r1 + r2 * r2);
-  const double id = d > 0.0 ? 1.0 / d : 0.0;
-  n[0] = r0 * id; n[1] = r1 * id; n[2] = r2 * id;
-}
-
-// additive CCD of one point-triangle pair (oracle/abd_oracle.py accd_point_triangle): largest t <= t_max keeping >= keep * d(0)
-__device__ double accd_pt(const double p[3], const double tr[9], const double dp_in[3], const double dtr_in[9], double t_max) {
-  double dp[3], dtr[9], mean[3];
-#pragma unroll
-  for (int i = 0; i < 3; ++i) mean[i] = (dp_in[i] + dtr_in[i] + dtr_in[3 + i] + dtr_in[6 + i]) * 0.25;
-#pragma unroll
-  for (int i = 0; i < 3; ++i) { dp[i] = dp_in[i] - mean[i]; dtr[i] = dtr_in[i] - mean[i]; dtr[3 + i] = dtr_in[3 + i] - mean[i]; dtr[6 + i] = dtr_in[6 + i] - mean[i]; }
-  double lt = 0.0;
-#pragma unroll
-  for (int k = 0; k < 3; ++k) lt = fmax(lt, sqrt(dtr[3 * k] * dtr[3 * k] + dtr[3 * k + 1] * dtr[3 * k + 1] + dtr[3 * k + 2] * dtr[3 * k + 2]));
-  const double l = sqrt(dp[0] * dp[0] + dp[1] * dp[1] + dp[2] * dp[2]) + lt;
-  if (!(l > 0.0)) return t_max;
-  auto dist = [&](double t) {
-    double q[3], a[3], b[3], c[3], be[3], d, n[3];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) { q[i] = p[i] + t * dp[i]; a[i] = tr[i] + t * dtr[i]; b[i] = tr[3 + i] + t * dtr[3 + i]; c[i] = tr[6 + i] + t * dtr[6 + i]; }
-    pt_closest(q, a, b, c, be, d, n);
-    return d;
-  };
-  const double d0 = dist(0.0), g = kBallKeep * d0;
-  double t = 0.0, tl = (1.0 - kBallKeep) * d0 / l;
-  for (int it = 0; it < 64; ++it) {
-    const double d = dist(t + tl);
-    if (t > 0.0 && d < g) break;
-    t += tl;
-    if (t >= t_max) return t_max;
-    tl = kCcdSlack * d / l;
-  }
-  return t;
-}
-
-// closest points of segments a0-a1 and b0-b1 (Ericson 5.1.9 - oracle/abd_oracle.py segment_segment): parameters, distance, unit vector from
-// the point on b to the point on a; the distance's gradient is (1-s) n, s n on a's end points and -(1-t) n, -t n on b's
-__device__ __forceinline__ void ee_closest(const double a0[3], const double a1[3], const double b0[3], const double b1[3], double& s, double& t, double& d,
-                                           double n[3]) {
-  const double d1[3] = {a1[0] - a0[0], a1[1] - a0[1], a1[2] - a0[2]}, d2[3] = {b1[0] - b0[0], b1[1] - b0[1], b1[2] - b0[2]};
-  const double r[3] = {a0[0] - b0[0], a0[1] - b0[1], a0[2] - b0[2]};
-  const double a = d1[0] * d1[0] + d1[1] * d1[1] + d1[2] * d1[2], e = d2[0] * d2[0] + d2[1] * d2[1] + d2[2] * d2[2];
-  const double f = d2[0] * r[0] + d2[1] * r[1] + d2[2] * r[2], c = d1[0] * r[0] + d1[1] * r[1] + d1[2] * r[2];
-  const double bq = d1[0] * d2[0] + d1[1] * d2[1] + d1[2] * d2[2];
-  const double den = a * e - bq * bq;
-  s = den > 0.0 ? fmin(fmax((bq * f - c * e) / den, 0.0), 1.0) : 0.0;
-  t = (bq * s + f) / e;
-  if (t < 0.0) { t = 0.0; s = fmin(fmax(-c / a, 0.0), 1.0); }
-  else if (t > 1.0) { t = 1.0; s = fmin(fmax((bq - c) / a, 0.0), 1.0); }
-  const double w0 = r[0] + s * d1[0] - t * d2[0], w1 = r[1] + s * d1[1] - t * d2[1], w2 = r[2] + s * d1[2] - t * d2[2];
-  d = sqrt(w0 * w0 + w1 * w1 + w2 * w2);
-  const double id = d > 0.0 ? 1.0 / d : 0.0;
-  n[0] = w0 * id; n[1] = w1 * id; n[2] = w2 * id;
-}
-
-// IPC's mollifier of nearly parallel edge pairs in c = |e_a x e_b|^2 (Li et al. 2020 eq. 24 - oracle edge_mollifier): m, dm/dc; u = e_a x e_b
-__device__ __forceinline__ void ee_mollifier(const double a0[3], const double a1[3], const double b0[3], const double b1[3], double eps, double& mol, double& dm,
-                                             double e1[3], double e2[3], double u[3]) {
-#pragma unroll
-  for (int i = 0; i < 3; ++i) { e1[i] = a1[i] - a0[i]; e2[i] = b1[i] - b0[i]; }
-  u[0] = e1[1] * e2[2] - e1[2] * e2[1]; u[1] = e1[2] * e2[0] - e1[0] * e2[2]; u[2] = e1[0] * e2[1] - e1[1] * e2[0];
-  const double r = (u[0] * u[0] + u[1] * u[1] + u[2] * u[2]) / eps;
-  if (r < 1.0) { mol = (2.0 - r) * r; dm = 2.0 * (1.0 - r) / eps; }
-  else { mol = 1.0; dm = 0.0; }
-}
-
-// additive CCD of one edge-edge pair (oracle accd_edge_edge); ea, eb, dea, deb: the two end points of each edge, row-major (2,3)
-__device__ double accd_ee(const double ea[6], const double eb[6], const double dea_in[6], const double deb_in[6], double t_max) {
-  double da[6], db[6], mean[3];
-#pragma unroll
-  for (int i = 0; i < 3; ++i) mean[i] = (dea_in[i] + dea_in[3 + i] + deb_in[i] + deb_in[3 + i]) * 0.25;
-#pragma unroll
-  for (int i = 0; i < 3; ++i) { da[i] = dea_in[i] - mean[i]; da[3 + i] = dea_in[3 + i] - mean[i]; db[i] = deb_in[i] - mean[i]; db[3 + i] = deb_in[3 + i] - mean[i]; }
-  const double la = fmax(sqrt(da[0] * da[0] + da[1] * da[1] + da[2] * da[2]), sqrt(da[3] * da[3] + da[4] * da[4] + da[5] * da[5]));
-  const double lb = fmax(sqrt(db[0] * db[0] + db[1] * db[1] + db[2] * db[2]), sqrt(db[3] * db[3] + db[4] * db[4] + db[5] * db[5]));
-  const double l = la + lb;
-  if (!(l > 0.0)) return t_max;
-  auto dist = [&](double t) {
-    double a0[3], a1[3], b0[3], b1[3], s, u, d, n[3];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) { a0[i] = ea[i] + t * da[i]; a1[i] = ea[3 + i] + t * da[3 + i]; b0[i] = eb[i] + t * db[i]; b1[i] = eb[3 + i] + t * db[3 + i]; }
-    ee_closest(a0, a1, b0, b1, s, u, d, n);
-    return d;
-  };
-  const double d0 = dist(0.0), g = kBallKeep * d0;
-  double t = 0.0, tl = (1.0 - kBallKeep) * d0 / l;
-  for (int it = 0; it < 64; ++it) {
-    const double d = dist(t + tl);
-    if (t > 0.0 && d < g) break;
-    t += tl;
-    if (t >= t_max) return t_max;
-    tl = kCcdSlack * d / l;
-  }
-  return t;
-}
-
-__device__ __forceinline__ void barrier3(double s, double& b, double& b1, double& b2) {  // b(s), b'(s), b''(s) of the dimensionless barrier
-  if (!(s > 0.0)) { b = INFINITY; b1 = 0.0; b2 = 0.0; return; }
-  if (s >= 1.0) { b = 0.0; b1 = 0.0; b2 = 0.0; return; }
-  const double ln = log(s), q = s - 1.0;
-  b = -q * q * ln;
-  b1 = -2.0 * q * ln - q * q / s;
-  b2 = -2.0 * ln - 4.0 * q / s + q * q / (s * s);
 }
 
 // mode 0: Newton loop of a time step; mode 1: energy and gradient at (x, q) only (terms entry point of the C ABI: tests)
@@ -234,9 +78,9 @@ __global__ __launch_bounds__(NT_, NT_ >= 512 ? TACEX_BALL_WG_PER_CU : 1) void fe
   double* xbc = xb + (size_t)3 * nv;   // ... at the candidate
   double* dxb = xbc + (size_t)3 * nv;  // ... their displacement along the Newton direction
   double* bts = dxb + (size_t)3 * nv;  // (nt,4) bounding sphere of every ball triangle at x
-  int* plist = reinterpret_cast<int*>(bts + (size_t)4 * nt);  // (kBallMaxPairs) kind << 30 | point << 15 | triangle
+  int* plist = reinterpret_cast<int*>(bts + (size_t)4 * nt);  // (kBallMaxPairs) ball_pair_code
   double* arec = reinterpret_cast<double*>(plist + kBallMaxPairs);
-  double* frec = arec + (size_t)kBallMaxActive * kBallRec;  // lagged friction contacts of the step: lam | n (3) | ball coefficients (4) | pad coefficients (3) | pad rows (3 ints)
+  double* frec = arec + (size_t)kBallMaxActive * kBallRec;  // lagged friction contacts of the step (ball_rec_store, head = lam)
   double* fM = frec + (size_t)kBallMaxFric * kBallRec;      // their 3 x 3 Hessians at x (6 each, dt^2 mu lam [a T + (b - a) t t^T])
   // LAGGED COULOMB FRICTION of every contact (Li et al. 2020 eq. 18-20; US:103-124 friction ratio / eps_velocity, tacex_fem_set_friction): the
   // contacts of the state the step STARTS from - active pairs of both kinds, ground contacts of both bodies - are frozen as (normal force,
@@ -244,6 +88,7 @@ __global__ __launch_bounds__(NT_, NT_ >= 512 ? TACEX_BALL_WG_PER_CU : 1) void fe
   const double* xprev = xprevg ? xprevg + o : nullptr;
   const bool fric = m.fric_mu > 0.0 && xprev != nullptr && qprevg != nullptr;
   const double f_eps = m.fric_eps, f_mu = m.fric_mu;
+  const double kUp[3] = {0.0, 0.0, 1.0};  // the ground's normal
   double* xs = ball_lds;           // (V,3) x of the iteration: the tet state is recomputed from it in every H.p (no cached F in HBM)
   double* ps = xs + 3 * V;         // (V + 4,3) PCG direction
   double* acc = ps + 3 * VN;       // (V,3) per-vertex sums of the tets' rows (ds_add_f64)
@@ -275,15 +120,8 @@ __global__ __launch_bounds__(NT_, NT_ >= 512 ? TACEX_BALL_WG_PER_CU : 1) void fe
   if (tid == 0) { s_flags = 0; n_fric = 0; }
   __syncthreads();
 
-  auto ball_points = [&](const double* qq, double* out) {  // out (nv,3) = Y qq; qq in LDS
-    for (int k = tid; k < nv; k += NT) {
-      const double y0 = bd.Y[k * 4], y1 = bd.Y[k * 4 + 1], y2 = bd.Y[k * 4 + 2], y3 = bd.Y[k * 4 + 3];
-#pragma unroll
-      for (int i = 0; i < 3; ++i) out[k * 3 + i] = y0 * qq[i] + y1 * qq[3 + i] + y2 * qq[6 + i] + y3 * qq[9 + i];
-    }
-  };
   auto fric_u = [&](const double* rc, const double* xx, const double* qq, double u[3]) {  // tangential relative displacement since the step's start
-    const int* ri = reinterpret_cast<const int*>(rc + 11);
+    const int* ri = ball_rec_rows(rc);
     double rel[3] = {0.0, 0.0, 0.0};
 #pragma unroll
     for (int a4 = 0; a4 < 4; ++a4)
@@ -294,9 +132,7 @@ __global__ __launch_bounds__(NT_, NT_ >= 512 ? TACEX_BALL_WG_PER_CU : 1) void fe
       if (ri[r] >= 0)
 #pragma unroll
         for (int i = 0; i < 3; ++i) rel[i] += rc[8 + r] * (xx[ri[r] * 3 + i] - xprev[ri[r] * 3 + i]);
-    const double rn = rel[0] * rc[1] + rel[1] * rc[2] + rel[2] * rc[3];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) u[i] = rel[i] - rn * rc[1 + i];
+    ball_tangential(rel, rc + 1, u);
   };
   // energy of the state (xx pad vertices in global memory, qq ball rows in LDS, xbb its surface points): every term of
   // oracle/abd_oracle.py BallScene.energy; the pairs are those of the iteration's list
@@ -353,38 +189,13 @@ __global__ __launch_bounds__(NT_, NT_ >= 512 ? TACEX_BALL_WG_PER_CU : 1) void fe
     }
     const int np = n_pairs;
     for (int k = tid; k < np; k += NT) {
-      const unsigned code = (unsigned)plist[k];
-      const int kind = (int)(code >> 30), pi = (int)((code >> 15) & 0x7fff), tj = (int)(code & 0x7fff);
-      double d, w;
-      if (kind == 2) {
-        const int* ea = bd.pedge + pi * 2;
-        const int* eb = bd.bedge + tj * 2;
-        double a0[3], a1[3], b0[3], b1[3], s, t, n[3], mol, dm, e1[3], e2[3], u[3];
-#pragma unroll
-        for (int i = 0; i < 3; ++i) { a0[i] = xx[ea[0] * 3 + i]; a1[i] = xx[ea[1] * 3 + i]; b0[i] = xbb[eb[0] * 3 + i]; b1[i] = xbb[eb[1] * 3 + i]; }
-        ee_closest(a0, a1, b0, b1, s, t, d, n);
-        ee_mollifier(a0, a1, b0, b1, 1e-3 * bd.pelen2[pi] * bd.belen2[tj], mol, dm, e1, e2, u);
-        w = 0.5 * (bd.pearea[pi] + bd.bearea[tj]) * mol;
-      } else {
-        double p3[3], a[3], bq[3], c[3], be[3], n[3];
-        if (kind == 0) {
-          const int* tr = bd.tri + tj * 3;
-#pragma unroll
-          for (int i = 0; i < 3; ++i) { p3[i] = xx[pi * 3 + i]; a[i] = xbb[tr[0] * 3 + i]; bq[i] = xbb[tr[1] * 3 + i]; c[i] = xbb[tr[2] * 3 + i]; }
-          w = bd.parea[pi];
-        } else {
-          const int* tr = bd.ptri + tj * 3;
-#pragma unroll
-          for (int i = 0; i < 3; ++i) { p3[i] = xbb[pi * 3 + i]; a[i] = xx[tr[0] * 3 + i]; bq[i] = xx[tr[1] * 3 + i]; c[i] = xx[tr[2] * 3 + i]; }
-          w = bd.area[pi];
-        }
-        pt_closest(p3, a, bq, c, be, d, n);
-      }
-      if (d < dhat) {
-        double bb, b1, b2;
-        barrier3(d / dhat, bb, b1, b2);
-        if (w > 0.0) e += kk * w * bb;  // (w = 0: an exactly parallel edge pair - mollified away, whatever its distance)
-      }
+      int kind, pi, tj;
+      ball_pair_decode(plist[k], kind, pi, tj);
+      BallPairEval pe;  // (the energy takes d and w: the coefficients are dropped where this is inlined)
+      if (!ball_pair_eval<true>(kind, pi, tj, xx, xbb, bd, pe)) continue;  // (w = 0: an exactly parallel edge pair - mollified away, whatever its distance)
+      double bb, b1, b2;
+      barrier3(pe.d / dhat, bb, b1, b2);
+      e += kk * pe.w * bb;
     }
     if (fric) {
       const int nf = n_fric;
@@ -392,8 +203,9 @@ __global__ __launch_bounds__(NT_, NT_ >= 512 ? TACEX_BALL_WG_PER_CU : 1) void fe
         const double* rc = frec + (size_t)k * kBallRec;
         double u[3];
         fric_u(rc, xx, qq, u);
-        const double yv = sqrt(u[0] * u[0] + u[1] * u[1] + u[2] * u[2]);
-        e += dt2 * f_mu * rc[0] * (yv < f_eps ? -yv * yv * yv / (3.0 * f_eps * f_eps) + yv * yv / f_eps + f_eps / 3.0 : yv);
+        double f0, fa, fb;
+        ball_fric_law(sqrt(u[0] * u[0] + u[1] * u[1] + u[2] * u[2]), f_eps, f0, fa, fb);
+        e += dt2 * f_mu * rc[0] * f0;
       }
     }
     return block_sum(e, sh);
@@ -515,7 +327,7 @@ __global__ __launch_bounds__(NT_, NT_ >= 512 ? TACEX_BALL_WG_PER_CU : 1) void fe
 #define SUB_TICK0() do { } while (0)
 #define SUB_TICK(k) do { } while (0)
 #endif
-  ball_points(qs, xb);
+  ball_points(bd, qs, xb, tid, NT);
   for (int k = tid; k < 3 * V; k += NT) xs[k] = x[k];
   __syncthreads();
   int n_newton = 0, pcg_total = 0;
@@ -541,11 +353,6 @@ __global__ __launch_bounds__(NT_, NT_ >= 512 ? TACEX_BALL_WG_PER_CU : 1) void fe
 #pragma unroll
         for (int i = 0; i < 3; ++i) atomicAdd(&vg[v[w4] * 3 + i], g[w4 * 3 + i]);
     }
-    double rb = 0.0;  // bounding radius of the ball about p
-    for (int k = tid; k < nv; k += NT) {
-      const double r0 = xb[k * 3] - qs[0], r1 = xb[k * 3 + 1] - qs[1], r2 = xb[k * 3 + 2] - qs[2];
-      rb = fmax(rb, sqrt(r0 * r0 + r1 * r1 + r2 * r2));
-    }
     for (int t = tid; t < nt; t += NT) {
       const int* tr = bd.tri + t * 3;
       double c3[3], rt = 0.0;
@@ -559,159 +366,42 @@ __global__ __launch_bounds__(NT_, NT_ >= 512 ? TACEX_BALL_WG_PER_CU : 1) void fe
       bts[t * 4] = c3[0]; bts[t * 4 + 1] = c3[1]; bts[t * 4 + 2] = c3[2]; bts[t * 4 + 3] = rt;
     }
     BALL_TICK(0);  // element pass, ball triangle spheres
-    if (tid == 0) { n_cpv = 0; n_cpt = 0; n_cpe = 0; n_cbv = 0; n_cbt = 0; n_cbe = 0; n_pairs = 0; n_act = 0; }
+    if (tid == 0) { n_pairs = 0; n_act = 0; }
     if (tid < 12) gb[tid] = 0.0;
     if (tid < 16) YY[tid] = 0.0;
     if (tid < 144) Bm[tid] = 0.0;
-    rb = block_sum_max(rb, sh);
-    // pad surface vertices / triangles within reach of the ball's bounding sphere; ball vertices within reach of ANY candidate pad triangle
-    // are found pair by pair below
-    for (int k = tid; k < bd.nsv; k += NT) {
-      const int v = bd.psv[k];
-      const double r0 = xs[v * 3] - qs[0], r1 = xs[v * 3 + 1] - qs[1], r2 = xs[v * 3 + 2] - qs[2];
-      const double lim = rb + L;
-      if (r0 * r0 + r1 * r1 + r2 * r2 < lim * lim) {
-        const int s = atomicAdd(&n_cpv, 1);
-        if (s < kBallMaxCand) cpv[s] = (unsigned short)v;
-      }
-    }
-    for (int k = tid; k < bd.npt; k += NT) {
-      const int* tr = bd.ptri + k * 3;
-      double c3[3], rt = 0.0;
-#pragma unroll
-      for (int i = 0; i < 3; ++i) c3[i] = (xs[tr[0] * 3 + i] + xs[tr[1] * 3 + i] + xs[tr[2] * 3 + i]) * (1.0 / 3.0);
-#pragma unroll
-      for (int j = 0; j < 3; ++j) {
-        const double r0 = xs[tr[j] * 3] - c3[0], r1 = xs[tr[j] * 3 + 1] - c3[1], r2 = xs[tr[j] * 3 + 2] - c3[2];
-        rt = fmax(rt, sqrt(r0 * r0 + r1 * r1 + r2 * r2));
-      }
-      const double r0 = c3[0] - qs[0], r1 = c3[1] - qs[1], r2 = c3[2] - qs[2];
-      const double lim = rb + L + rt;
-      if (r0 * r0 + r1 * r1 + r2 * r2 < lim * lim) {
-        const int s = atomicAdd(&n_cpt, 1);
-        if (s < kBallMaxCand) cpt[s] = (unsigned short)k;
-      }
-    }
-    if (bd.ee)
-      for (int k = tid; k < bd.npe; k += NT) {
-        const int* ed = bd.pedge + k * 2;
-        double r2 = 0.0, h2 = 0.0;
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-          const double mi = 0.5 * (xs[ed[0] * 3 + i] + xs[ed[1] * 3 + i]) - qs[i], hi = 0.5 * (xs[ed[1] * 3 + i] - xs[ed[0] * 3 + i]);
-          r2 += mi * mi; h2 += hi * hi;
-        }
-        const double lim = rb + L + sqrt(h2);
-        if (r2 < lim * lim) {
-          const int s = atomicAdd(&n_cpe, 1);
-          if (s < kBallMaxCand) cpe[s] = (unsigned short)k;
-        }
-      }
-    __syncthreads();
-    if (n_cpv > kBallMaxCand || n_cpt > kBallMaxCand || n_cpe > kBallMaxCand) { if (tid == 0) s_flags |= kBallFlagOverflow; }
-    const int ncpv = min(n_cpv, kBallMaxCand), ncpt = min(n_cpt, kBallMaxCand), ncpe = min(n_cpe, kBallMaxCand);
-    // the ball's side of the lists: what lies within L of the bounding box of the pad's candidates (a ball of 320 triangles / 480 edges / 162
-    // vertices touches the pad with a few dozen of each: the pair tests below shrink accordingly)
-    double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-    auto grow = [&](int v) {
-#pragma unroll
-      for (int i = 0; i < 3; ++i) { lo[i] = fmin(lo[i], xs[v * 3 + i]); hi[i] = fmax(hi[i], xs[v * 3 + i]); }
-    };
-    for (int k = tid; k < ncpv; k += NT) grow(cpv[k]);
-    for (int k = tid; k < ncpt; k += NT) { const int* tr = bd.ptri + cpt[k] * 3; grow(tr[0]); grow(tr[1]); grow(tr[2]); }
-    for (int k = tid; k < ncpe; k += NT) { const int* ed = bd.pedge + cpe[k] * 2; grow(ed[0]); grow(ed[1]); }
-#pragma unroll
-    for (int i = 0; i < 3; ++i) { lo[i] = -block_sum_max(-lo[i], sh) - L; hi[i] = block_sum_max(hi[i], sh) + L; }
-    for (int k = tid; k < nv; k += NT) {
-      const double p0 = xb[k * 3], p1 = xb[k * 3 + 1], p2 = xb[k * 3 + 2];
-      if (p0 >= lo[0] && p0 <= hi[0] && p1 >= lo[1] && p1 <= hi[1] && p2 >= lo[2] && p2 <= hi[2]) {
-        const int sl = atomicAdd(&n_cbv, 1);
-        if (sl < kBallMaxCand) cbv[sl] = (unsigned short)k;
-      }
-    }
-    for (int t = tid; t < nt; t += NT) {
+    // candidates at reach L (the cull's first barrier also stands behind the zeroing above); a ball triangle by its sphere
+    BallCull cl = {cpv, cpt, cpe, cbv, cbt, cbe, &n_cpv, &n_cpt, &n_cpe, &n_cbv, &n_cbt, &n_cbe, &s_flags};
+    ball_cull<NT>(bd, cl, xs, qs, xb, L, sh, tid, [&](int t, const double* lo, const double* hi) __attribute__((always_inline)) {
       const double rt = bts[t * 4 + 3];
       bool in = true;
 #pragma unroll
       for (int i = 0; i < 3; ++i) in = in && bts[t * 4 + i] + rt >= lo[i] && bts[t * 4 + i] - rt <= hi[i];
-      if (in) {
-        const int sl = atomicAdd(&n_cbt, 1);
-        if (sl < kBallMaxCand) cbt[sl] = (unsigned short)t;
+      return in;
+    });
+    // pair list: the products of the candidate lists behind a cheap rejection, every pair closer than L.  Kinds 1 and 2 reject with
+    // ball_pair_far; kind 0 keeps its own test against the triangle's sphere bts, which this kernel has at hand
+    auto list_pair = [&](int kind, int i, int j) __attribute__((always_inline)) {
+      BallPairEval pe;
+      ball_pair_eval<false>(kind, i, j, xs, xb, bd, pe);  // (the distance alone is used)
+      if (pe.d < L) {
+        const int s = atomicAdd(&n_pairs, 1);
+        if (s < kBallMaxPairs) plist[s] = ball_pair_code(kind, i, j);
       }
-    }
-    if (bd.ee)
-      for (int k = tid; k < bd.nbe; k += NT) {
-        const int* eb = bd.bedge + k * 2;
-        bool in = true;
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-          const double a = xb[eb[0] * 3 + i], b2 = xb[eb[1] * 3 + i];
-          in = in && fmax(a, b2) >= lo[i] && fmin(a, b2) <= hi[i];
-        }
-        if (in) {
-          const int sl = atomicAdd(&n_cbe, 1);
-          if (sl < kBallMaxCand) cbe[sl] = (unsigned short)k;
-        }
-      }
-    __syncthreads();
-    if (n_cbv > kBallMaxCand || n_cbt > kBallMaxCand || n_cbe > kBallMaxCand) { if (tid == 0) s_flags |= kBallFlagOverflow; }
-    const int ncbv = min(n_cbv, kBallMaxCand), ncbt = min(n_cbt, kBallMaxCand), ncbe = min(n_cbe, kBallMaxCand);
-    // pairs, kind 0: candidate pad vertex x candidate ball triangle
-    for (int k = tid; k < ncpv * ncbt; k += NT) {
-      const int v = cpv[k / ncbt], t = cbt[k - (k / ncbt) * ncbt];
+    };
+    for (int k = tid; k < cl.npv * cl.nbt; k += NT) {
+      const int v = cpv[k / cl.nbt], t = cbt[k - (k / cl.nbt) * cl.nbt];
       const double r0 = xs[v * 3] - bts[t * 4], r1 = xs[v * 3 + 1] - bts[t * 4 + 1], r2 = xs[v * 3 + 2] - bts[t * 4 + 2];
       const double lim = L + bts[t * 4 + 3];
-      if (r0 * r0 + r1 * r1 + r2 * r2 >= lim * lim) continue;
-      const int* tr = bd.tri + t * 3;
-      double p3[3], a[3], bq[3], c[3], be[3], d, n[3];
-#pragma unroll
-      for (int i = 0; i < 3; ++i) { p3[i] = xs[v * 3 + i]; a[i] = xb[tr[0] * 3 + i]; bq[i] = xb[tr[1] * 3 + i]; c[i] = xb[tr[2] * 3 + i]; }
-      pt_closest(p3, a, bq, c, be, d, n);
-      if (d < L) {
-        const int s = atomicAdd(&n_pairs, 1);
-        if (s < kBallMaxPairs) plist[s] = (0 << 30) | (v << 15) | t;
-      }
+      if (r0 * r0 + r1 * r1 + r2 * r2 < lim * lim) list_pair(0, v, t);
     }
-    // pairs, kind 1: candidate ball vertex x candidate pad triangle
-    for (int k = tid; k < ncbv * ncpt; k += NT) {
-      const int bv = cbv[k / ncpt], t = cpt[k - (k / ncpt) * ncpt];
-      const int* tr = bd.ptri + t * 3;
-      double p3[3], a[3], bq[3], c[3], be[3], d, n[3];
-#pragma unroll
-      for (int i = 0; i < 3; ++i) { p3[i] = xb[bv * 3 + i]; a[i] = xs[tr[0] * 3 + i]; bq[i] = xs[tr[1] * 3 + i]; c[i] = xs[tr[2] * 3 + i]; }
-      // sphere test about the triangle's first corner (its edges are bounded by the distance test itself: cheap rejection)
-      const double r0 = p3[0] - a[0], r1 = p3[1] - a[1], r2 = p3[2] - a[2];
-      const double e0 = bq[0] - a[0], e1 = bq[1] - a[1], e2 = bq[2] - a[2], f0 = c[0] - a[0], f1 = c[1] - a[1], f2 = c[2] - a[2];
-      const double ext = sqrt(fmax(e0 * e0 + e1 * e1 + e2 * e2, f0 * f0 + f1 * f1 + f2 * f2));
-      const double lim = L + ext;
-      if (r0 * r0 + r1 * r1 + r2 * r2 >= lim * lim) continue;
-      pt_closest(p3, a, bq, c, be, d, n);
-      if (d < L) {
-        const int s = atomicAdd(&n_pairs, 1);
-        if (s < kBallMaxPairs) plist[s] = (1 << 30) | (bv << 15) | t;
-      }
+    for (int k = tid; k < cl.nbv * cl.npt; k += NT) {
+      const int bv = cbv[k / cl.npt], t = cpt[k - (k / cl.npt) * cl.npt];
+      if (!ball_pair_far(1, bv, t, xs, xb, bd, L)) list_pair(1, bv, t);
     }
-    // pairs, kind 2: candidate pad edge x candidate ball edge
-    for (int k = tid; k < ncpe * ncbe; k += NT) {
-      const int pe = cpe[k / ncbe], be_ = cbe[k - (k / ncbe) * ncbe];
-      const int* ea = bd.pedge + pe * 2;
-      const int* eb = bd.bedge + be_ * 2;
-      double a0[3], a1[3], b0[3], b1[3];
-      double r2 = 0.0, ha = 0.0, hb = 0.0;
-#pragma unroll
-      for (int i = 0; i < 3; ++i) {
-        a0[i] = xs[ea[0] * 3 + i]; a1[i] = xs[ea[1] * 3 + i]; b0[i] = xb[eb[0] * 3 + i]; b1[i] = xb[eb[1] * 3 + i];
-        const double mi = 0.5 * ((a0[i] + a1[i]) - (b0[i] + b1[i])), hai = 0.5 * (a1[i] - a0[i]), hbi = 0.5 * (b1[i] - b0[i]);
-        r2 += mi * mi; ha += hai * hai; hb += hbi * hbi;
-      }
-      const double lim = L + sqrt(ha) + sqrt(hb);
-      if (r2 >= lim * lim) continue;
-      double sa, tb, d, n[3];
-      ee_closest(a0, a1, b0, b1, sa, tb, d, n);
-      if (d < L) {
-        const int s = atomicAdd(&n_pairs, 1);
-        if (s < kBallMaxPairs) plist[s] = (int)((2u << 30) | ((unsigned)pe << 15) | (unsigned)be_);
-      }
+    for (int k = tid; k < cl.npe * cl.nbe; k += NT) {
+      const int pe = cpe[k / cl.nbe], be_ = cbe[k - (k / cl.nbe) * cl.nbe];
+      if (!ball_pair_far(2, pe, be_, xs, xb, bd, L)) list_pair(2, pe, be_);
     }
     __syncthreads();
     if (n_pairs > kBallMaxPairs) { if (tid == 0) { s_flags |= kBallFlagOverflow; n_pairs = kBallMaxPairs; } }
@@ -735,13 +425,9 @@ __global__ __launch_bounds__(NT_, NT_ >= 512 ? TACEX_BALL_WG_PER_CU : 1) void fe
         D[8] += cb;
         if (fric && take_lag && b1 < 0.0) {  // (inside the ground's barrier zone)
           const int sl = atomicAdd(&n_fric, 1);
-          if (sl < kBallMaxFric) {
-            double* rc = frec + (size_t)sl * kBallRec;
-            rc[0] = -bd.kappa * w * b1 / dhat; rc[1] = 0.0; rc[2] = 0.0; rc[3] = 1.0;
-            rc[4] = rc[5] = rc[6] = rc[7] = 0.0; rc[8] = 1.0; rc[9] = 0.0; rc[10] = 0.0;
-            int* ri = reinterpret_cast<int*>(rc + 11);
-            ri[0] = v; ri[1] = -1; ri[2] = -1;
-          }
+          const double cq0[4] = {0.0, 0.0, 0.0, 0.0}, pco1[3] = {1.0, 0.0, 0.0};
+          const int row1[3] = {v, -1, -1};
+          if (sl < kBallMaxFric) ball_rec_store(frec + (size_t)sl * kBallRec, ball_contact_lambda(bd.kappa, w, b1, dhat), kUp, cq0, pco1, row1);
         }
       }
       cbp[v] = cb;
@@ -768,15 +454,9 @@ __global__ __launch_bounds__(NT_, NT_ >= 512 ? TACEX_BALL_WG_PER_CU : 1) void fe
           const double f = kk * bd.area[k] * b1 / dhat, cb = kk * bd.area[k] * b2 / (dhat * dhat);
           if (fric && take_lag) {
             const int sl = atomicAdd(&n_fric, 1);
-            if (sl < kBallMaxFric) {
-              double* rc = frec + (size_t)sl * kBallRec;
-              rc[0] = -bd.kappa * bd.area[k] * b1 / dhat; rc[1] = 0.0; rc[2] = 0.0; rc[3] = 1.0;
-#pragma unroll
-              for (int a4 = 0; a4 < 4; ++a4) rc[4 + a4] = bd.Y[k * 4 + a4];
-              rc[8] = rc[9] = rc[10] = 0.0;
-              int* ri = reinterpret_cast<int*>(rc + 11);
-              ri[0] = -1; ri[1] = -1; ri[2] = -1;
-            }
+            const double pco0[3] = {0.0, 0.0, 0.0};
+            const int row0[3] = {-1, -1, -1};
+            if (sl < kBallMaxFric) ball_rec_store(frec + (size_t)sl * kBallRec, ball_contact_lambda(bd.kappa, bd.area[k], b1, dhat), kUp, bd.Y + k * 4, pco0, row0);
           }
 #pragma unroll
           for (int a = 0; a < 4; ++a) {
@@ -793,83 +473,32 @@ __global__ __launch_bounds__(NT_, NT_ >= 512 ? TACEX_BALL_WG_PER_CU : 1) void fe
     {
       const int np = n_pairs;
       for (int k = tid; k < np; k += NT) {
-        const unsigned code = (unsigned)plist[k];
-        const int kind = (int)(code >> 30), pi = (int)((code >> 15) & 0x7fff), tj = (int)(code & 0x7fff);
-        double d, n[3], w, cq[4], pco[3];
-        int prow[3];
-        double molg = 0.0, ga[3] = {0.0, 0.0, 0.0}, gbq[3] = {0.0, 0.0, 0.0}, yd[4] = {0.0, 0.0, 0.0, 0.0};  // mollifier's own gradient (edge-edge pairs below the threshold)
-        if (kind == 2) {
-          const int* ea = bd.pedge + pi * 2;
-          const int* eb = bd.bedge + tj * 2;
-          double a0[3], a1[3], b0[3], b1[3], sa, tb, mol, dm, e1[3], e2[3], u[3];
-#pragma unroll
-          for (int i = 0; i < 3; ++i) { a0[i] = xs[ea[0] * 3 + i]; a1[i] = xs[ea[1] * 3 + i]; b0[i] = xb[eb[0] * 3 + i]; b1[i] = xb[eb[1] * 3 + i]; }
-          ee_closest(a0, a1, b0, b1, sa, tb, d, n);
-          if (!(d < dhat)) continue;
-          ee_mollifier(a0, a1, b0, b1, 1e-3 * bd.pelen2[pi] * bd.belen2[tj], mol, dm, e1, e2, u);
-          const double w0 = 0.5 * (bd.pearea[pi] + bd.bearea[tj]);
-          w = w0 * mol;
-#pragma unroll
-          for (int a4 = 0; a4 < 4; ++a4) {
-            cq[a4] = -((1.0 - tb) * bd.Y[eb[0] * 4 + a4] + tb * bd.Y[eb[1] * 4 + a4]);
-            yd[a4] = bd.Y[eb[1] * 4 + a4] - bd.Y[eb[0] * 4 + a4];
-          }
-          prow[0] = ea[0]; prow[1] = ea[1]; prow[2] = -1;
-          pco[0] = 1.0 - sa; pco[1] = sa; pco[2] = 0.0;
-          if (dm > 0.0) {  // grad c = 2 (e2 x u) on a1 (minus on a0), 2 (u x e1) on b1 (minus on b0)
-            molg = w0 * dm;
-            ga[0] = 2.0 * (e2[1] * u[2] - e2[2] * u[1]); ga[1] = 2.0 * (e2[2] * u[0] - e2[0] * u[2]); ga[2] = 2.0 * (e2[0] * u[1] - e2[1] * u[0]);
-            gbq[0] = 2.0 * (u[1] * e1[2] - u[2] * e1[1]); gbq[1] = 2.0 * (u[2] * e1[0] - u[0] * e1[2]); gbq[2] = 2.0 * (u[0] * e1[1] - u[1] * e1[0]);
-          }
-        } else {
-          const int* tr = (kind == 0 ? bd.tri : bd.ptri) + tj * 3;
-          const int t0 = tr[0], t1 = tr[1], t2 = tr[2];
-          double p3[3], a[3], bq[3], c[3], be[3];
-          if (kind == 0) {
-#pragma unroll
-            for (int i = 0; i < 3; ++i) { p3[i] = xs[pi * 3 + i]; a[i] = xb[t0 * 3 + i]; bq[i] = xb[t1 * 3 + i]; c[i] = xb[t2 * 3 + i]; }
-            w = bd.parea[pi];
-          } else {
-#pragma unroll
-            for (int i = 0; i < 3; ++i) { p3[i] = xb[pi * 3 + i]; a[i] = xs[t0 * 3 + i]; bq[i] = xs[t1 * 3 + i]; c[i] = xs[t2 * 3 + i]; }
-            w = bd.area[pi];
-          }
-          pt_closest(p3, a, bq, c, be, d, n);
-          if (kind == 0) {
-#pragma unroll
-            for (int a4 = 0; a4 < 4; ++a4) cq[a4] = -(be[0] * bd.Y[t0 * 4 + a4] + be[1] * bd.Y[t1 * 4 + a4] + be[2] * bd.Y[t2 * 4 + a4]);
-            prow[0] = pi; prow[1] = -1; prow[2] = -1;
-            pco[0] = 1.0; pco[1] = 0.0; pco[2] = 0.0;
-          } else {
-#pragma unroll
-            for (int a4 = 0; a4 < 4; ++a4) cq[a4] = bd.Y[pi * 4 + a4];
-            prow[0] = t0; prow[1] = t1; prow[2] = t2;
-            pco[0] = -be[0]; pco[1] = -be[1]; pco[2] = -be[2];
-          }
-        }
-        if (!(d < dhat) || !(w > 0.0)) continue;
+        int kind, pi, tj;
+        ball_pair_decode(plist[k], kind, pi, tj);
+        BallPairEval pe;  // (LISTED: most of the listed edge pairs are outside d_hat and leave ahead of the mollifier)
+        if (!ball_pair_eval<true>(kind, pi, tj, xs, xb, bd, pe)) continue;
         double bb, b1, b2;
-        barrier3(d / dhat, bb, b1, b2);
-        const double s = kk * w * b1 / dhat, wk = kk * w * b2 / (dhat * dhat);
-        if (molg > 0.0) {
-          const double f = kk * molg * bb;
+        barrier3(pe.d / dhat, bb, b1, b2);
+        const double s = kk * pe.w * b1 / dhat, wk = kk * pe.w * b2 / (dhat * dhat);
+        if (pe.molg > 0.0) {
+          const double f = kk * pe.molg * bb;
 #pragma unroll
           for (int i = 0; i < 3; ++i) {
-            atomicAdd(&vg[prow[0] * 3 + i], -f * ga[i]);
-            atomicAdd(&vg[prow[1] * 3 + i], f * ga[i]);
+            atomicAdd(&vg[pe.prow[0] * 3 + i], -f * pe.ga[i]);
+            atomicAdd(&vg[pe.prow[1] * 3 + i], f * pe.ga[i]);
 #pragma unroll
-            for (int a4 = 0; a4 < 4; ++a4) atomicAdd(&gb[a4 * 3 + i], f * yd[a4] * gbq[i]);
+            for (int a4 = 0; a4 < 4; ++a4) atomicAdd(&gb[a4 * 3 + i], f * pe.yd[a4] * pe.gbq[i]);
           }
         }
         // pad rows
 #pragma unroll
         for (int r = 0; r < 3; ++r) {
-          if (prow[r] < 0) continue;
+          if (pe.prow[r] < 0) continue;
 #pragma unroll
           for (int i = 0; i < 3; ++i) {
-            atomicAdd(&vg[prow[r] * 3 + i], s * pco[r] * n[i]);
+            atomicAdd(&vg[pe.prow[r] * 3 + i], s * pe.pco[r] * pe.n[i]);
 #pragma unroll
-            for (int j = 0; j < 3; ++j) atomicAdd(&Dinv[(size_t)prow[r] * 9 + i * 3 + j], wk * pco[r] * pco[r] * n[i] * n[j]);
+            for (int j = 0; j < 3; ++j) atomicAdd(&Dinv[(size_t)pe.prow[r] * 9 + i * 3 + j], wk * pe.pco[r] * pe.pco[r] * pe.n[i] * pe.n[j]);
           }
         }
         // ball rows
@@ -877,32 +506,18 @@ __global__ __launch_bounds__(NT_, NT_ >= 512 ? TACEX_BALL_WG_PER_CU : 1) void fe
         for (int a4 = 0; a4 < 4; ++a4)
 #pragma unroll
           for (int i = 0; i < 3; ++i) {
-            atomicAdd(&gb[a4 * 3 + i], s * cq[a4] * n[i]);
+            atomicAdd(&gb[a4 * 3 + i], s * pe.cq[a4] * pe.n[i]);
 #pragma unroll
             for (int c4 = 0; c4 < 4; ++c4)
 #pragma unroll
-              for (int j = 0; j < 3; ++j) atomicAdd(&Bm[(a4 * 3 + i) * 12 + c4 * 3 + j], wk * cq[a4] * cq[c4] * n[i] * n[j]);
+              for (int j = 0; j < 3; ++j) atomicAdd(&Bm[(a4 * 3 + i) * 12 + c4 * 3 + j], wk * pe.cq[a4] * pe.cq[c4] * pe.n[i] * pe.n[j]);
           }
         if (take_lag) {
           const int sf = atomicAdd(&n_fric, 1);
-          if (sf < kBallMaxFric) {
-            double* rc = frec + (size_t)sf * kBallRec;
-            rc[0] = -bd.kappa * w * b1 / dhat; rc[1] = n[0]; rc[2] = n[1]; rc[3] = n[2];
-            rc[4] = cq[0]; rc[5] = cq[1]; rc[6] = cq[2]; rc[7] = cq[3];
-            rc[8] = pco[0]; rc[9] = pco[1]; rc[10] = pco[2];
-            int* ri = reinterpret_cast<int*>(rc + 11);
-            ri[0] = prow[0]; ri[1] = prow[1]; ri[2] = prow[2];
-          }
+          if (sf < kBallMaxFric) ball_rec_store(frec + (size_t)sf * kBallRec, ball_contact_lambda(bd.kappa, pe.w, b1, dhat), pe.n, pe.cq, pe.pco, pe.prow);
         }
         const int sl = atomicAdd(&n_act, 1);
-        if (sl < kBallMaxActive) {
-          double* rc = arec + (size_t)sl * kBallRec;
-          rc[0] = wk; rc[1] = n[0]; rc[2] = n[1]; rc[3] = n[2];
-          rc[4] = cq[0]; rc[5] = cq[1]; rc[6] = cq[2]; rc[7] = cq[3];
-          rc[8] = pco[0]; rc[9] = pco[1]; rc[10] = pco[2];
-          int* ri = reinterpret_cast<int*>(rc + 11);
-          ri[0] = prow[0]; ri[1] = prow[1]; ri[2] = prow[2];
-        }
+        if (sl < kBallMaxActive) ball_rec_store(arec + (size_t)sl * kBallRec, wk, pe.n, pe.cq, pe.pco, pe.prow);
       }
     }
     __syncthreads();
@@ -916,13 +531,11 @@ __global__ __launch_bounds__(NT_, NT_ >= 512 ? TACEX_BALL_WG_PER_CU : 1) void fe
       //  that add to one address are served one after the other - 60 records in wave 0 were 45 kcycles of this phase)
       for (int k = (tid & 63) * NWV + (tid >> 6); k < nf; k += NT) {
         const double* rc = frec + (size_t)k * kBallRec;
-        const int* ri = reinterpret_cast<const int*>(rc + 11);
-        double u[3];
+        const int* ri = ball_rec_rows(rc);
+        double u[3], f0, fa, fb;
         fric_u(rc, xs, qs, u);
         const double yv = sqrt(u[0] * u[0] + u[1] * u[1] + u[2] * u[2]);
-        const bool stick = yv < f_eps;
-        const double fa = stick ? 2.0 / f_eps - yv / (f_eps * f_eps) : 1.0 / yv;
-        const double fb = stick ? 2.0 / f_eps - 2.0 * yv / (f_eps * f_eps) : 0.0;
+        ball_fric_law(yv, f_eps, f0, fa, fb);
         const double cf = dt2 * f_mu * rc[0];
         const double iy = yv > 0.0 ? 1.0 / yv : 0.0;
         const double t3[3] = {u[0] * iy, u[1] * iy, u[2] * iy}, n3[3] = {rc[1], rc[2], rc[3]};
@@ -1115,7 +728,7 @@ __global__ __launch_bounds__(NT_, NT_ >= 512 ? TACEX_BALL_WG_PER_CU : 1) void fe
         const int na = n_act;
         for (int k = (tid & 63) * NWV + (tid >> 6); k < na; k += NT) {
           const double* rc = arec + (size_t)k * kBallRec;
-          const int* ri = reinterpret_cast<const int*>(rc + 11);
+          const int* ri = ball_rec_rows(rc);
           const double n0 = rc[1], n1 = rc[2], n2 = rc[3];
           double gp = 0.0;
 #pragma unroll
@@ -1143,7 +756,7 @@ __global__ __launch_bounds__(NT_, NT_ >= 512 ? TACEX_BALL_WG_PER_CU : 1) void fe
         const int nf = n_fric;
         for (int k = (tid & 63) * NWV + (tid >> 6); k < nf; k += NT) {
           const double* rc = frec + (size_t)k * kBallRec;
-          const int* ri = reinterpret_cast<const int*>(rc + 11);
+          const int* ri = ball_rec_rows(rc);
           const double* M = fM + (size_t)k * 6;
           double w3[3] = {0.0, 0.0, 0.0};
 #pragma unroll
@@ -1206,7 +819,7 @@ __global__ __launch_bounds__(NT_, NT_ >= 512 ? TACEX_BALL_WG_PER_CU : 1) void fe
     // ---- step bound ----
     if (tid < 12) rhs12[tid] = dL[V * 3 + tid];
     __syncthreads();
-    ball_points(rhs12, dxb);
+    ball_points(bd, rhs12, dxb, tid, NT);
     __syncthreads();
     double amax = 1.0, vmax = 0.0, dmx = 0.0, dmc = 0.0;
     for (int v = tid; v < V; v += NT) {
@@ -1235,8 +848,8 @@ __global__ __launch_bounds__(NT_, NT_ >= 512 ? TACEX_BALL_WG_PER_CU : 1) void fe
       double al = amax;
       const int np = n_pairs;
       for (int k = tid; k < np; k += NT) {
-        const unsigned code = (unsigned)plist[k];
-        const int kind = (int)(code >> 30), pi = (int)((code >> 15) & 0x7fff), tj = (int)(code & 0x7fff);
+        int kind, pi, tj;
+        ball_pair_decode(plist[k], kind, pi, tj);
         if (kind == 2) {
           const int* ea = bd.pedge + pi * 2;
           const int* eb = bd.bedge + tj * 2;
@@ -1283,7 +896,7 @@ __global__ __launch_bounds__(NT_, NT_ >= 512 ? TACEX_BALL_WG_PER_CU : 1) void fe
       for (int k = tid; k < 3 * V; k += NT) ycl[k] = xs[k] + step * dL[k];  // (the candidate in the idle PCG direction's slot; dL still holds d)
       if (tid < 12) rhs12[tid] = qs[tid] + step * dL[V * 3 + tid];
       __syncthreads();
-      ball_points(rhs12, xbc);
+      ball_points(bd, rhs12, xbc, tid, NT);
       __syncthreads();
       const double Ec = energy(ycl, rhs12, xbc);
       if (Ec <= E0) { E1 = Ec; accepted = true; e_carry = Ec; have_e = true; break; }
@@ -1303,7 +916,7 @@ __global__ __launch_bounds__(NT_, NT_ >= 512 ? TACEX_BALL_WG_PER_CU : 1) void fe
         for (int k = tid; k < 3 * V; k += NT) ycl[k] = xs[k] + mid * dL[k];
         if (tid < 12) rhs12[tid] = qs[tid] + mid * dL[V * 3 + tid];
         __syncthreads();
-        ball_points(rhs12, xbc);
+        ball_points(bd, rhs12, xbc, tid, NT);
         __syncthreads();
         const double Ec = energy(ycl, rhs12, xbc);
         if (Ec <= E0) { lo_s = mid; E1 = Ec; e_carry = Ec; } else { hi_s = mid; }
@@ -1314,7 +927,7 @@ __global__ __launch_bounds__(NT_, NT_ >= 512 ? TACEX_BALL_WG_PER_CU : 1) void fe
       for (int k = tid; k < 3 * V; k += NT) ycl[k] = xs[k] + step * dL[k];
       if (tid < 12) rhs12[tid] = qs[tid] + step * dL[V * 3 + tid];
       __syncthreads();
-      ball_points(rhs12, xbc);
+      ball_points(bd, rhs12, xbc, tid, NT);
       __syncthreads();
     }
     ++n_newton;

@@ -2,12 +2,12 @@
 // env (tacex_fem_ball_contact_forces).
 //
 // What fem_ball_newton_kernel balances and then drops: the force the pad puts on the body, what the ground returns, the shear the pad
-// feels.  Every term is the step's own - the pairs of fem_ball.h (pt_closest, ee_closest, ee_mollifier, barrier3 and the tables of
-// BallDev; rows, coefficients and weights as its pair loop has them), the ground barrier of both bodies, IPC's lagged friction of all of
-// them - evaluated once at (x, q) and reduced per env.  A contact force on a state row is -(1 / dt^2) d/d row of the term's share of the
+// feels.  Every term is the step's own - the pairs, the cull, the friction law and the normal force are the functions of
+// fem_ball_pairs.h that the step calls; the ground barrier of both bodies and IPC's lagged friction of all of them are applied here -
+// evaluated once at (x, q) and reduced per env.  A contact force on a state row is -(1 / dt^2) d/d row of the term's share of the
 // incremental potential, in newtons: what oracle/abd_oracle.py BallScene.gradient adds for these terms, divided by -dt^2.
 #pragma once
-#include "fem_ball.h"
+#include "fem_ball_pairs.h"
 
 namespace tacex {
 
@@ -21,119 +21,15 @@ namespace tacex {
 //   38..40 pad <- ground | 41 / 42 count and smallest gap of the pad's ground contacts (+inf: none) | 43 0
 constexpr int kBallForceSlots = 44;
 
-// One pair of the scene at a state, as the pair loop of fem_ball_newton_kernel evaluates it: its distance is d, the gradient of d over
-// the state rows is pco[r] n on the pad rows prow[r] (-1: unused) and cq[a] n on the body's four rows.
-struct BallPairEval {
-  double d, w, n[3];    // distance, weight (the mollifier included), unit normal
-  double cq[4], pco[3];
-  int prow[3];
-  double cp[3];         // the pad-side closest point
-  double molg;          // w0 m'(c) of a mollified edge-edge pair (0: none); grad c = -ga / +ga on prow[0] / prow[1], yd[a] gbq on the body rows
-  double ga[3], gbq[3], yd[4];
-};
-
-// kind 0: pad surface vertex i x ball triangle j | 1: ball vertex i x pad surface triangle j | 2: pad surface edge i x ball edge j.
-// xs: the env's pad vertices, xb: the body's surface points Y q.  Returns whether the pair is active (d < d_hat, weight > 0).
-__device__ __forceinline__ bool ball_pair_eval(int kind, int i, int j, const double* xs, const double* xb, const BallDev& bd, BallPairEval& e) {
-  e.molg = 0.0;
-#pragma unroll
-  for (int k = 0; k < 3; ++k) { e.ga[k] = 0.0; e.gbq[k] = 0.0; }
-#pragma unroll
-  for (int k = 0; k < 4; ++k) e.yd[k] = 0.0;
-  if (kind == 2) {
-    const int* ea = bd.pedge + i * 2;
-    const int* eb = bd.bedge + j * 2;
-    double a0[3], a1[3], b0[3], b1[3], sa, tb, mol, dm, e1[3], e2[3], u[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) { a0[k] = xs[ea[0] * 3 + k]; a1[k] = xs[ea[1] * 3 + k]; b0[k] = xb[eb[0] * 3 + k]; b1[k] = xb[eb[1] * 3 + k]; }
-    ee_closest(a0, a1, b0, b1, sa, tb, e.d, e.n);
-    ee_mollifier(a0, a1, b0, b1, 1e-3 * bd.pelen2[i] * bd.belen2[j], mol, dm, e1, e2, u);
-    const double w0 = 0.5 * (bd.pearea[i] + bd.bearea[j]);
-    e.w = w0 * mol;
-#pragma unroll
-    for (int a4 = 0; a4 < 4; ++a4) {
-      e.cq[a4] = -((1.0 - tb) * bd.Y[eb[0] * 4 + a4] + tb * bd.Y[eb[1] * 4 + a4]);
-      e.yd[a4] = bd.Y[eb[1] * 4 + a4] - bd.Y[eb[0] * 4 + a4];
-    }
-    e.prow[0] = ea[0]; e.prow[1] = ea[1]; e.prow[2] = -1;
-    e.pco[0] = 1.0 - sa; e.pco[1] = sa; e.pco[2] = 0.0;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) e.cp[k] = (1.0 - sa) * a0[k] + sa * a1[k];
-    if (dm > 0.0) {  // grad c = 2 (e2 x u) on a1 (minus on a0), 2 (u x e1) on b1 (minus on b0)
-      e.molg = w0 * dm;
-      e.ga[0] = 2.0 * (e2[1] * u[2] - e2[2] * u[1]); e.ga[1] = 2.0 * (e2[2] * u[0] - e2[0] * u[2]); e.ga[2] = 2.0 * (e2[0] * u[1] - e2[1] * u[0]);
-      e.gbq[0] = 2.0 * (u[1] * e1[2] - u[2] * e1[1]); e.gbq[1] = 2.0 * (u[2] * e1[0] - u[0] * e1[2]); e.gbq[2] = 2.0 * (u[0] * e1[1] - u[1] * e1[0]);
-    }
-  } else {
-    const int* tr = (kind == 0 ? bd.tri : bd.ptri) + j * 3;
-    const int t0 = tr[0], t1 = tr[1], t2 = tr[2];
-    double p3[3], a[3], bq[3], c[3], be[3];
-    if (kind == 0) {
-#pragma unroll
-      for (int k = 0; k < 3; ++k) { p3[k] = xs[i * 3 + k]; a[k] = xb[t0 * 3 + k]; bq[k] = xb[t1 * 3 + k]; c[k] = xb[t2 * 3 + k]; }
-      e.w = bd.parea[i];
-    } else {
-#pragma unroll
-      for (int k = 0; k < 3; ++k) { p3[k] = xb[i * 3 + k]; a[k] = xs[t0 * 3 + k]; bq[k] = xs[t1 * 3 + k]; c[k] = xs[t2 * 3 + k]; }
-      e.w = bd.area[i];
-    }
-    pt_closest(p3, a, bq, c, be, e.d, e.n);
-    if (kind == 0) {
-#pragma unroll
-      for (int a4 = 0; a4 < 4; ++a4) e.cq[a4] = -(be[0] * bd.Y[t0 * 4 + a4] + be[1] * bd.Y[t1 * 4 + a4] + be[2] * bd.Y[t2 * 4 + a4]);
-      e.prow[0] = i; e.prow[1] = -1; e.prow[2] = -1;
-      e.pco[0] = 1.0; e.pco[1] = 0.0; e.pco[2] = 0.0;
-#pragma unroll
-      for (int k = 0; k < 3; ++k) e.cp[k] = p3[k];
-    } else {
-#pragma unroll
-      for (int a4 = 0; a4 < 4; ++a4) e.cq[a4] = bd.Y[i * 4 + a4];
-      e.prow[0] = t0; e.prow[1] = t1; e.prow[2] = t2;
-      e.pco[0] = -be[0]; e.pco[1] = -be[1]; e.pco[2] = -be[2];
-#pragma unroll
-      for (int k = 0; k < 3; ++k) e.cp[k] = be[0] * a[k] + be[1] * bq[k] + be[2] * c[k];
-    }
-  }
-  return e.d < bd.dhat && e.w > 0.0;
-}
-
-// cheap rejection ahead of ball_pair_eval: true when the pair cannot be closer than L (spheres about a triangle's first corner / the edges' mid points)
-__device__ __forceinline__ bool ball_pair_far(int kind, int i, int j, const double* xs, const double* xb, const BallDev& bd, double L) {
-  if (kind == 2) {
-    const int* ea = bd.pedge + i * 2;
-    const int* eb = bd.bedge + j * 2;
-    double r2 = 0.0, ha = 0.0, hb = 0.0;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      const double a0 = xs[ea[0] * 3 + k], a1 = xs[ea[1] * 3 + k], b0 = xb[eb[0] * 3 + k], b1 = xb[eb[1] * 3 + k];
-      const double mi = 0.5 * ((a0 + a1) - (b0 + b1)), hai = 0.5 * (a1 - a0), hbi = 0.5 * (b1 - b0);
-      r2 += mi * mi; ha += hai * hai; hb += hbi * hbi;
-    }
-    const double lim = L + sqrt(ha) + sqrt(hb);
-    return r2 >= lim * lim;
-  }
-  const double* P = kind == 0 ? xs : xb;  // the point's array; the triangle lives in the other
-  const double* Q = kind == 0 ? xb : xs;
-  const int* tr = (kind == 0 ? bd.tri : bd.ptri) + j * 3;
-  double r2 = 0.0, e2 = 0.0, f2 = 0.0;
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    const double a = Q[tr[0] * 3 + k], r = P[i * 3 + k] - a, e = Q[tr[1] * 3 + k] - a, f = Q[tr[2] * 3 + k] - a;
-    r2 += r * r; e2 += e * e; f2 += f * f;
-  }
-  const double lim = L + sqrt(fmax(e2, f2));
-  return r2 >= lim * lim;
-}
-
 // One workgroup per env, 256 threads, one launch.  Pass 0 stands at (x, q): barrier forces of the pairs and of the ground.  Pass 1 (friction)
 // stands at the state the last step started from, (x_prev, q_lag): every active pair and ground contact THERE is a lagged contact (lam, n and
 // the coefficients frozen, what take_lag stores in fem_ball_newton_kernel), its friction force at (x, q) follows at once from the sliding
 // since then - no record is kept.  The pad rows slide from x_prev, the body rows by q - q_ref (q_ref: q_lag for a free body, the pose
 // the step measured the body's motion from for a kinematic one; null: not at all).  A NaN in the env's q_lag row: its friction reference was cleared (tacex_fem_ball_reset_envs), no friction.
-// Both passes cull as the step does, at reach d_hat (no CCD here): the ball's bounding sphere about p, the pad's surface vertices /
-// triangles / edges within reach, the ball's side within the candidates' bounding box; lists in LDS, capacity kBallMaxCand, an overflow
-// sets kBallFlagOverflow in slot 11.  Slots are handed out with LDS atomics (the order of the candidates, and with it the order of a
-// thread's partial sums, varies between runs): results agree to round-off, not bit for bit.
+// Both passes cull with the step's ball_cull, at reach d_hat (no CCD here) and with the ball triangles tested by their corners' bounding
+// box (the step has their spheres at hand); lists in LDS, capacity kBallMaxCand, an overflow sets kBallFlagOverflow in slot 11.  Slots are
+// handed out with LDS atomics (the order of the candidates, and with it the order of a thread's partial sums, varies between runs):
+// results agree to round-off, not bit for bit.
 // Reduction: per-thread partial sums, a wave butterfly, the four waves added in wave order through LDS.  The optional per-vertex forces
 // accumulate in LDS (f64 atomic adds) and are written once.
 // dynamic LDS: ball surface points (nv,3) | per-vertex forces (V,3) when vforce is given (ball_force_lds_bytes)
@@ -154,7 +50,7 @@ __global__ __launch_bounds__(256) void fem_ball_contact_forces_kernel(BallDev bd
   __shared__ unsigned short cbv[kBallMaxCand], cbt[kBallMaxCand], cbe[kBallMaxCand];  // candidate ball vertices / triangles / edges
   constexpr int NT = 256;
   const int b = blockIdx.x, tid = threadIdx.x;
-  const int nv = bd.nv, nt = bd.nt;
+  const int nv = bd.nv;
   const size_t o = (size_t)b * V * 3;
   const double* x = xg + o;
   const double* xprev = xprevg ? xprevg + o : nullptr;
@@ -203,10 +99,9 @@ __global__ __launch_bounds__(256) void fem_ball_contact_forces_kernel(BallDev bd
   };
   // friction force per unit coefficient of a lagged contact (lam, n) whose rows slid by rel: -mu lam f1(|u|) / |u| u, u the tangential part
   auto friction = [&](double lam, const double n[3], const double rel[3], double ff[3]) {
-    const double rn = rel[0] * n[0] + rel[1] * n[1] + rel[2] * n[2];
-    const double u[3] = {rel[0] - rn * n[0], rel[1] - rn * n[1], rel[2] - rn * n[2]};
-    const double yv = sqrt(u[0] * u[0] + u[1] * u[1] + u[2] * u[2]);
-    const double fa = yv < fric_eps ? 2.0 / fric_eps - yv / (fric_eps * fric_eps) : 1.0 / yv;
+    double u[3], f0, fa, fb;
+    ball_tangential(rel, n, u);
+    ball_fric_law(sqrt(u[0] * u[0] + u[1] * u[1] + u[2] * u[2]), fric_eps, f0, fa, fb);
 #pragma unroll
     for (int k = 0; k < 3; ++k) ff[k] = -fric_mu * lam * fa * u[k];
   };
@@ -216,12 +111,7 @@ __global__ __launch_bounds__(256) void fem_ball_contact_forces_kernel(BallDev bd
     const double* xp = pass ? xprev : x;   // the state the pass stands at
     const double* qq = pass ? qls : qs;
     __syncthreads();  // (the previous pass no longer reads xb and the lists)
-    for (int k = tid; k < nv; k += NT) {
-      const double y0 = bd.Y[k * 4], y1 = bd.Y[k * 4 + 1], y2 = bd.Y[k * 4 + 2], y3 = bd.Y[k * 4 + 3];
-#pragma unroll
-      for (int i = 0; i < 3; ++i) xb[k * 3 + i] = y0 * qq[i] + y1 * qq[3 + i] + y2 * qq[6 + i] + y3 * qq[9 + i];
-    }
-    if (tid == 0) { n_cpv = 0; n_cpt = 0; n_cpe = 0; n_cbv = 0; n_cbt = 0; n_cbe = 0; }
+    ball_points(bd, qq, xb, tid, NT);
     __syncthreads();
     // ---- ground, both bodies (fem_ball.h: the nodal gradient's ground part and its lag) ----
     if (bd.ground) {
@@ -231,7 +121,7 @@ __global__ __launch_bounds__(256) void fem_ball_contact_forces_kernel(BallDev bd
         if (!(gap > 0.0 && gap < dhat)) continue;
         double bb, b1, b2;
         barrier3(gap / dhat, bb, b1, b2);
-        const double lam = -kap * w * b1 / dhat;
+        const double lam = ball_contact_lambda(kap, w, b1, dhat);
         if (pass == 0) {
           const double f[3] = {0.0, 0.0, lam};
           acc[40] += lam; acc[41] += 1.0;
@@ -251,7 +141,7 @@ __global__ __launch_bounds__(256) void fem_ball_contact_forces_kernel(BallDev bd
         if (!(gap > 0.0 && gap < dhat)) continue;
         double bb, b1, b2;
         barrier3(gap / dhat, bb, b1, b2);
-        const double lam = -kap * bd.area[k] * b1 / dhat;
+        const double lam = ball_contact_lambda(kap, bd.area[k], b1, dhat);
         double f[3] = {0.0, 0.0, lam};
         if (pass == 0) {
           acc[34] += lam; acc[35] += lam; acc[36] += 1.0;
@@ -272,76 +162,9 @@ __global__ __launch_bounds__(256) void fem_ball_contact_forces_kernel(BallDev bd
           for (int i = 0; i < 3; ++i) acc[20 + a4 * 3 + i] += bd.Y[k * 4 + a4] * f[i];
       }
     }
-    // ---- candidates (fem_ball.h: the lists of an iteration, here at reach d_hat) ----
-    double rb = 0.0;  // bounding radius of the ball about p
-    for (int k = tid; k < nv; k += NT) {
-      const double r0 = xb[k * 3] - qq[0], r1 = xb[k * 3 + 1] - qq[1], r2 = xb[k * 3 + 2] - qq[2];
-      rb = fmax(rb, sqrt(r0 * r0 + r1 * r1 + r2 * r2));
-    }
-    rb = block_sum_max(rb, sh);
-    for (int k = tid; k < bd.nsv; k += NT) {
-      const int v = bd.psv[k];
-      const double r0 = xp[v * 3] - qq[0], r1 = xp[v * 3 + 1] - qq[1], r2 = xp[v * 3 + 2] - qq[2];
-      const double lim = rb + L;
-      if (r0 * r0 + r1 * r1 + r2 * r2 < lim * lim) {
-        const int s = atomicAdd(&n_cpv, 1);
-        if (s < kBallMaxCand) cpv[s] = (unsigned short)v;
-      }
-    }
-    for (int k = tid; k < bd.npt; k += NT) {
-      const int* tr = bd.ptri + k * 3;
-      double c3[3], rt = 0.0;
-#pragma unroll
-      for (int i = 0; i < 3; ++i) c3[i] = (xp[tr[0] * 3 + i] + xp[tr[1] * 3 + i] + xp[tr[2] * 3 + i]) * (1.0 / 3.0);
-#pragma unroll
-      for (int j = 0; j < 3; ++j) {
-        const double r0 = xp[tr[j] * 3] - c3[0], r1 = xp[tr[j] * 3 + 1] - c3[1], r2 = xp[tr[j] * 3 + 2] - c3[2];
-        rt = fmax(rt, sqrt(r0 * r0 + r1 * r1 + r2 * r2));
-      }
-      const double r0 = c3[0] - qq[0], r1 = c3[1] - qq[1], r2 = c3[2] - qq[2];
-      const double lim = rb + L + rt;
-      if (r0 * r0 + r1 * r1 + r2 * r2 < lim * lim) {
-        const int s = atomicAdd(&n_cpt, 1);
-        if (s < kBallMaxCand) cpt[s] = (unsigned short)k;
-      }
-    }
-    if (bd.ee)
-      for (int k = tid; k < bd.npe; k += NT) {
-        const int* ed = bd.pedge + k * 2;
-        double r2 = 0.0, h2 = 0.0;
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-          const double mi = 0.5 * (xp[ed[0] * 3 + i] + xp[ed[1] * 3 + i]) - qq[i], hi = 0.5 * (xp[ed[1] * 3 + i] - xp[ed[0] * 3 + i]);
-          r2 += mi * mi; h2 += hi * hi;
-        }
-        const double lim = rb + L + sqrt(h2);
-        if (r2 < lim * lim) {
-          const int s = atomicAdd(&n_cpe, 1);
-          if (s < kBallMaxCand) cpe[s] = (unsigned short)k;
-        }
-      }
-    __syncthreads();
-    if (n_cpv > kBallMaxCand || n_cpt > kBallMaxCand || n_cpe > kBallMaxCand) { if (tid == 0) s_flags |= kBallFlagOverflow; }
-    const int ncpv = min(n_cpv, kBallMaxCand), ncpt = min(n_cpt, kBallMaxCand), ncpe = min(n_cpe, kBallMaxCand);
-    // the ball's side: what lies within L of the bounding box of the pad's candidates
-    double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-    auto grow = [&](int v) {
-#pragma unroll
-      for (int i = 0; i < 3; ++i) { lo[i] = fmin(lo[i], xp[v * 3 + i]); hi[i] = fmax(hi[i], xp[v * 3 + i]); }
-    };
-    for (int k = tid; k < ncpv; k += NT) grow(cpv[k]);
-    for (int k = tid; k < ncpt; k += NT) { const int* tr = bd.ptri + cpt[k] * 3; grow(tr[0]); grow(tr[1]); grow(tr[2]); }
-    for (int k = tid; k < ncpe; k += NT) { const int* ed = bd.pedge + cpe[k] * 2; grow(ed[0]); grow(ed[1]); }
-#pragma unroll
-    for (int i = 0; i < 3; ++i) { lo[i] = -block_sum_max(-lo[i], sh) - L; hi[i] = block_sum_max(hi[i], sh) + L; }
-    for (int k = tid; k < nv; k += NT) {
-      const double p0 = xb[k * 3], p1 = xb[k * 3 + 1], p2 = xb[k * 3 + 2];
-      if (p0 >= lo[0] && p0 <= hi[0] && p1 >= lo[1] && p1 <= hi[1] && p2 >= lo[2] && p2 <= hi[2]) {
-        const int sl = atomicAdd(&n_cbv, 1);
-        if (sl < kBallMaxCand) cbv[sl] = (unsigned short)k;
-      }
-    }
-    for (int t = tid; t < nt; t += NT) {
+    // ---- candidates at reach d_hat; a ball triangle by the bounding box of its corners ----
+    BallCull cl = {cpv, cpt, cpe, cbv, cbt, cbe, &n_cpv, &n_cpt, &n_cpe, &n_cbv, &n_cbt, &n_cbe, &s_flags};
+    ball_cull<NT>(bd, cl, xp, qq, xb, L, sh, tid, [&](int t, const double* lo, const double* hi) __attribute__((always_inline)) {
       const int* tr = bd.tri + t * 3;
       bool in = true;
 #pragma unroll
@@ -349,41 +172,21 @@ __global__ __launch_bounds__(256) void fem_ball_contact_forces_kernel(BallDev bd
         const double a = xb[tr[0] * 3 + i], b2 = xb[tr[1] * 3 + i], c2 = xb[tr[2] * 3 + i];
         in = in && fmax(a, fmax(b2, c2)) >= lo[i] && fmin(a, fmin(b2, c2)) <= hi[i];
       }
-      if (in) {
-        const int sl = atomicAdd(&n_cbt, 1);
-        if (sl < kBallMaxCand) cbt[sl] = (unsigned short)t;
-      }
-    }
-    if (bd.ee)
-      for (int k = tid; k < bd.nbe; k += NT) {
-        const int* eb = bd.bedge + k * 2;
-        bool in = true;
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-          const double a = xb[eb[0] * 3 + i], b2 = xb[eb[1] * 3 + i];
-          in = in && fmax(a, b2) >= lo[i] && fmin(a, b2) <= hi[i];
-        }
-        if (in) {
-          const int sl = atomicAdd(&n_cbe, 1);
-          if (sl < kBallMaxCand) cbe[sl] = (unsigned short)k;
-        }
-      }
-    __syncthreads();
-    if (n_cbv > kBallMaxCand || n_cbt > kBallMaxCand || n_cbe > kBallMaxCand) { if (tid == 0) s_flags |= kBallFlagOverflow; }
-    const int ncbv = min(n_cbv, kBallMaxCand), ncbt = min(n_cbt, kBallMaxCand), ncbe = min(n_cbe, kBallMaxCand);
-    // ---- pairs of the three kinds over the candidates' products (fem_ball.h: "pairs at x") ----
-    const int n0 = ncpv * ncbt, n1 = ncbv * ncpt, n2 = bd.ee ? ncpe * ncbe : 0;
+      return in;
+    });
+    // ---- pairs of the three kinds over the candidates' products, one strided loop ----
+    const int n0 = cl.npv * cl.nbt, n1 = cl.nbv * cl.npt, n2 = bd.ee ? cl.npe * cl.nbe : 0;
     for (int k = tid; k < n0 + n1 + n2; k += NT) {
       int kind, i, j;
-      if (k < n0) { kind = 0; i = cpv[k / ncbt]; j = cbt[k % ncbt]; }
-      else if (k < n0 + n1) { const int r = k - n0; kind = 1; i = cbv[r / ncpt]; j = cpt[r % ncpt]; }
-      else { const int r = k - n0 - n1; kind = 2; i = cpe[r / ncbe]; j = cbe[r % ncbe]; }
+      if (k < n0) { kind = 0; i = cpv[k / cl.nbt]; j = cbt[k % cl.nbt]; }
+      else if (k < n0 + n1) { const int r = k - n0; kind = 1; i = cbv[r / cl.npt]; j = cpt[r % cl.npt]; }
+      else { const int r = k - n0 - n1; kind = 2; i = cpe[r / cl.nbe]; j = cbe[r % cl.nbe]; }
       if (ball_pair_far(kind, i, j, xp, xb, bd, L)) continue;
       BallPairEval e;
-      if (!ball_pair_eval(kind, i, j, xp, xb, bd, e)) continue;
+      if (!ball_pair_eval<false>(kind, i, j, xp, xb, bd, e)) continue;
       double bb, b1, b2;
       barrier3(e.d / dhat, bb, b1, b2);
-      const double lam = -kap * e.w * b1 / dhat;
+      const double lam = ball_contact_lambda(kap, e.w, b1, dhat);
       double fu[3];  // the force per unit coefficient: lam n (barrier) or the friction force of the lagged contact
       if (pass == 0) {
 #pragma unroll
