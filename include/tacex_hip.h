@@ -1141,6 +1141,64 @@ int tacex_height_map_from_sdf(const float* voxels_dev, int num_voxels, const int
                               float gelpad_to_camera_min_distance_m, float* hm_mm_dev, float* frame_min_dev, float* indent_mm_dev,
                               int32_t* frame_rows_dev, int num_frames, int height, int width, void* stream);
 
+/* Scenes of signed-distance volumes as a height-map source: every env holds K = num_slots (1..8) SLOTS, each a volume of the library of
+ * tacex_height_map_from_sdf under its own pose, folded into one field by union, subtraction and intersection during the march
+ * (tacex_amd/csrc/sdf_scene.hip).  Library, projection, float32 arithmetic ("each operation rounded on its own, in the order of the
+ * parentheses"), clip planes, max_steps, tol_mm, the outputs besides hm and the two launches are those of tacex_height_map_from_sdf;
+ * sqrt is the correctly rounded root.  The caller writes three tensors in place between steps:
+ *   part_ids_dev (B,K) int32: the slot's volume;   part_ops_dev (B,K) int32: 0 union, 1 subtract, 2 intersect;
+ *   part_pose_dev (B,K,16) f32: the pose row of tacex_height_map_from_sdf, with [14] blend_mm (>= 0) and [15] 0 (not read).
+ * Per slot: g, inv, vox, ax, ay, az, q0, par, ia, hmax as in tacex_height_map_from_sdf from the slot's pose row and volume row, and
+ *   blend = r[14].  The slot is EMPTY - the library is not read for it - when its id is outside [0, P), its op outside 0..2, unless
+ *   |blend| < 2^30, or when the volume row or the pose fail the checks of tacex_height_map_from_sdf.
+ *   vox_env = the smallest vox over the env's non-empty union slots (2^30 when there is none).
+ * Per 32 x 8 TILE of the frame (tile column tc, tile row tr) a non-empty slot is LIVE when its op is intersect, or when the image of
+ * its grid's box meets the tile: over the eight corners c (bit 0, 1, 2 of c choose 0 or hmax[a] on axis a = 0, 1, 2)
+ *     o[a] = (corner[a] - anchor[a])*vox     X = (((r[0]*o[0]) + (r[1]*o[1])) + (r[2]*o[2])) + tx     Y likewise with r[3..5], ty
+ *     xmin, xmax, ymin, ymax: the smallest and largest X and Y;     margin = blend > 0 ? pixmm + blend : pixmm
+ *     x0 = float(32*tc)*pixmm   x1 = float(32*tc + 31)*pixmm   y0 = float(8*tr)*pixmm   y1 = float(8*tr + 7)*pixmm
+ *     live = xmax + margin >= x0 && xmin - margin <= x1 && ymax + margin >= y0 && ymin - margin <= y1
+ *   (a union or subtraction whose box is further than its blend width from every ray of the tile cannot be hit there; an
+ *   intersection with a part that is absent leaves nothing, so it is never dropped).  Slots that are not live do not exist for the
+ *   tile's pixels.  A tile without a live union slot is far clip, and reads no voxel.
+ * Per pixel and live slot s: b_s[a] as b[a] in tacex_height_map_from_sdf, and [lo_s, hi_s] by its clipping from lo = near_clip,
+ *   hi = far_clip; meets_s = the interval is not empty, lo_s <= hi_s and all |b_s[a]| < 2^30.
+ *   The pixel's interval is lo = the smallest lo_s, hi = the largest hi_s over the live UNION slots with meets_s; without one the
+ *   pixel is far clip and reads no voxel.  Subtract and intersect slots never extend it.
+ * The field f at depth z is a left fold over the live slots in slot order, from f = 2^30:
+ *     q[a] = b_s[a] + (z*az[a]);  c[a], m[a], w[a] and the tap s(c) at the clamped point as in tacex_height_map_from_sdf;  x[a] = q[a] - c[a]
+ *     inside = meets_s && z >= lo_s && z <= hi_s
+ *     inside:   u = ((s(c) - level)*scale)*step_scale
+ *     else      e2 = (((x[0]*x[0]) + (x[1]*x[1])) + (x[2]*x[2]))*(vox*vox)                    squared distance to the box [mm^2]
+ *               p = ((s(c) - level)*scale)*step_scale;  p = p > 0 ? p : 0;  u = sqrt(e2 + (p*p))
+ *       (for a surface inside its convex box a lower bound of the distance: |P-Q|^2 >= |P-C|^2 + |C-Q|^2 for the projection C of P;
+ *       equal to the tap on the faces up to rounding, growing with the distance from the box)
+ *     min(a, b) = b < a ? b : a;     smin_k(a, b) = min(a, b), and for k > 0:
+ *               t = k - |a - b|;  t = t > 0 ? t : 0;  h = t/k;  smin_k(a, b) = min(a, b) - ((h*h)*(k*0.25f))
+ *     union: f = smin_blend(f, u)     subtract: f = -smin_blend(-f, u)     intersect: f = -smin_blend(-f, -u)
+ *   (A union slot with blend not > 0 that is not inside and has sqrt(e2) >= f cannot change f; the kernel skips its tap.)
+ * marching:  z = lo;  for n = 0 .. max_steps-1:
+ *     if f(z) < tol_mm:  depth = z, done
+ *     z = z + f(z)
+ *     if !(z <= hi):  depth = far_clip, done
+ *     if n == max_steps-1:  depth = f(z before the step) < vox_env ? z : far_clip                          the grazing-ray rule
+ *   hm = depth < far_clip ? depth : far_clip
+ * A scene whose only non-empty slot is slot 0, a union with blend 0, gives the bits of tacex_height_map_from_sdf for that volume and
+ * pose in hm, frame_min, indent and the ranges: the one slot is live wherever a ray meets its box, every marched point is inside
+ * (z stays in [lo_s, hi_s]), and min(2^30, u) takes the steps u takes.
+ * All three operations are 1-Lipschitz in 1-Lipschitz arguments, so the march never steps past the folded surface.  No atomics and
+ * no dependence on the batch: the same inputs give the same bits on every call, alone or in a batch.
+ * Returns 2 before any HIP call, writing nothing, for a NULL voxels_dev, volumes_i_dev, volumes_f_dev, part_ids_dev, part_pose_dev,
+ * part_ops_dev, hm_mm_dev or frame_min_dev, num_voxels, num_volumes, num_frames, height or width <= 0, num_slots outside 1..8,
+ * width % 4 != 0, height or width above 2048, more tiles than one launch takes, pixmm not > 0, max_steps outside 1..128, tol_mm not
+ * > 0, near_clip_mm >= far_clip_mm (or a NaN), and an hm_mm_dev that is not 16-byte aligned.  The call was added without a change of
+ * TACEX_ABI_VERSION (no existing signature or struct moved): a caller detects it by looking the symbol up, not by the version. */
+int tacex_height_map_from_sdf_scene(const float* voxels_dev, int num_voxels, const int32_t* volumes_i_dev, const float* volumes_f_dev,
+                                    int num_volumes, const int32_t* part_ids_dev, const float* part_pose_dev, const int32_t* part_ops_dev,
+                                    int num_slots, float pixmm, float near_clip_mm, float far_clip_mm, int max_steps, float tol_mm,
+                                    float gelpad_height_m, float gelpad_to_camera_min_distance_m, float* hm_mm_dev, float* frame_min_dev,
+                                    float* indent_mm_dev, int32_t* frame_rows_dev, int num_frames, int height, int width, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

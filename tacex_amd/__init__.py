@@ -9,7 +9,8 @@ from .gelsight_sensor_group import GelSightSensorGroup
 from .height_map_source import AffineBodyDepthSource, FemSurfaceDepthSource, FemTractionImage, IndenterHeightMapSource, MeshDepthSource, MeshLibraryDepthSource
 from .lens_model import LensProfile, TactileLensModel
 from .relief_source import ReliefHeightMapSource, ReliefTile
+from .sdf_scene import SdfSceneSource
 from .volume_source import SdfVolume, SdfVolumeSource
 
 __all__ = ["AffineBodyDepthSource", "CameraProfile", "ContactField", "ContactGel", "GelMemoryProfile", "GelSightSensor", "GelSightSensorCfg", "GelSightSensorData", "GelSightSensorGroup", "FemSurfaceDepthSource", "FemTractionImage", "IndenterHeightMapSource", "LensProfile", "MeshDepthSource",
-           "MeshLibraryDepthSource", "ReliefHeightMapSource", "ReliefTile", "SdfVolume", "SdfVolumeSource", "TactileCameraModel", "TactileContactModel", "TactileGelMemory", "TactileLensModel", "slip_from_fots"]
+           "MeshLibraryDepthSource", "ReliefHeightMapSource", "ReliefTile", "SdfSceneSource", "SdfVolume", "SdfVolumeSource", "TactileCameraModel", "TactileContactModel", "TactileGelMemory", "TactileLensModel", "slip_from_fots"]

@@ -17,7 +17,7 @@ _TAG = os.environ.get("TACEX_LIB_TAG", "")
 LIB = PKG / (f"libtacex_hip.{_TAG}.so" if _TAG else "libtacex_hip.so")
 STAMP = PKG / (LIB.name + ".stamp")
 _FLAGS_FILE = PKG / f"libtacex_hip.{_TAG}.flags"
-SOURCES = ["taxim_kernels.hip", "taxim_mfma.hip", "taxim_tail.hip", "taxim_stream.hip", "taxim_shadow.hip", "fots_kernels.hip", "fem_kernels.hip", "depth_raster.hip", "camera_model.hip", "lens_model.hip", "contact_field.hip", "gel_memory.hip", "relief_source.hip", "volume_source.hip", "tacex_capi.hip"]
+SOURCES = ["taxim_kernels.hip", "taxim_mfma.hip", "taxim_tail.hip", "taxim_stream.hip", "taxim_shadow.hip", "fots_kernels.hip", "fem_kernels.hip", "depth_raster.hip", "camera_model.hip", "lens_model.hip", "contact_field.hip", "gel_memory.hip", "relief_source.hip", "volume_source.hip", "sdf_scene.hip", "tacex_capi.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=fast", "-Wno-unused-result"]
 # A/B hook for kernel tuning macros, e.g. TACEX_EXTRA_HIPCC_FLAGS="-DTACEX_MFMA_CH=2" (part of the build digest)
 _STREAM_DEFAULT = "-mllvm -amdgpu-sched-strategy=max-memory-clause"
@@ -48,7 +48,9 @@ FILE_FLAGS = {"taxim_stream.hip": ["-fno-slp-vectorize"] + _stream_flags.split()
               # the relief source: every product and sum of its per-sample contract on its own, as tests/relief_source_ref.py restates it
               "relief_source.hip": ["-ffp-contract=off"],
               # the SDF volume source: every operation of its ray march on its own, as tests/volume_source_ref.py restates it
-              "volume_source.hip": ["-ffp-contract=off"]}
+              "volume_source.hip": ["-ffp-contract=off"],
+              # the SDF scene source: the same taps folded over several parts, as tests/sdf_scene_ref.py restates it
+              "sdf_scene.hip": ["-ffp-contract=off"]}
 
 
 def _hipcc() -> str:

@@ -186,6 +186,7 @@ SIGNATURES = {
     "tacex_gel_memory": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _f, _f, _f, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "tacex_height_map_from_relief": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _f, _f, _f, _f, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "tacex_height_map_from_sdf": (_i, [_vp, _i, _vp, _vp, _i, _vp, _vp, _f, _f, _f, _i, _f, _f, _f, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
+    "tacex_height_map_from_sdf_scene": (_i, [_vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _i, _f, _f, _f, _i, _f, _f, _f, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
 }
 
 _lib = None

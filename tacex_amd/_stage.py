@@ -1,7 +1,7 @@
 """What the per-env stages of the optical path share (camera_model, lens_model, contact_field, gel_memory): the profile table with
 its ids, the check of a tensor argument, and the constructor preamble.  A stage keeps its own profile class, its own arguments and
 its one launch; DESIGN.md 4.0.12a.4 says how a new stage uses these pieces.  `LibrarySource` is the base of the height-map sources
-that press one entry of a library per env (relief_source, volume_source)."""
+that press one entry of a library per env (relief_source, volume_source) or several (sdf_scene)."""
 from __future__ import annotations
 
 import math
@@ -152,13 +152,17 @@ class LibrarySource:
             arg("indent", indent, (B,))
         if rows is not None:
             arg("rows", rows, (B, 4), torch.int32)
-        arg("pose", self.pose, (B, 16), must="must stay")
+        self._check_pose(arg)
         ints = arg(table_i, getattr(self, table_i), (P, 4), torch.int32, must="must stay")
         data = arg(payload, getattr(self, payload), ("N",), must="must stay")
         ids, floats = self._table.check()
         arg(rows_name, floats, (P, self._table.width), must="must stay")
         self._launch(data, ints, floats, ids, hm, frame_min, indent, rows, float(gelpad_height), float(gelpad_to_camera_min_distance))
         return hm
+
+    def _check_pose(self, arg):
+        """The tensors the caller writes in place besides the ids, as `fill` needs them (a source with several poses per env has its own)."""
+        arg("pose", self.pose, (self.num_envs, 16), must="must stay")
 
     def _launch(self, data, ints, floats, ids, hm, frame_min, indent, rows, gelpad_height, gelpad_to_camera_min_distance):
         raise NotImplementedError

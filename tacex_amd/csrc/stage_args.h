@@ -1,5 +1,5 @@
 // What the per-env stages of the optical path and the library height-map sources share on the C side (camera_model.hip,
-// lens_model.hip, contact_field.hip, gel_memory.hip, relief_source.hip, volume_source.hip): the refusals every entry point opens with, the launch geometry of "blocks stay inside one frame", and the
+// lens_model.hip, contact_field.hip, gel_memory.hip, relief_source.hip, volume_source.hip, sdf_scene.hip): the refusals every entry point opens with, the launch geometry of "blocks stay inside one frame", and the
 // lookup of a frame's row in a profile table.  No arithmetic lives here: the four units are pinned bit for bit on their own.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -23,7 +23,7 @@ inline bool not_positive(const char* fn, const char* name, int v) {
   return true;
 }
 
-// The height-map sources whose frame outputs come from the row kernel's statements (relief_source.hip, volume_source.hip): a frame
+// The height-map sources whose frame outputs come from the row kernel's statements (relief_source.hip, volume_source.hip, sdf_scene.hip): a frame
 // of whole float4 groups whose row and column minima fit LDS, and a map that float4 stores may write.
 inline bool not_frame_rows_geometry(const char* fn, int height, int width) {
   if (width % 4 != 0) { set_error("%s: width = %d (must be a multiple of 4)", fn, width); return true; }

@@ -13,14 +13,12 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "sdf_tap.h"
 #include "stage_args.h"
 #include "tacex_internal.h"
 
 namespace tacex {
 namespace {
-
-constexpr int kSdfTileW = 32, kSdfTileH = 8;  // 2 x 2 waves of 16 x 4 pixels
-constexpr float kSdfTwo30 = 1073741824.0f;
 
 struct SdfArgs {
   const float* voxels;  // all grids back to back
@@ -33,8 +31,6 @@ struct SdfArgs {
   float pixmm, near_clip, far_clip, tol;
 };
 
-__device__ __forceinline__ float sdf_lerp(float p, float q, float t) { return p + (t * (q - p)); }
-
 __global__ __launch_bounds__(256) void sdf_height_map_kernel(SdfArgs a) {
   const int b = (int)(blockIdx.x / (unsigned)a.tiles), tile = (int)(blockIdx.x - (unsigned)b * (unsigned)a.tiles);
   const int tr = tile / a.tiles_x, tc = tile - tr * a.tiles_x;
@@ -44,42 +40,12 @@ __global__ __launch_bounds__(256) void sdf_height_map_kernel(SdfArgs a) {
   const bool in_frame = x < a.W && y < a.H;
   const float far_clip = a.far_clip;
 
-  // the frame's volume, pose and ray coefficients (blockIdx alone)
-  const int id = a.ids ? a.ids[b] : 0;
-  bool none = !(id >= 0 && id < a.P);  // no such volume: far clip everywhere, the library is not touched
-  int first = 0, N[3] = {2, 2, 2};
-  float pitch = 0.f, anchor[3] = {0.f, 0.f, 0.f}, step_scale = 0.f;
-  if (!none) {
-    const int* vi = a.vi + 4 * (size_t)id;
-    const float* vf = a.vf + 8 * (size_t)id;
-    first = vi[0]; N[2] = vi[1]; N[1] = vi[2]; N[0] = vi[3];
-    pitch = vf[0]; anchor[0] = vf[1]; anchor[1] = vf[2]; anchor[2] = vf[3]; step_scale = vf[4];
-    none = first < 0 || N[0] < 2 || N[1] < 2 || N[2] < 2 ||
-           (long long)first + (long long)N[2] * N[1] * N[0] > (long long)a.num_voxels;  // (a table row the host would not have written)
-  }
-  float ax[3], ay[3], az[3], q0[3], ia[3], hmax[3], scale = 0.f, level = 0.f, vox = 0.f;
+  // the frame's volume, pose and ray coefficients (blockIdx alone; sdf_tap.h: shared with the scene source)
+  int first, N[3];
+  float ax[3], ay[3], az[3], q0[3], ia[3], hmax[3], scale, level, step_scale, vox;
   bool par[3];
-  if (!none) {
-    const float* r = a.pose + 16 * (size_t)b;
-    const float tx = r[9], ty = r[10], tz = r[11];
-    scale = r[12]; level = r[13];
-    const float g = scale * pitch;
-    const float inv = 1.0f / g;
-    vox = g;
-    bool ok = g > 0.0f && step_scale > 0.0f && fabsf(level) < kSdfTwo30;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      ax[k] = (r[k] * a.pixmm) * inv;
-      ay[k] = (r[3 + k] * a.pixmm) * inv;
-      az[k] = r[6 + k] * inv;
-      q0[k] = anchor[k] - ((((r[k] * tx) + (r[3 + k] * ty)) + (r[6 + k] * tz)) * inv);
-      par[k] = !(fabsf(az[k]) >= 1e-12f);
-      ia[k] = par[k] ? 0.0f : 1.0f / az[k];
-      hmax[k] = (float)(N[k] - 1);
-      ok = ok && fabsf(ax[k]) < kSdfTwo30 && fabsf(ay[k]) < kSdfTwo30 && fabsf(az[k]) < kSdfTwo30 && fabsf(q0[k]) < kSdfTwo30;
-    }
-    none = !ok;
-  }
+  const bool none = !sdf_load_slot(a.ids ? a.ids[b] : 0, a.vi, a.vf, a.P, a.num_voxels, a.pose + 16 * (size_t)b, a.pixmm, &first, N, ax, ay,
+                                   az, q0, ia, hmax, par, &scale, &level, &step_scale, &vox);
   float* __restrict__ out = a.hm + (size_t)b * ((size_t)a.H * (size_t)a.W) + (size_t)y * (size_t)a.W + (size_t)x;
   if (none) {
     if (in_frame) *out = far_clip;
@@ -91,19 +57,8 @@ __global__ __launch_bounds__(256) void sdf_height_map_kernel(SdfArgs a) {
   float bq[3], lo = a.near_clip, hi = far_clip;
   bool active = in_frame;
 #pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    bq[k] = (q0[k] + (xf * ax[k])) + (yf * ay[k]);
-    active = active && fabsf(bq[k]) < kSdfTwo30;
-    if (par[k]) {
-      active = active && bq[k] >= 0.0f && bq[k] <= hmax[k];
-    } else {
-      const float t1 = (0.0f - bq[k]) * ia[k], t2 = (hmax[k] - bq[k]) * ia[k];
-      const float tn = t1 < t2 ? t1 : t2, tf = t1 < t2 ? t2 : t1;
-      lo = tn > lo ? tn : lo;
-      hi = tf < hi ? tf : hi;
-    }
-  }
-  active = active && lo <= hi;
+  for (int k = 0; k < 3; ++k) bq[k] = (q0[k] + (xf * ax[k])) + (yf * ay[k]);
+  active = active && sdf_clip(bq, ia, hmax, par, &lo, &hi);  // (sdf_tap.h: shared with the scene source)
 
   float depth = far_clip;
   if (active) {
@@ -114,20 +69,8 @@ __global__ __launch_bounds__(256) void sdf_height_map_kernel(SdfArgs a) {
       int m[3];
       float w[3];
 #pragma unroll
-      for (int k = 0; k < 3; ++k) {
-        float c = bq[k] + (z * az[k]);
-        c = c > 0.0f ? c : 0.0f;  // (a NaN: 0 - the index stays legal whatever the pose)
-        c = c < hmax[k] ? c : hmax[k];
-        m[k] = min((int)floorf(c), N[k] - 2);
-        w[k] = c - (float)m[k];
-      }
-      const float* v = vol + ((m[2] * sz + m[1] * sy) + m[0]);
-      const float v000 = v[0], v001 = v[1], v010 = v[sy], v011 = v[sy + 1];
-      const float v100 = v[sz], v101 = v[sz + 1], v110 = v[sz + sy], v111 = v[sz + sy + 1];
-      const float e00 = sdf_lerp(v000, v001, w[0]), e01 = sdf_lerp(v010, v011, w[0]);
-      const float e10 = sdf_lerp(v100, v101, w[0]), e11 = sdf_lerp(v110, v111, w[0]);
-      const float f0 = sdf_lerp(e00, e01, w[1]), f1 = sdf_lerp(e10, e11, w[1]);
-      const float s = sdf_lerp(f0, f1, w[2]);
+      for (int k = 0; k < 3; ++k) sdf_cell(bq[k] + (z * az[k]), hmax[k], N[k], &m[k], &w[k]);
+      const float s = sdf_tap(vol, sy, sz, m, w);  // (sdf_tap.h: shared with the scene source)
       const float d = ((s - level) * scale) * step_scale;
       if (d < a.tol) { depth = z; break; }
       z = z + d;

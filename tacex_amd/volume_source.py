@@ -99,6 +99,31 @@ class SdfVolume:
         return np.resize(picked, (count, 3)).astype(np.float32)
 
 
+def placement_rows(src, ids, cx_px, cy_px, quat_wxyz, press_mm, z_mm, scale, level_mm, blend_mm=0.0) -> torch.Tensor:
+    """(n, 16) float32 pose rows (`POSE_FIELDS`) for the volumes `ids` (n,) long of `src` (its `surface_points`, `gel_top_mm`, `pixmm`,
+    `device`): the placement of `SdfVolumeSource.set_pose`, shared with `SdfSceneSource.set_pose` (whose rows carry `blend_mm`)."""
+    dev = src.device
+    n = ids.shape[0]
+    per_env = functools.partial(_stage.per_env, n=n, device=dev)
+    q = quat_wxyz.to(device=dev, dtype=torch.float64) if isinstance(quat_wxyz, torch.Tensor) else torch.tensor(
+        [float(c) for c in quat_wxyz], dtype=torch.float64, device=dev)
+    q = (q.expand(n, 4) if q.dim() == 1 else q)
+    q = q / q.norm(dim=1, keepdim=True)
+    w, x, y, z = q.unbind(1)
+    R = torch.stack([1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y),
+                     2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x),
+                     2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)], dim=1)
+    scale, level = per_env(scale), per_env(level_mm)
+    if z_mm is not None:
+        tz = per_env(z_mm)
+    else:
+        low = (src.surface_points[ids].double() * R[:, None, 6:9]).sum(-1).min(dim=1).values
+        tz = (src.gel_top_mm - per_env(press_mm)) - scale * (low - level)
+    zero = torch.zeros(n, dtype=torch.float64, device=dev)
+    cols = [per_env(cx_px) * src.pixmm, per_env(cy_px) * src.pixmm, tz, scale, level, per_env(blend_mm) + zero, zero]
+    return torch.cat([R, torch.stack(cols, dim=1)], dim=1).float()
+
+
 class SdfVolumeSource(_stage.LibrarySource):
     """A signed-distance volume per env as the sensor's height-map source (`GelSightSensor.set_height_map_source`).  It owns the
     library - `voxels` (all grids back to back), `volumes_i` (P, 4) int32 [first voxel, D, Hv, Wv], `volumes_f` (P, 8) float32
@@ -151,27 +176,8 @@ class SdfVolumeSource(_stage.LibrarySource):
         no host sync."""
         if (press_mm is None) == (z_mm is None):
             raise ValueError("SdfVolumeSource.set_pose: give exactly one of press_mm and z_mm")
-        dev = self.device
         ids = self.volume_ids[env_ids].long().clamp(0, self.num_volumes - 1)
-        n = ids.shape[0]
-        per_env = functools.partial(_stage.per_env, n=n, device=dev)
-        q = quat_wxyz.to(device=dev, dtype=torch.float64) if isinstance(quat_wxyz, torch.Tensor) else torch.tensor(
-            [float(c) for c in quat_wxyz], dtype=torch.float64, device=dev)
-        q = (q.expand(n, 4) if q.dim() == 1 else q)
-        q = q / q.norm(dim=1, keepdim=True)
-        w, x, y, z = q.unbind(1)
-        R = torch.stack([1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y),
-                         2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x),
-                         2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)], dim=1)
-        scale, level = per_env(scale), per_env(level_mm)
-        if z_mm is not None:
-            tz = per_env(z_mm)
-        else:
-            low = (self.surface_points[ids].double() * R[:, None, 6:9]).sum(-1).min(dim=1).values
-            tz = (self.gel_top_mm - per_env(press_mm)) - scale * (low - level)
-        zero = torch.zeros(n, dtype=torch.float64, device=dev)
-        cols = [per_env(cx_px) * self.pixmm, per_env(cy_px) * self.pixmm, tz, scale, level, zero, zero]
-        self.pose[env_ids] = torch.cat([R, torch.stack(cols, dim=1)], dim=1).float()
+        self.pose[env_ids] = placement_rows(self, ids, cx_px, cy_px, quat_wxyz, press_mm, z_mm, scale, level_mm)
 
     def _launch(self, voxels, volumes_i, volumes_f, ids, hm, frame_min, indent, rows, gelpad_height, gelpad_to_camera_min_distance):
         dev = self.device
