@@ -17,6 +17,7 @@
 
 #include "tacex_hip.h"
 #include "tacex_internal.h"
+#include "wave_ops.h"
 
 namespace tacex {
 
@@ -246,15 +247,6 @@ struct DeformArgs {
   float fx, fy, cx, cy, near_m, far_m;
   int tiles_x, tiles_y, staged;
 };
-
-__device__ __forceinline__ float wave_min(float v) {
-  for (int o = 32; o > 0; o >>= 1) v = fminf(v, __shfl_xor(v, o));
-  return v;
-}
-__device__ __forceinline__ float wave_max(float v) {
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-  return v;
-}
 
 struct FemSurfaceVerts {
   const double* x;      // (B,V,3) world positions

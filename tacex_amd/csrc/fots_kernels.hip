@@ -438,16 +438,9 @@ int tacex_fots_marker_image(const float* markers, const uint8_t* patches, int su
   a.nbands = (CH + a.band_rows - 1) / a.band_rows;
   const size_t lds = (size_t)a.band_rows * CW;
   auto kern = fots_marker_image_kernel;
-  if (lds > 64 * 1024) {
-    static bool attr_done[64] = {};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-    if (!attr_done[dev]) {
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)budget);
-      if (e != hipSuccess) return fail_hip(e, "hipFuncSetAttribute(fots_marker_image_kernel)");
-      attr_done[dev] = true;
-    }
-  }
+  static size_t granted[64] = {};
+  if (hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), lds, granted); e != hipSuccess)
+    return fail_hip(e, "hipFuncSetAttribute(fots_marker_image_kernel)");
   hipLaunchKernelGGL(kern, dim3(B * a.nbands), dim3(256), lds, (hipStream_t)stream, a);
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? 0 : fail_hip(e, "fots_marker_image_kernel");

@@ -120,6 +120,29 @@ __host__ __device__ constexpr inline int mfma_wpad_index(int u, int i) { return 
 __host__ __device__ constexpr inline int mfma_wpad_tap0(int K) { return (((K - 1) / 2 + 7) & ~7) - (K - 1) / 2 + 15; }
 __host__ __device__ constexpr inline int mfma_wpad_floats(int K) { return (2 * (((K - 1) / 2 + 7) & ~7) + 31 + 15) & ~15; }
 
+// The fused level sets of the Taxim tails: the ONE mapping from (number of fused trailing levels, kernel size of the first of
+// them) to the template instantiation of the tiled tail (taxim_tail.hip) and of the streaming tail (taxim_stream.hip).
+// STREAM: the streaming tail has an instantiation of the set as well (the tiled tail has one of every set).
+template <bool STREAM, int... KS>
+struct FusedSet { static constexpr bool stream = STREAM; };
+// f(FusedSet<..>{}) of the set (n_fused, k0) names, `none` where it names no set
+template <typename R, typename F>
+inline R with_fused_set(int n_fused, int k0, R none, F&& f) {
+  if (n_fused == 4 && k0 == 9) return f(FusedSet<true, 9, 5, 3, 5>{});    // 320x240
+  if (n_fused == 4 && k0 == 15) return f(FusedSet<false, 15, 9, 5, 9>{}); // 640x480, all four levels (A/B choice): tiled tail only
+  if (n_fused == 3 && k0 == 9) return f(FusedSet<true, 9, 5, 9>{});       // 640x480, k = 15 stays a band level
+  if (n_fused == 3 && k0 == 5) return f(FusedSet<true, 5, 3, 5>{});       // 320x240, k = 9 stays a band level
+  return none;
+}
+// the same over the sets the streaming tail is instantiated for
+template <typename R, typename F>
+inline R with_stream_set(int n_fused, int k0, R none, F&& f) {
+  return with_fused_set(n_fused, k0, none, [&](auto s) -> R {
+    if constexpr (decltype(s)::stream) return f(s);
+    else return none;
+  });
+}
+
 // fused tail (taxim_tail.hip): trailing small-kernel levels + shading in one LDS-tiled kernel
 int tail_levels(const LevelDesc* lv, int n_levels, int H, int W);
 // triangle-filter tables of the antialiased policy-observation down-sample (one entry per output row / column):

@@ -1,9 +1,14 @@
-// Device-side helpers shared by the Taxim translation units (taxim_kernels.hip, taxim_tail.hip).
+// Device-side helpers shared by the Taxim translation units: the compile-time loop, the contact rule of the pyramid levels, reflect
+// padding, the XCD remap, the shading of a pixel with its argument block (ShadeArgs, make_shade_args) and the observation finish.
+// The wave reductions and scans are in wave_ops.h, the table of fused level sets in tacex_internal.h (with_fused_set).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include <type_traits>
+
+#include "tacex_internal.h"
+#include "wave_ops.h"
 
 namespace tacex {
 
@@ -31,47 +36,27 @@ __device__ __forceinline__ float fmin_raw(float a, float b) {
   return r;
 }
 
+// The contact rule of the deformation pyramid (TT:441-467), one copy for every kernel that applies it: the band kernels and the
+// generic passes (taxim_kernels.hip), the matrix-core band kernel (taxim_mfma.hip) and the tiled tail (taxim_tail.hip).  The
+// streaming tail (taxim_stream.hip) keeps its own text of the non-zero-gel rule inside its register-tuned body.
+//   S = (hm - shift_a) - shift_b      the height map under the press                                   TT:441
+//   J = min(S, gel)                   input of the first level and value of the restore                TT:454
+//   M = (J - gel < thr) && (S < 0)    contact mask, thr = -P * contact_scale (P: press depth)          TT:457-461
+//   Z[M] = J[M]                       the masked restore after a level's blur                          TT:467
+// With a zero gel map a kernel passes the literal 0 for `gel`: J - 0 and min(S, 0) fold as they did written out.
+__device__ __forceinline__ float contact_threshold(float pdepth, float contact_scale) { return -pdepth * contact_scale; }
+__device__ __forceinline__ float contact_shifted(float hm, float shift_a, float shift_b) { return (hm - shift_a) - shift_b; }
+// RAW: plain v_min_f32 (fmin_raw) in place of fminf - each call site keeps the minimum it was measured with (fminf canonicalises
+// first and returns the other operand for a NaN; the hazard recognizer cannot see an asm result feeding an MFMA)
+template <bool RAW>
+__device__ __forceinline__ float contact_input(float S, float gel) { return RAW ? fmin_raw(S, gel) : fminf(S, gel); }
+__device__ __forceinline__ bool contact_mask(float S, float J, float gel, float thr) { return ((J - gel) < thr) && (S < 0.0f); }
+__device__ __forceinline__ float contact_restore(int restore, bool M, float J, float blur) { return (restore && M) ? J : blur; }
+
 __device__ __forceinline__ int reflect_idx(int i, int n) {
   // torch 'reflect' (no edge repeat), single reflection: valid for -(n-1) <= i <= 2(n-1)
   i = i < 0 ? -i : i;
   return i >= n ? 2 * (n - 1) - i : i;
-}
-
-__device__ __forceinline__ float wave_min(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fminf(v, __shfl_xor(v, o, 64));
-  return v;
-}
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-  return v;
-}
-
-// Wave-wide inclusive scans on the VALU (DPP row shifts / broadcasts, no LDS round trips like ds_bpermute): lane 63 ends up
-// with the reduction over the wave.  Sequence of LLVM's AMDGPU atomic optimizer for wave64 on gfx9.
-#define TACEX_DPP_SCAN(v, IDENT, OP, T_AS_INT, INT_AS_T)                                                              \
-  do {                                                                                                                \
-    v = OP(v, INT_AS_T(__builtin_amdgcn_update_dpp(T_AS_INT(IDENT), T_AS_INT(v), 0x111, 0xf, 0xf, false)));           \
-    v = OP(v, INT_AS_T(__builtin_amdgcn_update_dpp(T_AS_INT(IDENT), T_AS_INT(v), 0x112, 0xf, 0xf, false)));           \
-    v = OP(v, INT_AS_T(__builtin_amdgcn_update_dpp(T_AS_INT(IDENT), T_AS_INT(v), 0x114, 0xf, 0xf, false)));           \
-    v = OP(v, INT_AS_T(__builtin_amdgcn_update_dpp(T_AS_INT(IDENT), T_AS_INT(v), 0x118, 0xf, 0xf, false)));           \
-    v = OP(v, INT_AS_T(__builtin_amdgcn_update_dpp(T_AS_INT(IDENT), T_AS_INT(v), 0x142, 0xa, 0xf, false)));           \
-    v = OP(v, INT_AS_T(__builtin_amdgcn_update_dpp(T_AS_INT(IDENT), T_AS_INT(v), 0x143, 0xc, 0xf, false)));           \
-  } while (0)
-__device__ __forceinline__ int dpp_id_int(int x) { return x; }
-__device__ __forceinline__ int dpp_add_int(int a, int b) { return a + b; }
-__device__ __forceinline__ int wave_scan_add_lane63(int v) {
-  TACEX_DPP_SCAN(v, 0, dpp_add_int, dpp_id_int, dpp_id_int);
-  return v;
-}
-__device__ __forceinline__ float wave_scan_min_lane63(float v) {
-  TACEX_DPP_SCAN(v, INFINITY, fminf, __float_as_int, __int_as_float);
-  return v;
-}
-__device__ __forceinline__ float wave_scan_max_lane63(float v) {
-  TACEX_DPP_SCAN(v, -INFINITY, fmaxf, __float_as_int, __int_as_float);
-  return v;
 }
 
 // XCD-aware bijective remap of the linear block id (blocks b, b+8, b+16.. share an XCD / L2):
@@ -100,7 +85,16 @@ struct ShadeArgs {
   float gsy, gsx;              // 0.5 * H / calib_h / pixmm, 0.5 * W / calib_w / pixmm
   float inv_x_binr, inv_y_binr;
 };
-
+// The argument block of a context's shading tables for B frames of H x W, derived scales included; the caller sets z, rgb and idx_out.
+inline ShadeArgs make_shade_args(const ShadeParams& sp, int B, int H, int W) {
+  ShadeArgs a{};
+  a.poly = sp.poly_dev; a.bg = sp.bg_nhwc_dev; a.fx = sp.fx_dev; a.fy = sp.fy_dev;
+  a.H = H; a.W = W; a.B = B; a.nb = sp.nb; a.pixmm = sp.pixmm;
+  a.calib_h = (float)sp.calib_h; a.calib_w = (float)sp.calib_w; a.x_binr = sp.x_binr; a.y_binr = sp.y_binr;
+  a.gsy = (float)(0.5 * H / sp.calib_h / (double)sp.pixmm); a.gsx = (float)(0.5 * W / sp.calib_w / (double)sp.pixmm);
+  a.inv_x_binr = (float)(1.0 / (double)sp.x_binr); a.inv_y_binr = (float)(1.0 / (double)sp.y_binr);
+  return a;
+}
 
 // plain v_max_f32 (see fmin_raw)
 __device__ __forceinline__ float fmax_raw(float a, float b) {
@@ -243,6 +237,35 @@ __device__ __forceinline__ void shade_pixel(const ShadeArgs& a, float ztop, floa
     io[0] = (uint8_t)im;
     io[1] = (uint8_t)id;
   }
+}
+
+// One thread of an observation finish kernel (grid: cells of a frame x frames): gather(b, oy, ox, a0, a1, a2) adds the partial
+// sums of cell (oy, ox) of frame b in its fixed order; here the sums are normalised by the weight sums and stored (U8: as bytes).
+template <bool U8, typename G>
+__device__ __forceinline__ void obs_finish_cell(void* __restrict__ obs_v, const ObsTables& T, G&& gather) {
+  const int oh = T.oh, ow = T.ow;
+  const int cell = blockIdx.x * blockDim.x + threadIdx.x;
+  if (cell >= oh * ow) return;
+  const int b = blockIdx.y;
+  const int oy = cell / ow, ox = cell - oy * ow;
+  float a0 = 0.0f, a1 = 0.0f, a2 = 0.0f;
+  gather(b, oy, ox, a0, a1, a2);
+  const float nrm = T.xsum[ox] * T.ysum[oy];
+  const size_t oi = ((size_t)b * (oh * ow) + cell) * 3;
+  if constexpr (U8) {  // RGB is clipped to [0,1] (TT:257-258), so is every convex combination of it
+    uint8_t* o = static_cast<uint8_t*>(obs_v) + oi;
+    o[0] = (uint8_t)(a0 / nrm * 255.0f + 0.5f); o[1] = (uint8_t)(a1 / nrm * 255.0f + 0.5f); o[2] = (uint8_t)(a2 / nrm * 255.0f + 0.5f);
+  } else {
+    float* o = static_cast<float*>(obs_v) + oi;
+    o[0] = a0 / nrm; o[1] = a1 / nrm; o[2] = a2 / nrm;
+  }
+}
+// ... and its launch: the U8 or the float instantiation of the kernel over that grid
+template <typename K, typename... A>
+inline hipError_t launch_obs_finish(bool u8, K kern_u8, K kern_f32, const ObsTables& t, int B, hipStream_t st, A... args) {
+  const dim3 grid((t.oh * t.ow + 255) / 256, B);
+  hipLaunchKernelGGL(u8 ? kern_u8 : kern_f32, grid, dim3(256), 0, st, args...);
+  return hipGetLastError();
 }
 
 }  // namespace tacex

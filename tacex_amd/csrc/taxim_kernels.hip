@@ -14,6 +14,9 @@
 //   H-pass : each thread owns 2 rows x RH columns, reads its window from LDS with ds_read_b128,
 //            then applies the masked restore Z[M] = J[M] and writes coalesced.
 // Both passes are "tap x window" FMA loops on float2 so the compiler can use v_pk_fma_f32.
+//
+// Shared steps: the contact rule S / J / M / restore, the shading and its argument block - taxim_device.h; what the two band
+// kernels share - BandCoords and band_*, below; the frame walk - frame_rows.h; wave reductions - wave_ops.h.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
@@ -252,6 +255,118 @@ __global__ void press_depth_kernel(const float* __restrict__ fmin, const float* 
 // K3/K4: one pyramid level = separable Gaussian + masked restore, band-tiled (see file header)
 // ------------------------------------------------------------------------------------------------
 
+// What the two band kernels share around their tap loops: where the workgroup and the thread work (BandCoords), the level's streamed
+// input, the row-pair LDS store of the V-pass, and the masked restore + stores of an H-pass item.
+struct BandCoords {
+  int frame, by0;  // frame, first row of the band
+  size_t fo;       // the frame's offset in a (B,H,W) array
+  const float *src, *hm;  // the frame's input (FIRST: the height map) and height map
+  float sa, sb;    // its shifts
+  // The V-pass row chunk is WAVE-UNIFORM (waves [ch*wpc, (ch+1)*wpc) own chunk ch), so the reflected row index and the
+  // row base address are scalar (SALU) work; with a per-lane chunk they cost ~8 VALU instructions per streamed row,
+  // i.e. half as many again as the FMAs themselves.
+  int ch, cpair;   // row chunk, this thread's column pair
+};
+template <int TH, bool FIRST>
+__device__ __forceinline__ BandCoords band_coords(const BlurArgs& a) {
+  const int H = a.H, W = a.W;
+  BandCoords bc;
+  const int nbands = (H + TH - 1) / TH;
+  const int lid = xcd_remap(blockIdx.x, gridDim.x);
+  bc.frame = lid / nbands;
+  const int band = lid - bc.frame * nbands;
+  bc.by0 = band * TH;
+  bc.fo = (size_t)bc.frame * H * W;
+  bc.src = FIRST ? a.hm + bc.fo : a.src + bc.fo;
+  bc.hm = a.hm + bc.fo;
+  bc.sa = a.shift_a[bc.frame]; bc.sb = a.shift_b[bc.frame];
+  const int ncp = W >> 1;
+  const int wpc = (ncp + 63) >> 6;                                        // waves per row chunk
+  const int wid = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  bc.ch = wid / wpc;
+  bc.cpair = (wid - bc.ch * wpc) * 64 + (int)(threadIdx.x & 63);
+  return bc;
+}
+
+// columns c, c + 1 (coff = 4 c bytes) of input row y, reflected; clamped for the rows of a partial last band (never stored) and for
+// those beyond the looped kernel's window (finite data, zero weight); FIRST: the level's input J = min(S, gel) (TT:441, TT:454)
+template <bool FIRST>
+__device__ __forceinline__ v2f band_v_input(const float* src, const float* gel, float sa, float sb, int y, int H, int W, unsigned coff) {
+  int yy = reflect_idx(y, H);
+  yy = yy < 0 ? 0 : (yy >= H ? H - 1 : yy);
+  // scalar row base + 32-bit unsigned lane offset -> global_load with an SGPR base, no per-lane 64-bit adds
+  const char* rowb = reinterpret_cast<const char*>(src + (size_t)yy * W);
+  v2f x = *reinterpret_cast<const v2f*>(rowb + coff);
+  if (FIRST) {
+    const char* gelb = reinterpret_cast<const char*>(gel + (size_t)yy * W);
+    const v2f g = *reinterpret_cast<const v2f*>(gelb + coff);
+    x.x = contact_input<true>(contact_shifted(x.x, sa, sb), g.x);
+    x.y = contact_input<true>(contact_shifted(x.y, sa, sb), g.y);
+  }
+  return x;
+}
+
+// V-pass sums of row chunk ch (RV rows) x column pair cpair -> LDS, row-pair interleaved, with the mirrored x-padding
+// (torch 'reflect'): position -cc <- cc, position 2(W-1)-cc <- cc
+template <int RV>
+__device__ __forceinline__ void band_v_store(v2f* mid, const v2f (&acc)[RV], int ch, int cpair, int W, int pitch, int padx) {
+  const int rp0 = (ch * RV) >> 1, c = cpair << 1;
+#pragma unroll
+  for (int r = 0; r < RV; r += 2) {
+    v2f* row = mid + (size_t)(rp0 + (r >> 1)) * pitch + padx;
+    v2f e0 = {acc[r].x, acc[r + 1].x};  // column c   : (row y, row y+1)
+    v2f e1 = {acc[r].y, acc[r + 1].y};  // column c+1
+    v4f q = {e0.x, e0.y, e1.x, e1.y};
+    *reinterpret_cast<v4f*>(row + c) = q;
+    if (c >= 1 && c <= padx) row[-c] = e0;
+    if (c + 1 <= padx) row[-(c + 1)] = e1;
+    if (c >= W - 1 - padx && c <= W - 2) row[2 * (W - 1) - c] = e0;
+    if (c + 1 >= W - 1 - padx && c + 1 <= W - 2) row[2 * (W - 1) - (c + 1)] = e1;
+  }
+}
+
+// H-pass sums of row pair rp x columns [x0, x0 + RH): the masked restore Z[M] = J[M] (TT:457-467), then dst and the mask, coalesced.
+// blur_band_kernel calls it; blur_band_loop_kernel keeps the same text written out (as a call: 2 VGPRs and 6 SGPRs more there).
+template <int RH>
+__device__ __forceinline__ void band_h_store(const BlurArgs& a, const BandCoords& bc, const float* gel, float thr, const v2f (&acc)[RH], int rp, int x0) {
+  const int H = a.H, W = a.W;
+  const size_t fo = bc.fo;
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    const int y = bc.by0 + 2 * rp + h;
+    if (y >= H) continue;
+    const size_t ro = (size_t)y * W + x0;
+    float outv[RH];
+    uint8_t mk[RH];
+#pragma unroll
+    for (int r4 = 0; r4 < RH; r4 += 4) {
+      v4f hv = *reinterpret_cast<const v4f*>(bc.hm + ro + r4);
+      v4f gv = *reinterpret_cast<const v4f*>(gel + ro + r4);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const float S = contact_shifted(hv[k], bc.sa, bc.sb);
+        const float J = contact_input<false>(S, gv[k]);
+        const bool M = contact_mask(S, J, gv[k], thr);
+        const float bl = h == 0 ? acc[r4 + k].x : acc[r4 + k].y;
+        outv[r4 + k] = contact_restore(a.restore, M, J, bl);
+        mk[r4 + k] = M ? 1 : 0;
+      }
+    }
+#pragma unroll
+    for (int r4 = 0; r4 < RH; r4 += 4) {
+      v4f o = {outv[r4], outv[r4 + 1], outv[r4 + 2], outv[r4 + 3]};
+      *reinterpret_cast<v4f*>(a.dst + fo + ro + r4) = o;
+    }
+    if (a.mask_out) {
+#pragma unroll
+      for (int r4 = 0; r4 < RH; r4 += 4) {
+        uchar4 u = {mk[r4], mk[r4 + 1], mk[r4 + 2], mk[r4 + 3]};
+        *reinterpret_cast<uchar4*>(a.mask_out + fo + ro + r4) = u;
+      }
+    }
+  }
+}
+
 template <int K, int TH, int RV, int RH, bool FIRST, int NT>
 __global__ __launch_bounds__(NT, 3) void blur_band_kernel(BlurArgs a) {
   static_assert(K % 2 == 1, "odd kernel");
@@ -262,48 +377,21 @@ __global__ __launch_bounds__(NT, 3) void blur_band_kernel(BlurArgs a) {
   v2f* mid = reinterpret_cast<v2f*>(smem_raw);
 
   const int H = a.H, W = a.W;
-  const int nbands = (H + TH - 1) / TH;
-  const int lid = xcd_remap(blockIdx.x, gridDim.x);
-  const int frame = lid / nbands;
-  const int band = lid - frame * nbands;
-  const int by0 = band * TH;
-  const size_t fo = (size_t)frame * H * W;
-  const float* __restrict__ src = FIRST ? a.hm + fo : a.src + fo;
-  const float* __restrict__ hm = a.hm + fo;
+  const BandCoords bc = band_coords<TH, FIRST>(a);
   const float* __restrict__ gel = a.gel;
-  const float sa = a.shift_a[frame], sb = a.shift_b[frame];
   const float* __restrict__ taps = a.taps;
   const int pitch = a.pitch, padx = a.padx;
 
   // ---- V-pass: global -> registers -> LDS (row-pair interleaved) ----
-  // The row chunk is WAVE-UNIFORM (waves [ch*wpc, (ch+1)*wpc) own chunk ch), so the reflected row index and the
-  // row base address are scalar (SALU) work; with a per-lane chunk they cost ~8 VALU instructions per streamed row,
-  // i.e. half as many again as the FMAs themselves.
-  const int ncp = W >> 1;
-  const int wpc = (ncp + 63) >> 6;                                        // waves per row chunk
-  const int wid = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  const int ch = wid / wpc;
-  const int cpair = (wid - ch * wpc) * 64 + (int)(threadIdx.x & 63);
-  if (ch < TH / RV && cpair < ncp) {
-    const int c = cpair << 1;
-    const unsigned coff = (unsigned)c * 4u;
-    const int y0 = by0 + ch * RV;
+  if (bc.ch < TH / RV && bc.cpair < (W >> 1)) {
+    const unsigned coff = (unsigned)(bc.cpair << 1) * 4u;  // columns 2 cpair, 2 cpair + 1
+    const int y0 = bc.by0 + bc.ch * RV;
     v2f acc[RV];
 #pragma unroll
     for (int r = 0; r < RV; ++r) acc[r] = (v2f)(0.0f);
     static_for<0, RV + K - 1>([&](auto jc) {
       constexpr int j = decltype(jc)::value;
-      int yy = reflect_idx(y0 - R + j, H);
-      yy = yy < 0 ? 0 : (yy >= H ? H - 1 : yy);  // rows of a partial last band (never stored)
-      // scalar row base + 32-bit unsigned lane offset -> global_load with an SGPR base, no per-lane 64-bit adds
-      const char* rowb = reinterpret_cast<const char*>(src + (size_t)yy * W);
-      v2f x = *reinterpret_cast<const v2f*>(rowb + coff);
-      if (FIRST) {  // J = min(S, gel), S = (hm - shift_a) - shift_b   (TT:441, TT:454)
-        const char* gelb = reinterpret_cast<const char*>(gel + (size_t)yy * W);
-        const v2f g = *reinterpret_cast<const v2f*>(gelb + coff);
-        x.x = fmin_raw((x.x - sa) - sb, g.x);
-        x.y = fmin_raw((x.y - sa) - sb, g.y);
-      }
+      const v2f x = band_v_input<FIRST>(bc.src, gel, bc.sa, bc.sb, y0 - R + j, H, W, coff);
       static_for<0, RV>([&](auto rc) {
         constexpr int r = decltype(rc)::value;
         constexpr int t = j - r;
@@ -313,26 +401,12 @@ __global__ __launch_bounds__(NT, 3) void blur_band_kernel(BlurArgs a) {
         }
       });
     });
-    const int rp0 = (ch * RV) >> 1;
-#pragma unroll
-    for (int r = 0; r < RV; r += 2) {
-      v2f* row = mid + (size_t)(rp0 + (r >> 1)) * pitch + padx;
-      v2f e0 = {acc[r].x, acc[r + 1].x};  // column c   : (row y, row y+1)
-      v2f e1 = {acc[r].y, acc[r + 1].y};  // column c+1
-      v4f q = {e0.x, e0.y, e1.x, e1.y};
-      *reinterpret_cast<v4f*>(row + c) = q;
-      // mirrored x-padding (torch 'reflect'): position -cc <- cc, position 2(W-1)-cc <- cc
-      if (c >= 1 && c <= padx) row[-c] = e0;
-      if (c + 1 <= padx) row[-(c + 1)] = e1;
-      if (c >= W - 1 - padx && c <= W - 2) row[2 * (W - 1) - c] = e0;
-      if (c + 1 >= W - 1 - padx && c + 1 <= W - 2) row[2 * (W - 1) - (c + 1)] = e1;
-    }
+    band_v_store<RV>(mid, acc, bc.ch, bc.cpair, W, pitch, padx);
   }
   __syncthreads();
 
   // ---- H-pass: LDS -> registers -> masked restore -> global ----
-  const float P = a.pdepth[frame];
-  const float thr = -P * a.contact_scale;  // TT:459
+  const float thr = contact_threshold(a.pdepth[bc.frame], a.contact_scale);
   const int nseg = W / RH;
   const int hitems = (TH >> 1) * ((nseg + 3) & ~3);
   for (int it = threadIdx.x; it < hitems; it += NT) {
@@ -363,40 +437,7 @@ __global__ __launch_bounds__(NT, 3) void blur_band_kernel(BlurArgs a) {
         });
       });
     });
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      const int y = by0 + 2 * rp + h;
-      if (y >= H) continue;
-      const size_t ro = (size_t)y * W + x0;
-      float outv[RH];
-      uint8_t mk[RH];
-#pragma unroll
-      for (int r4 = 0; r4 < RH; r4 += 4) {
-        v4f hv = *reinterpret_cast<const v4f*>(hm + ro + r4);
-        v4f gv = *reinterpret_cast<const v4f*>(gel + ro + r4);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          const float S = (hv[k] - sa) - sb;
-          const float J = fminf(S, gv[k]);
-          const bool M = ((J - gv[k]) < thr) && (S < 0.0f);  // TT:457-461
-          const float bl = h == 0 ? acc[r4 + k].x : acc[r4 + k].y;
-          outv[r4 + k] = (a.restore && M) ? J : bl;         // TT:467
-          mk[r4 + k] = M ? 1 : 0;
-        }
-      }
-#pragma unroll
-      for (int r4 = 0; r4 < RH; r4 += 4) {
-        v4f o = {outv[r4], outv[r4 + 1], outv[r4 + 2], outv[r4 + 3]};
-        *reinterpret_cast<v4f*>(a.dst + fo + ro + r4) = o;
-      }
-      if (a.mask_out) {
-#pragma unroll
-        for (int r4 = 0; r4 < RH; r4 += 4) {
-          uchar4 u = {mk[r4], mk[r4 + 1], mk[r4 + 2], mk[r4 + 3]};
-          *reinterpret_cast<uchar4*>(a.mask_out + fo + ro + r4) = u;
-        }
-      }
-    }
+    band_h_store<RH>(a, bc, gel, thr, acc, rp, x0);
   }
 }
 
@@ -416,28 +457,14 @@ __global__ __launch_bounds__(NT, 3) void blur_band_loop_kernel(BlurArgs a, int K
   v2f* mid = reinterpret_cast<v2f*>(smem_raw);
   const int R = (K - 1) / 2, RUP = (R + 1) & ~1;
   const int H = a.H, W = a.W;
-  const int nbands = (H + TH - 1) / TH;
-  const int lid = xcd_remap(blockIdx.x, gridDim.x);
-  const int frame = lid / nbands;
-  const int band = lid - frame * nbands;
-  const int by0 = band * TH;
-  const size_t fo = (size_t)frame * H * W;
-  const float* __restrict__ src = FIRST ? a.hm + fo : a.src + fo;
-  const float* __restrict__ hm = a.hm + fo;
+  const BandCoords bc = band_coords<TH, FIRST>(a);
   const float* __restrict__ gel = a.gel;
-  const float sa = a.shift_a[frame], sb = a.shift_b[frame];
   const float* __restrict__ wq = a.taps;  // zero-padded taps
   const int pitch = a.pitch, padx = a.padx;
 
-  const int ncp = W >> 1;
-  const int wpc = (ncp + 63) >> 6;
-  const int wid = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  const int ch = wid / wpc;
-  const int cpair = (wid - ch * wpc) * 64 + (int)(threadIdx.x & 63);
-  if (ch < TH / RV && cpair < ncp) {
-    const int c = cpair << 1;
-    const unsigned coff = (unsigned)c * 4u;
-    const int y0 = by0 + ch * RV;
+  if (bc.ch < TH / RV && bc.cpair < (W >> 1)) {
+    const unsigned coff = (unsigned)(bc.cpair << 1) * 4u;  // columns 2 cpair, 2 cpair + 1
+    const int y0 = bc.by0 + bc.ch * RV;
     v2f acc[RV];
 #pragma unroll
     for (int r = 0; r < RV; ++r) acc[r] = (v2f)(0.0f);
@@ -446,43 +473,18 @@ __global__ __launch_bounds__(NT, 3) void blur_band_loop_kernel(BlurArgs a, int K
     for (int g = 0; g < ng; ++g) {
       v2f xv[G];
 #pragma unroll
-      for (int i = 0; i < G; ++i) {
-        int yy = reflect_idx(y0 - R + g * G + i, H);
-        yy = yy < 0 ? 0 : (yy >= H ? H - 1 : yy);  // beyond the window / partial band: finite data, zero weight
-        const char* rowb = reinterpret_cast<const char*>(src + (size_t)yy * W);
-        v2f x = *reinterpret_cast<const v2f*>(rowb + coff);
-        if (FIRST) {
-          const char* gelb = reinterpret_cast<const char*>(gel + (size_t)yy * W);
-          const v2f gg = *reinterpret_cast<const v2f*>(gelb + coff);
-          x.x = fmin_raw((x.x - sa) - sb, gg.x);
-          x.y = fmin_raw((x.y - sa) - sb, gg.y);
-        }
-        xv[i] = x;
-      }
+      for (int i = 0; i < G; ++i) xv[i] = band_v_input<FIRST>(bc.src, gel, bc.sa, bc.sb, y0 - R + g * G + i, H, W, coff);
       const float* wg = wq + kLoopOff + g * G;  // weight of (element i, output r) = wg[i - r]
 #pragma unroll
       for (int i = 0; i < G; ++i)
 #pragma unroll
         for (int r = 0; r < RV; ++r) acc[r] += wg[i - r] * xv[i];
     }
-    const int rp0 = (ch * RV) >> 1;
-#pragma unroll
-    for (int r = 0; r < RV; r += 2) {
-      v2f* row = mid + (size_t)(rp0 + (r >> 1)) * pitch + padx;
-      v2f e0 = {acc[r].x, acc[r + 1].x};
-      v2f e1 = {acc[r].y, acc[r + 1].y};
-      v4f q = {e0.x, e0.y, e1.x, e1.y};
-      *reinterpret_cast<v4f*>(row + c) = q;
-      if (c >= 1 && c <= padx) row[-c] = e0;
-      if (c + 1 <= padx) row[-(c + 1)] = e1;
-      if (c >= W - 1 - padx && c <= W - 2) row[2 * (W - 1) - c] = e0;
-      if (c + 1 >= W - 1 - padx && c + 1 <= W - 2) row[2 * (W - 1) - (c + 1)] = e1;
-    }
+    band_v_store<RV>(mid, acc, bc.ch, bc.cpair, W, pitch, padx);
   }
   __syncthreads();
 
-  const float P = a.pdepth[frame];
-  const float thr = -P * a.contact_scale;
+  const float thr = contact_threshold(a.pdepth[bc.frame], a.contact_scale);
   const int nseg = W / RH;
   const int hitems = (TH >> 1) * ((nseg + 3) & ~3);
   const int nwin = RH + 2 * RUP;  // float2 elements of the window
@@ -514,24 +516,26 @@ __global__ __launch_bounds__(NT, 3) void blur_band_loop_kernel(BlurArgs a, int K
 #pragma unroll
         for (int r = 0; r < RH; ++r) acc[r] += wg[i - r] * xv[i];
     }
+    // (band_h_store, written out: profiles/taxim_device_isa.md)
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
-      const int y = by0 + 2 * rp + h;
+      const int y = bc.by0 + 2 * rp + h;
       if (y >= H) continue;
+      const size_t fo = bc.fo;
       const size_t ro = (size_t)y * W + x0;
       float outv[RH];
       uint8_t mk[RH];
 #pragma unroll
       for (int r4 = 0; r4 < RH; r4 += 4) {
-        v4f hv = *reinterpret_cast<const v4f*>(hm + ro + r4);
+        v4f hv = *reinterpret_cast<const v4f*>(bc.hm + ro + r4);
         v4f gv = *reinterpret_cast<const v4f*>(gel + ro + r4);
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
-          const float S = (hv[k] - sa) - sb;
-          const float J = fminf(S, gv[k]);
-          const bool M = ((J - gv[k]) < thr) && (S < 0.0f);
+          const float S = contact_shifted(hv[k], bc.sa, bc.sb);
+          const float J = contact_input<false>(S, gv[k]);
+          const bool M = contact_mask(S, J, gv[k], thr);
           const float bl = h == 0 ? acc[r4 + k].x : acc[r4 + k].y;
-          outv[r4 + k] = (a.restore && M) ? J : bl;
+          outv[r4 + k] = contact_restore(a.restore, M, J, bl);
           mk[r4 + k] = M ? 1 : 0;
         }
       }
@@ -550,6 +554,7 @@ __global__ __launch_bounds__(NT, 3) void blur_band_loop_kernel(BlurArgs a, int K
     }
   }
 }
+
 
 // ------------------------------------------------------------------------------------------------
 // generic fallback (any odd kw, kh; any H, W): two plain passes through a temp buffer.
@@ -577,8 +582,7 @@ __global__ __launch_bounds__(256) void blur_generic_v_kernel(GenericArgs a) {  /
       const int yy = reflect_idx(y - r + t, H);
       float v;
       if (a.first) {
-        const float S = (a.hm[fo + (size_t)yy * W + x] - a.shift_a[b]) - a.shift_b[b];
-        v = fminf(S, a.gel[(size_t)yy * W + x]);
+        v = contact_input<false>(contact_shifted(a.hm[fo + (size_t)yy * W + x], a.shift_a[b], a.shift_b[b]), a.gel[(size_t)yy * W + x]);
       } else {
         v = a.src[fo + (size_t)yy * W + x];
       }
@@ -603,10 +607,10 @@ __global__ __launch_bounds__(256) void blur_generic_h_kernel(GenericArgs a) {  /
       acc = fmaf(a.taps[t], a.src[fo + (size_t)y * W + xx], acc);
     }
     const float g = a.gel[(size_t)y * W + x];
-    const float S = (a.hm[i] - a.shift_a[b]) - a.shift_b[b];
-    const float J = fminf(S, g);
-    const bool M = ((J - g) < (-a.pdepth[b] * a.contact_scale)) && (S < 0.0f);
-    a.dst[i] = (a.restore && M) ? J : acc;
+    const float S = contact_shifted(a.hm[i], a.shift_a[b], a.shift_b[b]);
+    const float J = contact_input<false>(S, g);
+    const bool M = contact_mask(S, J, g, contact_threshold(a.pdepth[b], a.contact_scale));
+    a.dst[i] = contact_restore(a.restore, M, J, acc);
     if (a.mask_out) a.mask_out[i] = M ? 1 : 0;
   }
 }
@@ -968,20 +972,14 @@ hipError_t run_blur_level(const LevelDesc& lv, const float* src, const float* hm
   if (route == kRouteMfma)
     return dispatch_mfma(lv.kw, first, mfma_level_args(lv, src, hm, gel, sa, sb, pd, dst, mask_out, B, H, W, contact_scale, restore, rows_ext, ext_grow,
                                                        ext_grow_x, lean, zero_bands_unread, wlds), st);
-  if (route == kRouteBandLoop384 || route == kRouteBandLoop640) {
+  if (route != kRouteGeneric) {  // the band routes: one argument block, the looped kernels read the zero-padded taps
     BlurArgs a{};
     a.src = src; a.hm = hm; a.gel = gel; a.shift_a = sa; a.shift_b = sb; a.pdepth = pd;
-    a.dst = dst; a.mask_out = mask_out; a.taps = lv.taps_pad_dev; a.H = H; a.W = W; a.B = B;
+    a.dst = dst; a.mask_out = mask_out; a.taps = route == kRouteBand ? lv.taps_w_dev : lv.taps_pad_dev; a.H = H; a.W = W; a.B = B;
     a.contact_scale = contact_scale; a.restore = restore;
+    if (route == kRouteBand) return dispatch_band(lv.kw, first, a, st);
     if (route == kRouteBandLoop384) return first ? launch_band_loop<true, 384>(a, lv.kw, st) : launch_band_loop<false, 384>(a, lv.kw, st);
     return first ? launch_band_loop<true, 640>(a, lv.kw, st) : launch_band_loop<false, 640>(a, lv.kw, st);
-  }
-  if (route == kRouteBand) {
-    BlurArgs a{};
-    a.src = src; a.hm = hm; a.gel = gel; a.shift_a = sa; a.shift_b = sb; a.pdepth = pd;
-    a.dst = dst; a.mask_out = mask_out; a.taps = lv.taps_w_dev; a.H = H; a.W = W; a.B = B;
-    a.contact_scale = contact_scale; a.restore = restore;
-    return dispatch_band(lv.kw, first, a, st);
   }
   GenericArgs g{};
   g.hm = hm; g.gel = gel; g.shift_a = sa; g.shift_b = sb; g.pdepth = pd; g.H = H; g.W = W; g.B = B;
@@ -999,13 +997,8 @@ hipError_t run_blur_level(const LevelDesc& lv, const float* src, const float* hm
 
 hipError_t run_shade(const ShadeParams& sp, const float* z, float* rgb, uint8_t* idx_out, int B,
                      hipStream_t st) {
-  ShadeArgs a{};
-  a.z = z; a.poly = sp.poly_dev; a.bg = sp.bg_nhwc_dev; a.fx = sp.fx_dev; a.fy = sp.fy_dev; a.rgb = rgb;
-  a.idx_out = idx_out; a.H = sp.H; a.W = sp.W; a.B = B; a.nb = sp.nb; a.pixmm = sp.pixmm;
-  a.calib_h = (float)sp.calib_h; a.calib_w = (float)sp.calib_w;
-  a.x_binr = sp.x_binr; a.y_binr = sp.y_binr;
-  a.gsy = (float)(0.5 * sp.H / sp.calib_h / (double)sp.pixmm); a.gsx = (float)(0.5 * sp.W / sp.calib_w / (double)sp.pixmm);
-  a.inv_x_binr = (float)(1.0 / (double)sp.x_binr); a.inv_y_binr = (float)(1.0 / (double)sp.y_binr);
+  ShadeArgs a = make_shade_args(sp, B, sp.H, sp.W);
+  a.z = z; a.rgb = rgb; a.idx_out = idx_out;
   const int npix = sp.H * sp.W;
   hipLaunchKernelGGL(shade_kernel, dim3((npix + 255) / 256, B), dim3(256), 0, st, a);
   return hipGetLastError();

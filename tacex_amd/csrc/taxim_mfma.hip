@@ -1,4 +1,4 @@
-// Matrix-core (v_mfma_f32_16x16x4_f32) band kernels of the Taxim pyramid levels - see the banner below.
+// Matrix-core (v_mfma_f32_16x16x4_f32) band kernels of the Taxim pyramid levels - see the banner below; the contact rule: taxim_device.h.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
@@ -229,10 +229,10 @@ __device__ __forceinline__ void blur_mfma_body(const BlurArgs a, int block, int 
         constexpr int c = decltype(cc)::value;
         constexpr int ku = chunk * CH + c;
         v4f x = xb[chunk & 1][c];
-        if constexpr (FIRST) {  // J = min(S, gel), S = (hm - shift_a) - shift_b (TT:441, TT:454).  fminf, not the
-          const v4f gq = gb[chunk & 1][c];  // inline-asm fmin_raw: the hazard recognizer cannot see asm feeding an MFMA
-          x.x = fminf((x.x - sa) - sb, gq.x); x.y = fminf((x.y - sa) - sb, gq.y);
-          x.z = fminf((x.z - sa) - sb, gq.z); x.w = fminf((x.w - sa) - sb, gq.w);
+        if constexpr (FIRST) {  // the level's input J (TT:441, TT:454).  fminf, not the inline-asm fmin_raw: the hazard
+          const v4f gq = gb[chunk & 1][c];  // recognizer cannot see asm feeding an MFMA
+#pragma unroll
+          for (int k = 0; k < 4; ++k) x[k] = contact_input<false>(contact_shifted(x[k], sa, sb), gq[k]);
           if constexpr (LEAN) {  // nothing was loaded: J = +0.0f, what min(S, 0) gives outside the contact rectangle
             const bool in = vin[chunk & 1][c];
             x.x = in ? x.x : 0.0f; x.y = in ? x.y : 0.0f; x.z = in ? x.z : 0.0f; x.w = in ? x.w : 0.0f;
@@ -288,7 +288,7 @@ __device__ __forceinline__ void blur_mfma_body(const BlurArgs a, int block, int 
       if constexpr (WLDS) wl[ks] = wh[ks];
       else wl[ks] = a.taps[((TACEX_MFMA_H_CONSEC ? 0 : KS) + ks) * 64 + lane];
     });
-    const float thr = -(WLDS ? pd_pre : a.pdepth[frame]) * a.contact_scale;  // TT:459
+    const float thr = contact_threshold(WLDS ? pd_pre : a.pdepth[frame], a.contact_scale);
     if (!h_need) {  // (wave-uniform) exactly zero output, no contact pixel in these columns
 #pragma unroll
       for (int t = 0; t < NTILE; ++t) {
@@ -364,10 +364,10 @@ __device__ __forceinline__ void blur_mfma_body(const BlurArgs a, int block, int 
         uint8_t mk[4];
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
-          const float S = (hv[n][k] - sa) - sb;
-          const float J = fminf(S, gv[n][k]);
-          const bool M = (((J - gv[n][k]) < thr) && (S < 0.0f)) & hin[n];  // TT:457-461
-          o[k] = (a.restore && M) ? J : acc[n][k];              // TT:467
+          const float S = contact_shifted(hv[n][k], sa, sb);
+          const float J = contact_input<false>(S, gv[n][k]);
+          const bool M = contact_mask(S, J, gv[n][k], thr) & hin[n];
+          o[k] = contact_restore(a.restore, M, J, acc[n][k]);
           mk[k] = M ? 1 : 0;
         }
         *reinterpret_cast<v4f*>(a.dst + fo + p0 + 16 * n) = o;

@@ -184,12 +184,8 @@ hipError_t run_shadow_rays(const ShadowParams& sw, const ShadeParams& sp, const 
 hipError_t run_shadow(const ShadowParams& sw, const ShadeParams& sp, const float* z, const uint8_t* mask, const float* gel,
                       float* rgb, float* ws_raw, float* ws_shadow, float* ws_gdir, float* ws_tmp, int B, hipStream_t st) {
   const int H = sp.H, W = sp.W, npix = H * W;
-  ShadeArgs a{};
-  a.z = z; a.poly = sp.poly_dev; a.bg = sp.bg_nhwc_dev; a.fx = sp.fx_dev; a.fy = sp.fy_dev; a.rgb = nullptr; a.idx_out = nullptr;
-  a.H = H; a.W = W; a.B = B; a.nb = sp.nb; a.pixmm = sp.pixmm; a.calib_h = (float)sp.calib_h; a.calib_w = (float)sp.calib_w;
-  a.x_binr = sp.x_binr; a.y_binr = sp.y_binr;
-  a.gsy = (float)(0.5 * H / sp.calib_h / (double)sp.pixmm); a.gsx = (float)(0.5 * W / sp.calib_w / (double)sp.pixmm);
-  a.inv_x_binr = (float)(1.0 / (double)sp.x_binr); a.inv_y_binr = (float)(1.0 / (double)sp.y_binr);
+  ShadeArgs a = make_shade_args(sp, B, H, W);
+  a.z = z;
   const dim3 grid((npix + 255) / 256, B);
   hipLaunchKernelGGL(shade_raw_kernel, grid, dim3(256), 0, st, a, ws_raw, ws_gdir);
   if (hipError_t e = run_shadow_rays(sw, sp, z, mask, gel, ws_gdir, ws_shadow, B, st); e != hipSuccess) return e;

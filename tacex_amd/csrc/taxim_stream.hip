@@ -26,6 +26,9 @@
 // Summation order of every level equals the band kernels / the tiled tail (taps ascending, fmaf chains), so the deformed gel
 // is bit-identical to theirs.  Reference semantics: TT:464-471 (levels + restore), TT:411 (reflect padding: the strip loads
 // rows / columns at REFLECTED coordinates, a symmetric kernel keeps the halo mirror-symmetric), TT:475-503, 237-258 (shading).
+//
+// Shared steps: the fused level sets and their instantiations - with_stream_set, tacex_internal.h; the shading argument block and the
+// observation finish - taxim_device.h; wave scans - wave_ops.h.  The contact rule (taxim_device.h) stays written out in the kernel's body.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
@@ -38,7 +41,7 @@
 
 namespace tacex {
 
-constexpr int kStreamPx = 3;         // pixels per lane
+constexpr int kStreamPx = 3;        // pixels per lane
 constexpr int kStreamWaves = 4;      // waves per workgroup (independent of each other)
 constexpr int kStreamObsActive = 3;  // observation rows a frame row can contribute to (down-sampling factor >= 2)
 
@@ -879,7 +882,7 @@ __global__ __launch_bounds__(64 * kStreamWaves, MINW) void taxim_stream_kernel(S
             m = valid[i] && S[i] < thr_eff;
           } else {
             const float J = fmin_raw(S[i], gl[i]);
-            m = valid[i] && ((J - gl[i]) < thr) && (S[i] < 0.0f);  // TT:457-461
+            m = valid[i] && ((J - gl[i]) < thr) && (S[i] < 0.0f);  // TT:457-461; this kernel's own text of contact_mask, taxim_device.h
           }
           mrow[i] = m ? 1 : 0;
 #ifndef TACEX_STREAM_NO_CONTACT_STATS
@@ -974,7 +977,7 @@ __global__ __launch_bounds__(64 * kStreamWaves, MINW) void taxim_stream_kernel(S
               out[i] = Si < thr_eff ? Si : out[i];
             } else {
               const float J = fmin_raw(Si, gl[i]);
-              out[i] = (((J - gl[i]) < thr) && (Si < 0.0f)) ? J : out[i];
+              out[i] = (((J - gl[i]) < thr) && (Si < 0.0f)) ? J : out[i];  // (contact_mask, written out as above)
             }
           }
         }
@@ -1177,53 +1180,34 @@ __global__ __launch_bounds__(256) void obs_finish_stream_kernel(const float* __r
                                                                const int* __restrict__ strip_q0, const int* __restrict__ strip_nq,
                                                                const int* __restrict__ seg_oa, const int* __restrict__ seg_ob,
                                                                int nstrips, int nseg, int nrows, int ncols) {
-  const int oh = T.oh, ow = T.ow;
-  const int cell = blockIdx.x * blockDim.x + threadIdx.x;
-  if (cell >= oh * ow) return;
-  const int b = blockIdx.y;
-  const int oy = cell / ow, ox = cell - oy * ow;
-  float a0 = 0.0f, a1 = 0.0f, a2 = 0.0f;
-  for (int s = 0; s < nstrips; ++s) {
-    const int qi = ox - strip_q0[s];
-    if (qi < 0 || qi >= strip_nq[s]) continue;
-    for (int g = 0; g < nseg; ++g) {
-      if (oy < seg_oa[g] || oy > seg_ob[g]) continue;
-      const size_t blk = ((size_t)b * nstrips + s) * nseg + g;
-      const float* pp = part + blk * ((size_t)nrows * ncols * 3) + ((size_t)(oy - seg_oa[g]) * ncols + qi) * 3;
-      a0 += pp[0]; a1 += pp[1]; a2 += pp[2];
+  obs_finish_cell<U8>(obs_v, T, [&](int b, int oy, int ox, float& a0, float& a1, float& a2) {
+    for (int s = 0; s < nstrips; ++s) {
+      const int qi = ox - strip_q0[s];
+      if (qi < 0 || qi >= strip_nq[s]) continue;
+      for (int g = 0; g < nseg; ++g) {
+        if (oy < seg_oa[g] || oy > seg_ob[g]) continue;
+        const size_t blk = ((size_t)b * nstrips + s) * nseg + g;
+        const float* pp = part + blk * ((size_t)nrows * ncols * 3) + ((size_t)(oy - seg_oa[g]) * ncols + qi) * 3;
+        a0 += pp[0]; a1 += pp[1]; a2 += pp[2];
+      }
     }
-  }
-  const float nrm = T.xsum[ox] * T.ysum[oy];
-  const size_t oi = ((size_t)b * (oh * ow) + cell) * 3;
-  if constexpr (U8) {  // RGB is clipped to [0,1] (TT:257-258), so is every convex combination of it
-    uint8_t* o = static_cast<uint8_t*>(obs_v) + oi;
-    o[0] = (uint8_t)(a0 / nrm * 255.0f + 0.5f); o[1] = (uint8_t)(a1 / nrm * 255.0f + 0.5f); o[2] = (uint8_t)(a2 / nrm * 255.0f + 0.5f);
-  } else {
-    float* o = static_cast<float*>(obs_v) + oi;
-    o[0] = a0 / nrm; o[1] = a1 / nrm; o[2] = a2 / nrm;
-  }
+  });
 }
 
 // ------------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------------
-template <int ROLE, int... KS>
+template <int ROLE, bool ST, int... KS>
+constexpr StreamCfg<ROLE, KS...> stream_cfg(FusedSet<ST, KS...>) { return {}; }  // ROLE's configuration of a set of with_stream_set
+
+template <typename C>  // C: a StreamCfg
 static bool stream_geometry_t(int W, int* nstrips, int* strip_w) {
-  using C = StreamCfg<ROLE, KS...>;
   int ns = (W + C::VW - 1) / C::VW;
   int sw = (((W + ns - 1) / ns) + 3) & ~3;
   if (sw > C::VW) { ++ns; sw = (((W + ns - 1) / ns) + 3) & ~3; }
   *nstrips = ns;
   *strip_w = sw;
   return sw <= C::VW;
-}
-
-// fused level sets with a streaming instantiation (the same sets the tiled tail covers)
-static int stream_variant(int n_fused, int k0) {
-  if (n_fused == 4 && k0 == 9) return 0;   // <9,5,3,5>  320x240
-  if (n_fused == 3 && k0 == 9) return 1;   // <9,5,9>    640x480 (k = 15 stays a band level)
-  if (n_fused == 3 && k0 == 5) return 2;   // <5,3,5>    320x240 with k = 9 as a band level (three waves per SIMD)
-  return -1;
 }
 
 static bool stream_split() {
@@ -1233,25 +1217,20 @@ static bool stream_split() {
 
 bool stream_supported(int n_fused, int k0, int H, int W) {
   static const int en = getenv("TACEX_TAIL_STREAM") ? atoi(getenv("TACEX_TAIL_STREAM")) : 1;
-  return en != 0 && stream_variant(n_fused, k0) >= 0 && H >= 16 && W >= 16 && W % 4 == 0;
+  return en != 0 && with_stream_set(n_fused, k0, false, [](auto) { return true; }) && H >= 16 && W >= 16 && W % 4 == 0;
 }
 
 // geometry of the kernel that SHADES (strip layout of the RGB / observation partial sums) and of the one that runs the LEVELS
 // (strip layout of the FOTS partial records); identical in fused mode
 bool stream_geometry(int n_fused, int k0, int W, int* nstrips, int* strip_w, int* lv_nstrips, int* lv_strip_w) {
-  const int v = stream_variant(n_fused, k0);
-  if (v < 0) return false;
-  if (stream_split()) {
-    if (!stream_geometry_t<kStreamShade>(W, nstrips, strip_w)) return false;
-    return v == 0 ? stream_geometry_t<kStreamLevels, 9, 5, 3, 5>(W, lv_nstrips, lv_strip_w)
-         : v == 1 ? stream_geometry_t<kStreamLevels, 9, 5, 9>(W, lv_nstrips, lv_strip_w)
-                  : stream_geometry_t<kStreamLevels, 5, 3, 5>(W, lv_nstrips, lv_strip_w);
-  }
-  const bool ok = v == 0 ? stream_geometry_t<kStreamFused, 9, 5, 3, 5>(W, nstrips, strip_w)
-                : v == 1 ? stream_geometry_t<kStreamFused, 9, 5, 9>(W, nstrips, strip_w)
-                         : stream_geometry_t<kStreamFused, 5, 3, 5>(W, nstrips, strip_w);
-  *lv_nstrips = *nstrips; *lv_strip_w = *strip_w;
-  return ok;
+  return with_stream_set(n_fused, k0, false, [&](auto s) {
+    if (stream_split())
+      return stream_geometry_t<StreamCfg<kStreamShade>>(W, nstrips, strip_w) &&
+             stream_geometry_t<decltype(stream_cfg<kStreamLevels>(s))>(W, lv_nstrips, lv_strip_w);
+    const bool ok = stream_geometry_t<decltype(stream_cfg<kStreamFused>(s))>(W, nstrips, strip_w);
+    *lv_nstrips = *nstrips; *lv_strip_w = *strip_w;
+    return ok;
+  });
 }
 
 // vertical segments per strip: enough waves to give every SIMD `per_simd` of them, at most kStreamMaxSeg; a segment costs
@@ -1267,11 +1246,15 @@ int stream_segments(int B, int nstrips, int H, int warm, int per_simd) {
 }
 // waves per SIMD the fused kernel of this level set is compiled for (sizes the segment count: a launch should bring a whole
 // number of resident rounds)
-int stream_waves_per_simd(int n_fused, int k0) { return stream_variant(n_fused, k0) == 2 ? TACEX_STREAM3_WAVES : 2; }
-// summed radii of a variant's levels (StreamCfg::sum_r of its instantiation: 9,5,3,5 / 9,5,9 / 5,3,5)
-static int variant_sum_r(int v) { return v == 0 ? 9 : (v == 1 ? 10 : 5); }
+int stream_waves_per_simd(int n_fused, int k0) {
+  return with_stream_set(n_fused, k0, 2, [](auto s) { return decltype(stream_cfg<kStreamFused>(s))::min_waves(); });
+}
+// summed radii of a streamed set's levels (0: no such set - callers ask for the set of a plan, and stream_geometry made that)
+static int stream_sum_r(int n_fused, int k0) {
+  return with_stream_set(n_fused, k0, 0, [](auto s) { return decltype(stream_cfg<kStreamFused>(s))::sum_r(); });
+}
 int stream_warm_rows(int n_fused, int k0, bool levels_kernel) {
-  const int sum_r = variant_sum_r(stream_variant(n_fused, k0));
+  const int sum_r = stream_sum_r(n_fused, k0);
   if (!stream_split()) return 2 * sum_r + 2;
   return levels_kernel ? 2 * sum_r : 2;
 }
@@ -1291,24 +1274,14 @@ static hipError_t launch_stream_k(const StreamArgs& a, hipStream_t st) {
   return hipGetLastError();
 }
 
-template <int ROLE, int... KS>
-static hipError_t launch_stream(const StreamArgs& a, bool gel_zero, hipStream_t st) {
+template <int ROLE, bool ST, int... KS>  // (the shading role of the split pair runs no levels: an empty set)
+static hipError_t launch_stream(FusedSet<ST, KS...>, const StreamArgs& a, bool gel_zero, hipStream_t st) {
   return gel_zero ? launch_stream_k<true, ROLE, KS...>(a, st) : launch_stream_k<false, ROLE, KS...>(a, st);
-}
-
-static void fill_shade_args(ShadeArgs& sh, const ShadeParams* sp, float* rgb, int B, int H, int W) {
-  sh.poly = sp->poly_dev; sh.bg = sp->bg_nhwc_dev; sh.fx = sp->fx_dev; sh.fy = sp->fy_dev; sh.rgb = rgb;
-  sh.idx_out = nullptr; sh.H = H; sh.W = W; sh.B = B; sh.nb = sp->nb; sh.pixmm = sp->pixmm;
-  sh.calib_h = (float)sp->calib_h; sh.calib_w = (float)sp->calib_w; sh.x_binr = sp->x_binr; sh.y_binr = sp->y_binr;
-  sh.gsy = (float)(0.5 * H / sp->calib_h / (double)sp->pixmm); sh.gsx = (float)(0.5 * W / sp->calib_w / (double)sp->pixmm);
-  sh.inv_x_binr = (float)(1.0 / (double)sp->x_binr); sh.inv_y_binr = (float)(1.0 / (double)sp->y_binr);
 }
 
 hipError_t run_stream_flat_image(const ShadeParams* sp, int H, int W, hipStream_t st) {
   if (!sp->flat_rgb_dev) return hipErrorInvalidValue;
-  ShadeArgs sh{};
-  fill_shade_args(sh, sp, nullptr, 1, H, W);
-  hipLaunchKernelGGL(stream_flat_image_kernel, dim3((W + 255) / 256, H), dim3(256), 0, st, sh, sp->flat_rgb_dev);
+  hipLaunchKernelGGL(stream_flat_image_kernel, dim3((W + 255) / 256, H), dim3(256), 0, st, make_shade_args(*sp, 1, H, W), sp->flat_rgb_dev);
   return hipGetLastError();
 }
 
@@ -1319,10 +1292,10 @@ static bool stream_sorted() {
 }
 
 // heaviest items first (see the kernel's "work distribution" note): the order of the B * nstrips * nseg items of a fused launch
-static hipError_t launch_stream_order(int v, const int* rows_ext, int ext_grow, int B, int nstrips, int nseg, int seg_rows, int H, int* order_buf,
+static hipError_t launch_stream_order(int sum_r, const int* rows_ext, int ext_grow, int B, int nstrips, int nseg, int seg_rows, int H, int* order_buf,
                                       hipStream_t st) {
   hipLaunchKernelGGL(stream_order_kernel, dim3(1), dim3(1024), 0, st, rows_ext, B * nstrips * nseg, nstrips * nseg, nseg, seg_rows, H,
-                     ext_grow + variant_sum_r(v) + 1, order_buf);
+                     ext_grow + sum_r + 1, order_buf);
   return hipGetLastError();
 }
 
@@ -1333,7 +1306,7 @@ hipError_t run_stream_order(const LevelDesc* lv, int n_levels, int n_fused, cons
                             int* order_buf, hipStream_t st, bool* launched) {
   *launched = false;
   if (stream_split() || !stream_sorted() || !order_buf || !lv[0].gel_zero || !rows_ext) return hipSuccess;
-  const hipError_t e = launch_stream_order(stream_variant(n_fused, lv[n_levels - n_fused].kw), rows_ext, ext_grow, B, plan.nstrips, plan.nseg,
+  const hipError_t e = launch_stream_order(stream_sum_r(n_fused, lv[n_levels - n_fused].kw), rows_ext, ext_grow, B, plan.nstrips, plan.nseg,
                                            plan.seg_rows, H, order_buf, st);
   *launched = e == hipSuccess;
   return e;
@@ -1358,7 +1331,8 @@ hipError_t run_stream_tail(const LevelDesc* lv, int n_levels, int n_fused, const
   a.zin = zin; a.hm = hm; a.gel = lv[0].gel_zero ? nullptr : gel; a.shift_a = sa; a.shift_b = sb; a.pdepth = pd;
   a.H = H; a.W = W; a.B = B; a.contact_scale = contact_scale;
   for (int i = 0; i < n_fused; ++i) a.taps[i] = lv[n_levels - n_fused + i].taps_w_dev;
-  fill_shade_args(a.sh, sp, rgb, B, H, W);
+  a.sh = make_shade_args(*sp, B, H, W);
+  a.sh.rgb = rgb;
 #ifndef TACEX_STREAM_NO_TRIM
   a.flat_rgb = sp->flat_rgb_dev;
 #endif
@@ -1385,38 +1359,32 @@ hipError_t run_stream_tail(const LevelDesc* lv, int n_levels, int n_fused, const
     f.pix_z = pix_z; f.pix_m = pix_m; f.n_markers = plan.n_markers;
     f.mk_x = plan.mk_x; f.mk_id = plan.mk_id;
   }
-  const int v = stream_variant(n_fused, lv[n_levels - n_fused].kw);
+  const int k0 = lv[n_levels - n_fused].kw;
   const bool gz = lv[0].gel_zero;
   if (!stream_split()) {
     if (order_done) {
       sh.order = order_buf;  // (run_stream_order has been issued for this launch)
     } else if (sorted && order_buf && gz && rows_ext) {
-      if (hipError_t e = launch_stream_order(v, rows_ext, ext_grow, B, sh.nstrips, sh.nseg, sh.seg_rows, H, order_buf, st); e != hipSuccess) return e;
+      if (hipError_t e = launch_stream_order(stream_sum_r(n_fused, k0), rows_ext, ext_grow, B, sh.nstrips, sh.nseg, sh.seg_rows, H, order_buf, st);
+          e != hipSuccess)
+        return e;
       sh.order = order_buf;
     }
-    if (v == 0) return launch_stream<kStreamFused, 9, 5, 3, 5>(sh, gz, st);
-    if (v == 1) return launch_stream<kStreamFused, 9, 5, 9>(sh, gz, st);
-    if (v == 2) return launch_stream<kStreamFused, 5, 3, 5>(sh, gz, st);
-    return hipErrorInvalidValue;
+    return with_stream_set(n_fused, k0, hipErrorInvalidValue, [&](auto s) { return launch_stream<kStreamFused>(s, sh, gz, st); });
   }
   if (!z_last) return hipErrorInvalidValue;
   lvl.z_out = z_last;
-  hipError_t e = v == 0 ? launch_stream<kStreamLevels, 9, 5, 3, 5>(lvl, gz, st)
-               : v == 1 ? launch_stream<kStreamLevels, 9, 5, 9>(lvl, gz, st) : launch_stream<kStreamLevels, 5, 3, 5>(lvl, gz, st);
-  if (e != hipSuccess) return e;
+  if (hipError_t e = with_stream_set(n_fused, k0, hipErrorInvalidValue, [&](auto s) { return launch_stream<kStreamLevels>(s, lvl, gz, st); });
+      e != hipSuccess)
+    return e;
   sh.zin = z_last;
-  return launch_stream<kStreamShade>(sh, true, st);
+  return launch_stream<kStreamShade>(FusedSet<true>{}, sh, true, st);
 }
 
 hipError_t run_obs_finish_stream(const float* part, void* obs, bool u8, const StreamPlan& plan, int B, hipStream_t st) {
-  const dim3 grid((plan.obs.oh * plan.obs.ow + 255) / 256, B);
-  if (u8)
-    hipLaunchKernelGGL(obs_finish_stream_kernel<true>, grid, dim3(256), 0, st, part, obs, plan.obs, plan.obs_strip_q0, plan.obs_strip_nq,
-                       plan.obs_seg_oa, plan.obs_seg_ob, plan.nstrips, plan.nseg, plan.obs_nrows, plan.obs_ncols);
-  else
-    hipLaunchKernelGGL(obs_finish_stream_kernel<false>, grid, dim3(256), 0, st, part, obs, plan.obs, plan.obs_strip_q0, plan.obs_strip_nq,
-                       plan.obs_seg_oa, plan.obs_seg_ob, plan.nstrips, plan.nseg, plan.obs_nrows, plan.obs_ncols);
-  return hipGetLastError();
+  return launch_obs_finish(u8, obs_finish_stream_kernel<true>, obs_finish_stream_kernel<false>, plan.obs, B, st, part, obs, plan.obs,
+                           plan.obs_strip_q0, plan.obs_strip_nq, plan.obs_seg_oa, plan.obs_seg_ob, plan.nstrips, plan.nseg, plan.obs_nrows,
+                           plan.obs_ncols);
 }
 
 #ifdef TACEX_STREAM_PROBE_DEEP

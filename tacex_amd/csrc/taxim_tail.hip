@@ -8,6 +8,9 @@
 // Reference semantics per level: Z = G(Z); Z[M] = J[M]  (TT:464-467), final Z = G(Z) without restore (TT:468-471),
 // reflect padding at the IMAGE border at every level (TT:411) - reproduced by loading input, J and M at reflected
 // coordinates (a symmetric blur keeps the halo mirror-symmetric); then normals/bins/polynomial/background/clip.
+//
+// Shared steps: S, J and M of the contact rule, the shading with its argument block and the observation finish - taxim_device.h;
+// the fused level sets and their instantiations - with_fused_set, tacex_internal.h; wave scans - wave_ops.h.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
@@ -35,11 +38,7 @@ constexpr int kTailThreads = 512;
 // at the 80-VGPR budget (3 per CU, 31 spilled VGPRs) 329 us - the third workgroup does not pay while the epilogue
 // spills, so the cached layout stays the default.
 constexpr bool kTailCacheJ = true;
-constexpr int kTailWavesPerSimd = kTailCacheJ ? 4 : 6;  // register budget: 128 / 80 VGPRs  // register budget: 128 / 80 VGPRs
-// observation cells a 64 x 32 tile can overlap when the down-sampling factor is >= 7.5 (y) / >= 8 (x): tile / scale + 3
-// (per tail instantiation: TailCfg::ONRY / ONCX; 8 x 11 for the 320x240 tail, 6 x 7 for the 640x480 one whose filters are longer)
-// longest triangle filter the fused observation handles (taps per output row / column); longer ones take the two-pass resize
-// (TailCfg::OKY / OKX: 16 / 24 taps at 320x240 -> 32x32, 32 / 44 at 640x480 -> 32x32)
+constexpr int kTailWavesPerSimd = kTailCacheJ ? 4 : 6;  // register budget: 128 / 80 VGPRs
 
 struct TailArgs {
   const float* zin;      // (B,H,W) output of the last band-kernel level
@@ -97,6 +96,9 @@ struct TailCfg {
   }
 };
 
+template <bool ST, int... KS>
+constexpr TailCfg<KS...> tail_cfg(FusedSet<ST, KS...>) { return {}; }  // the configuration of a set of with_fused_set
+
 template <int... KS>
 __global__ __launch_bounds__(kTailThreads, kTailWavesPerSimd) void taxim_tail_kernel(TailArgs a) {
   using C = TailCfg<KS...>;
@@ -117,7 +119,7 @@ __global__ __launch_bounds__(kTailThreads, kTailWavesPerSimd) void taxim_tail_ke
   const int ty0 = (tix / ntx) * TH, tx0 = (tix % ntx) * TW;
   const size_t fo = (size_t)frame * H * W;
   const float sa = a.shift_a[frame], sb = a.shift_b[frame];
-  const float thr = -a.pdepth[frame] * a.contact_scale;  // TT:459
+  const float thr = contact_threshold(a.pdepth[frame], a.contact_scale);
   const float* __restrict__ zin = a.zin + fo;
   const float* __restrict__ hm = a.hm + fo;
   const int gy0 = ty0 - HLY, gx0 = tx0 - HLX;  // global coords of region cell (0,0)
@@ -213,10 +215,10 @@ __global__ __launch_bounds__(kTailThreads, kTailWavesPerSimd) void taxim_tail_ke
         uint8_t mk[4];
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
-          const float S = (hv[ps][k] - sa) - sb;
-          const float J = fmin_raw(S, gv[ps][k]);
+          const float S = contact_shifted(hv[ps][k], sa, sb);
+          const float J = contact_input<true>(S, gv[ps][k]);
           Jv[k] = J;
-          mk[k] = (((J - gv[ps][k]) < thr) && (S < 0.0f)) ? 1 : 0;  // TT:457-461
+          mk[k] = contact_mask(S, J, gv[ps][k], thr) ? 1 : 0;
         }
         if constexpr (kTailCacheJ) {
           *reinterpret_cast<v4f*>(bufJ + ly * P + PADX + lx) = Jv;
@@ -270,7 +272,7 @@ __global__ __launch_bounds__(kTailThreads, kTailWavesPerSimd) void taxim_tail_ke
             }
 #pragma unroll
             for (int k = 0; k < 4; ++k)
-              if (bits & (1u << k)) o[k] = fmin_raw((hq[k] - sa) - sb, gq[k]);
+              if (bits & (1u << k)) o[k] = contact_input<true>(contact_shifted(hq[k], sa, sb), gq[k]);
           }
         }
       }
@@ -519,34 +521,21 @@ __global__ __launch_bounds__(kTailThreads, kTailWavesPerSimd) void taxim_tail_ke
 template <bool U8>
 __global__ __launch_bounds__(256) void obs_finish_kernel(const float* __restrict__ part, void* __restrict__ obs_v, ObsTables T,
                                                         int H, int W, int ntx, int nty, int TW, int TH, int NRY, int NCX) {
-  const int oh = T.oh, ow = T.ow;
-  const int cell = blockIdx.x * blockDim.x + threadIdx.x;
-  if (cell >= oh * ow) return;
-  const int b = blockIdx.y;
-  const int oy = cell / ow, ox = cell - oy * ow;
-  const float scy = (float)H / oh, scx = (float)W / ow;
-  const int ylo = T.ylo[oy], yhi = ylo + T.ycnt[oy], xlo = T.xlo[ox], xhi = xlo + T.xcnt[ox];
-  float a0 = 0.0f, a1 = 0.0f, a2 = 0.0f;
-  for (int ty = ylo / TH; ty <= (yhi - 1) / TH; ++ty) {
-    const int oy0 = max(0, (int)floorf(((float)(ty * TH) - scy) / scy));
-    for (int tx = xlo / TW; tx <= (xhi - 1) / TW; ++tx) {
-      const int ox0 = max(0, (int)floorf(((float)(tx * TW) - scx) / scx));
-      const int j = oy - oy0, q = ox - ox0;
-      if (j < 0 || j >= NRY || q < 0 || q >= NCX) continue;  // cannot happen for the scales run_tail accepts
-      const size_t tile = ((size_t)b * nty + ty) * ntx + tx;
-      const float* pp = part + (tile * (NRY * NCX) + (unsigned)(j * NCX + q)) * 3;
-      a0 += pp[0]; a1 += pp[1]; a2 += pp[2];
+  obs_finish_cell<U8>(obs_v, T, [&](int b, int oy, int ox, float& a0, float& a1, float& a2) {
+    const float scy = (float)H / T.oh, scx = (float)W / T.ow;
+    const int ylo = T.ylo[oy], yhi = ylo + T.ycnt[oy], xlo = T.xlo[ox], xhi = xlo + T.xcnt[ox];
+    for (int ty = ylo / TH; ty <= (yhi - 1) / TH; ++ty) {
+      const int oy0 = max(0, (int)floorf(((float)(ty * TH) - scy) / scy));
+      for (int tx = xlo / TW; tx <= (xhi - 1) / TW; ++tx) {
+        const int ox0 = max(0, (int)floorf(((float)(tx * TW) - scx) / scx));
+        const int j = oy - oy0, q = ox - ox0;
+        if (j < 0 || j >= NRY || q < 0 || q >= NCX) continue;  // cannot happen for the scales run_tail accepts
+        const size_t tile = ((size_t)b * nty + ty) * ntx + tx;
+        const float* pp = part + (tile * (NRY * NCX) + (unsigned)(j * NCX + q)) * 3;
+        a0 += pp[0]; a1 += pp[1]; a2 += pp[2];
+      }
     }
-  }
-  const float nrm = T.xsum[ox] * T.ysum[oy];
-  const size_t oi = ((size_t)b * (oh * ow) + cell) * 3;
-  if constexpr (U8) {  // RGB is clipped to [0,1] (TT:257-258), so is every convex combination of it
-    uint8_t* o = static_cast<uint8_t*>(obs_v) + oi;
-    o[0] = (uint8_t)(a0 / nrm * 255.0f + 0.5f); o[1] = (uint8_t)(a1 / nrm * 255.0f + 0.5f); o[2] = (uint8_t)(a2 / nrm * 255.0f + 0.5f);
-  } else {
-    float* o = static_cast<float*>(obs_v) + oi;
-    o[0] = a0 / nrm; o[1] = a1 / nrm; o[2] = a2 / nrm;
-  }
+  });
 }
 
 __global__ __launch_bounds__(256) void obs_to_u8_kernel(const float* __restrict__ src, uint8_t* __restrict__ dst, size_t n) {
@@ -562,26 +551,18 @@ hipError_t run_obs_to_u8(const float* src, uint8_t* dst, size_t n, hipStream_t s
 
 // observation geometry of the fused tail instantiation for (n_fused, first fused k); false: no room to stage the observation
 bool tail_obs_geom(int n_fused, int k0, int* nry, int* ncx, int* ky, int* kx) {
-  auto set = [&](auto cfg) {
-    using C = decltype(cfg);
+  return with_fused_set(n_fused, k0, false, [&](auto s) {
+    using C = decltype(tail_cfg(s));
     *nry = C::ONRY; *ncx = C::ONCX; *ky = C::OKY; *kx = C::OKX;
     return C::obs_ok;
-  };
-  if (n_fused == 4 && k0 == 9) return set(TailCfg<9, 5, 3, 5>{});
-  if (n_fused == 4 && k0 == 15) return set(TailCfg<15, 9, 5, 9>{});
-  if (n_fused == 3 && k0 == 9) return set(TailCfg<9, 5, 9>{});
-  if (n_fused == 3 && k0 == 5) return set(TailCfg<5, 3, 5>{});
-  return false;
+  });
 }
 
 hipError_t run_obs_finish(const float* part, void* obs, bool u8, const ObsTables& t, int H, int W, int B, int nry, int ncx,
                           hipStream_t st) {
   const int TW = 64, TH = 32;
   const int ntx = (W + TW - 1) / TW, nty = (H + TH - 1) / TH;
-  const dim3 grid((t.oh * t.ow + 255) / 256, B);
-  if (u8) hipLaunchKernelGGL(obs_finish_kernel<true>, grid, dim3(256), 0, st, part, obs, t, H, W, ntx, nty, TW, TH, nry, ncx);
-  else hipLaunchKernelGGL(obs_finish_kernel<false>, grid, dim3(256), 0, st, part, obs, t, H, W, ntx, nty, TW, TH, nry, ncx);
-  return hipGetLastError();
+  return launch_obs_finish(u8, obs_finish_kernel<true>, obs_finish_kernel<false>, t, B, st, part, obs, t, H, W, ntx, nty, TW, TH, nry, ncx);
 }
 
 // can the fused tail (n_fused levels, first fused k) produce this observation?  Cells per tile and filter lengths must fit
@@ -599,23 +580,14 @@ size_t obs_part_floats(int H, int W, int B, int nry, int ncx) {
   return (size_t)B * tail_tiles_per_frame(H, W) * nry * ncx * 3;
 }
 
-template <int... KS>
-static hipError_t launch_tail(const TailArgs& a0, hipStream_t st) {
+template <bool ST, int... KS>
+static hipError_t launch_tail(FusedSet<ST, KS...>, const TailArgs& a, hipStream_t st) {
   using C = TailCfg<KS...>;
-  if (!C::obs_ok && a0.obs_part) return hipErrorInvalidValue;  // callers check obs_fusable() first
-  TailArgs a = a0;
+  if (!C::obs_ok && a.obs_part) return hipErrorInvalidValue;  // callers check obs_fusable() first
   const int ntx = (a.W + C::TW - 1) / C::TW, nty = (a.H + C::TH - 1) / C::TH;
   auto kern = taxim_tail_kernel<KS...>;
-  // > 64 KB of dynamic LDS is an opt-in per kernel AND device: one flag per device (contexts on several GPUs in one process)
-  static bool attr_done[64] = {};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-  if (!attr_done[dev]) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)C::lds_bytes());
-    if (e != hipSuccess) return e;
-    attr_done[dev] = true;
-  }
+  static size_t granted[64] = {};
+  if (hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), C::lds_bytes(), granted); e != hipSuccess) return e;
   hipLaunchKernelGGL(kern, dim3(ntx * nty * a.B), dim3(kTailThreads), C::lds_bytes(), st, a);
   return hipGetLastError();
 }
@@ -670,18 +642,10 @@ hipError_t run_tail(const LevelDesc* lv, int n_levels, int n_fused, const float*
   a.H = H; a.W = W; a.B = B; a.contact_scale = contact_scale;
   for (int i = 0; i < n_fused; ++i) a.taps[i] = lv[n_levels - n_fused + i].taps_w_dev;
   if (sp && rgb) {
-    a.sh.poly = sp->poly_dev; a.sh.bg = sp->bg_nhwc_dev; a.sh.fx = sp->fx_dev; a.sh.fy = sp->fy_dev; a.sh.rgb = rgb;
-    a.sh.idx_out = nullptr; a.sh.H = H; a.sh.W = W; a.sh.B = B; a.sh.nb = sp->nb; a.sh.pixmm = sp->pixmm;
-    a.sh.calib_h = (float)sp->calib_h; a.sh.calib_w = (float)sp->calib_w; a.sh.x_binr = sp->x_binr; a.sh.y_binr = sp->y_binr;
-    a.sh.gsy = (float)(0.5 * H / sp->calib_h / (double)sp->pixmm); a.sh.gsx = (float)(0.5 * W / sp->calib_w / (double)sp->pixmm);
-    a.sh.inv_x_binr = (float)(1.0 / (double)sp->x_binr); a.sh.inv_y_binr = (float)(1.0 / (double)sp->y_binr);
+    a.sh = make_shade_args(*sp, B, H, W);
+    a.sh.rgb = rgb;
   }
-  const int k0 = lv[n_levels - n_fused].kw;
-  if (n_fused == 4 && k0 == 9) return launch_tail<9, 5, 3, 5>(a, st);
-  if (n_fused == 4 && k0 == 15) return launch_tail<15, 9, 5, 9>(a, st);
-  if (n_fused == 3 && k0 == 9) return launch_tail<9, 5, 9>(a, st);
-  if (n_fused == 3 && k0 == 5) return launch_tail<5, 3, 5>(a, st);
-  return hipErrorInvalidValue;
+  return with_fused_set(n_fused, lv[n_levels - n_fused].kw, hipErrorInvalidValue, [&](auto s) { return launch_tail(s, a, st); });
 }
 
 }  // namespace tacex
