@@ -1199,6 +1199,54 @@ int tacex_height_map_from_sdf_scene(const float* voxels_dev, int num_voxels, con
                                     float gelpad_height_m, float gelpad_to_camera_min_distance_m, float* hm_mm_dev, float* frame_min_dev,
                                     float* indent_mm_dev, int32_t* frame_rows_dev, int num_frames, int height, int width, void* stream);
 
+/* tacex_height_map_from_sdf_scene, and which slot every pixel shows: the same arguments, contract, launches and bits in hm_mm_dev,
+ * frame_min_dev, indent_mm_dev and frame_rows_dev (the same kernel source, instantiated with the owner), plus
+ *   part_map_dev (B,H,W) uint8, not NULL: the OWNER of every pixel, a slot index 0..K-1, or 255 where hm is far_clip.
+ * The owner follows the comparison inside smin at every fold.  In every evaluation of f(z):
+ *     own = 255
+ *     for every live slot s in slot order that is evaluated (one that the rule "a union slot with blend not > 0 that is not inside
+ *     and has sqrt(e2) >= f" skips is not), with f the value BEFORE the fold and u the slot's value:
+ *         union:      if u < f:    own = s          (smin_blend(f, u) takes its second argument)
+ *         subtract:   if u < -f:   own = s          (smin_blend(-f, u))
+ *         intersect:  if -u < -f:  own = s          (smin_blend(-f, -u))
+ *     the same rule with blend > 0 and without.  s is the slot's index in 0..K-1, not its position among the tile's live slots.
+ *   part_map = own of the evaluation that assigned the pixel's depth - the one with f(z) < tol_mm, or the last one where the
+ *   grazing-ray rule gave the depth -, and 255 wherever hm == far_clip: a tile without a live union slot, a pixel without an
+ *   interval, a ray that hit nothing, a depth >= far_clip.
+ * So the owner is the part one sees: of a union the nearer part, of a subtraction the wall of the cut, of an intersection the
+ * clipping part.  One byte per pixel is stored by the lane that stores the depth; no atomics, no dependence on the batch.
+ * Returns 2 before any HIP call, writing nothing, for what tacex_height_map_from_sdf_scene refuses and for a NULL part_map_dev.
+ * Added without a change of TACEX_ABI_VERSION: a caller detects it by looking the symbol up. */
+int tacex_height_map_from_sdf_scene_parts(const float* voxels_dev, int num_voxels, const int32_t* volumes_i_dev, const float* volumes_f_dev,
+                                          int num_volumes, const int32_t* part_ids_dev, const float* part_pose_dev,
+                                          const int32_t* part_ops_dev, int num_slots, float pixmm, float near_clip_mm, float far_clip_mm,
+                                          int max_steps, float tol_mm, float gelpad_height_m, float gelpad_to_camera_min_distance_m,
+                                          float* hm_mm_dev, float* frame_min_dev, float* indent_mm_dev, int32_t* frame_rows_dev,
+                                          uint8_t* part_map_dev, int num_frames, int height, int width, void* stream);
+
+/* Per-part contact records: tacex_contact_field with a LABEL per pixel, one slip row and one record per (frame, label), in ONE launch on
+ * `stream` (tacex_amd/csrc/contact_parts.hip).  Inputs, per-pixel float32 operations, float64 sums, gel table, pixmm, frame_rows_dev and
+ * the 16 record slots are those of tacex_contact_field; there are no cells.  L = num_labels (1..8).
+ *   labels_dev (B,H,W) uint8: the pixel's label, e.g. the part map of tacex_height_map_from_sdf_scene_parts;
+ *   slip_dev (B,L,5) f32: a slip row [dx_mm, dy_mm, dtheta_rad, cx_px, cy_px] per label; NULL: all zero.
+ * Per pixel: S, d, p as in tacex_contact_field; where d > 0 and the label l is < L, the shear (tx, ty) and `slips` with the slip row
+ *   (b, l).  A pixel whose label is >= L has no shear (tx = ty = 0, slips = false) and enters no record: e.g. where the gel memory
+ *   leaves an imprint and no part was hit.
+ * record_dev (B,L,16) f64: record (b, l) holds the slots of tacex_contact_field over the pixels of label l alone - the same sums,
+ *   the same torque origin (the image centre), the same values for a label without pressure ([9], [10] the image centre, [14], [15]
+ *   zero).  An id outside the gel table: all L records of the env and its image are zero.
+ * image_dev (B,H,W,3) f32 [Pa], nullable: (tx, ty, -p) of every pixel, (0, 0, -p) where the label is >= L; every pixel is written.
+ * Sums are float64 in an order fixed by (H, W) alone, without atomics; a record does not depend on the batch, on the other labels'
+ * slip rows, on frame_rows_dev being given, or on the alignment of image_dev.  With L = 1, every label 0 and slip_dev (B,1,5) holding
+ * the rows of a (B,5) table, record_dev[:,0] and image_dev are the bits of tacex_contact_field with that table.
+ * 16-byte loads are used when W % 4 == 0, hm_mm_dev is 16-byte and labels_dev 4-byte aligned; the same bits otherwise.
+ * Returns 2 before any HIP call for a NULL hm_mm_dev, frame_min_dev, indent_mm_dev, gels_dev, labels_dev or record_dev, num_gels,
+ * num_frames, height or width <= 0, num_labels outside 1..8, pixmm <= 0 (or NaN).  Added without a change of TACEX_ABI_VERSION. */
+int tacex_contact_field_parts(const float* hm_mm_dev, const float* frame_min_dev, const float* indent_mm_dev, const float* gels_dev,
+                              int num_gels, const int32_t* gel_ids_dev, const uint8_t* labels_dev, int num_labels, const float* slip_dev,
+                              float pixmm, const int32_t* frame_rows_dev, double* record_dev, float* image_dev, int num_frames, int height,
+                              int width, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -187,6 +187,9 @@ SIGNATURES = {
     "tacex_height_map_from_relief": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _f, _f, _f, _f, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "tacex_height_map_from_sdf": (_i, [_vp, _i, _vp, _vp, _i, _vp, _vp, _f, _f, _f, _i, _f, _f, _f, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "tacex_height_map_from_sdf_scene": (_i, [_vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _i, _f, _f, _f, _i, _f, _f, _f, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
+    "tacex_height_map_from_sdf_scene_parts": (_i, [_vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _i, _f, _f, _f, _i, _f, _f, _f, _vp, _vp, _vp, _vp, _vp, _i,
+                                                   _i, _i, _vp]),
+    "tacex_contact_field_parts": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _f, _vp, _vp, _vp, _i, _i, _i, _vp]),
 }
 
 _lib = None

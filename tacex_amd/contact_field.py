@@ -130,6 +130,32 @@ class ContactField:
         return self.record[:, 15]
 
 
+class PartContactField(ContactField):
+    """What `TactileContactModel.parts` returns: `record` (B,L,16) float64, one record of `tacex_contact_field`'s slots per env and
+    label (over the pixels of that label alone), and `image` (B,H,W,3) float32 traction [Pa] or None; `cells` is None (the call has
+    none).  The accessors are `ContactField`'s, shaped (B, L, ...)."""
+
+    def __init__(self, record: torch.Tensor, image: torch.Tensor | None):
+        super().__init__(record, None, image)
+
+    force = property(lambda self: self.record[..., 0:3], doc="(B,L,3) net force on the pad through each part [N].")
+    normal_force = property(lambda self: self.record[..., 6], doc="(B,L) Fn >= 0 [N].")
+    friction_force = property(lambda self: self.record[..., 0:2], doc="(B,L,2) net shear force (x, y) [N].")
+    torque = property(lambda self: self.record[..., 3:6], doc="(B,L,3) torque about the image centre on the pad face [N m].")
+    contact_area = property(lambda self: self.record[..., 7], doc="(B,L) [m^2].")
+    num_contact = property(lambda self: self.record[..., 8])
+    centre_of_pressure = property(lambda self: self.record[..., 9:11], doc="(B,L,2) (x, y) in pixels; the image centre without contact.")
+    max_penetration = property(lambda self: self.record[..., 11], doc="(B,L) [mm].")
+    volume = property(lambda self: self.record[..., 12], doc="(B,L) penetrated volume [mm^3].")
+    num_slipping = property(lambda self: self.record[..., 13])
+    slip_ratio = property(lambda self: self.record[..., 13] / self.record[..., 8].clamp(min=1.0), doc="(B,L) slipping / contact pixels.")
+    patch_angle = property(lambda self: self.record[..., 14], doc="(B,L) [rad].")
+    patch_aspect = property(lambda self: self.record[..., 15], doc="(B,L) short / long axis of the pressure patch.")
+
+
+MAX_LABELS = 8
+
+
 def slip_from_fots(marker_sim) -> torch.Tensor:
     """The (B,5) slip table [dx_mm, dy_mm, dtheta_rad, cx_px, cy_px] from a `FOTSMarkerSimulator`'s trajectory state
     [len, x0, y0, th0, xl, yl, thl, n] (contact centroids in mm from the image centre, indenter yaw): the shear and twist since first
@@ -204,3 +230,41 @@ class TactileContactModel:
                                                _lib.current_stream_handle(dev))
         _lib.check(rc, "tacex_contact_field")
         return ContactField(record, cells, img)
+
+    def parts(self, hm: torch.Tensor, frame_min: torch.Tensor, indent: torch.Tensor, labels: torch.Tensor, num_labels: int,
+              slip: torch.Tensor | None = None, frame_rows: torch.Tensor | None = None,
+              image: bool | torch.Tensor = False) -> PartContactField:
+        """One launch of `tacex_contact_field_parts` on the current stream: a record per env and label.  `hm`, `frame_min`, `indent`,
+        `frame_rows` and `image` as in `__call__`; `labels` (num_frames,H,W) uint8, the label of every pixel (e.g.
+        `SdfSceneSource.part_map`); `num_labels` L in 1..8 - a pixel whose label is >= L has no shear and enters no record; `slip`
+        (num_frames,L,5) float32, a slip row per label, or None (no shear).  The grid has no part in this call."""
+        B, dev = self.num_frames, self._table.device
+
+        def arg(name, t, shape, dtype=torch.float32):
+            return _stage.check_tensor("TactileContactModel.parts", name, t, shape, dtype, dev)
+
+        if not 1 <= int(num_labels) <= MAX_LABELS:
+            raise ValueError(f"TactileContactModel.parts: num_labels = {num_labels} (must be 1..{MAX_LABELS})")
+        L = int(num_labels)
+        arg("hm", hm, (B, "H", "W"))
+        H, W = int(hm.shape[1]), int(hm.shape[2])
+        arg("frame_min", frame_min, (B,))
+        arg("indent", indent, (B,))
+        arg("labels", labels, (B, H, W), torch.uint8)
+        if slip is not None:
+            arg("slip", slip, (B, L, 5))
+        if frame_rows is not None:
+            arg("frame_rows", frame_rows, (B, 4), torch.int32)
+        gel_ids, gels = self._table.check()
+        img = None
+        if isinstance(image, torch.Tensor):
+            img = arg("image", image, (B, H, W, 3))
+        elif image:
+            img = torch.empty((B, H, W, 3), dtype=torch.float32, device=dev)
+        record = torch.empty((B, L, 16), dtype=torch.float64, device=dev)
+        with torch.cuda.device(dev):
+            rc = self._lib.tacex_contact_field_parts(_lib.ptr(hm), _lib.ptr(frame_min), _lib.ptr(indent), _lib.ptr(gels), int(gels.shape[0]),
+                                                     _lib.ptr(gel_ids), _lib.ptr(labels), L, _lib.ptr(slip), self.pixmm, _lib.ptr(frame_rows),
+                                                     _lib.ptr(record), _lib.ptr(img), B, H, W, _lib.current_stream_handle(dev))
+        _lib.check(rc, "tacex_contact_field_parts")
+        return PartContactField(record, img)

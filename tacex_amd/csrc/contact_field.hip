@@ -24,6 +24,7 @@
 #include <math.h>
 #include <stdint.h>
 
+#include "contact_terms.h"
 #include "stage_args.h"
 #include "tacex_hip.h"
 #include "tacex_internal.h"
@@ -31,16 +32,7 @@
 namespace tacex {
 namespace {
 
-constexpr int kCfBlock = 256;
-constexpr int kCfWaves = kCfBlock / 64;
-constexpr int kBandRows = 8;
-constexpr int kCfGroup = 4;   // items whose loads a thread issues together
 constexpr int kCfChunk = 32;  // pixels of a cell run that one thread adds
-constexpr int kCfSums = 14;
-constexpr int kCfRed = 18;  // doubles per wave in the LDS exchange: 14 sums, count, slipping count, maximum, one spare
-
-// float64 sums of a frame (each term is a float32 value widened to float64, or its product with pixel indices formed in float64)
-enum { kFx = 0, kFy, kFn, kP, kD, kPj, kPi, kPjj, kPii, kPij, kFni, kFnj, kFyj, kFxi };
 
 struct ContactArgs {
   const float* hm;         // (B,H,W)
@@ -57,36 +49,6 @@ struct ContactArgs {
   int num_gels, H, W, rows, cols;
   int chunks;              // chunks of kCfChunk pixels per cell run: ceil(ceil(W / cols) / kCfChunk)
 };
-
-struct ContactFrame {
-  float fmin, indent, kn, kt, mu, dx, dy, dth, cx, cy;
-};
-
-struct ContactPixel {
-  float d, p, tx, ty;
-  bool slip;
-};
-
-// one pixel of the definition (include/tacex_hip.h); h is the height map value, (i, j) its row and column
-__device__ inline ContactPixel contact_pixel(const ContactFrame& f, float pixmm, float h, int i, int j) {
-  ContactPixel o;
-  const float S = (h - f.fmin) - f.indent;
-  o.d = S < 0.0f ? -S : 0.0f;  // a NaN compares false
-  o.p = f.kn * o.d;
-  o.tx = 0.0f; o.ty = 0.0f; o.slip = false;
-  if (o.d > 0.0f) {
-    const float rx = ((float)j - f.cx) * pixmm, ry = ((float)i - f.cy) * pixmm;
-    const float ux = f.dx - f.dth * ry, uy = f.dy + f.dth * rx;
-    const float n = sqrtf(ux * ux + uy * uy);
-    const float stick = f.kt * n, cone = f.mu * o.p;
-    o.slip = stick >= cone;
-    if (n != 0.0f) {
-      const float s = fminf(stick, cone) / n;
-      o.tx = ux * s; o.ty = uy * s;
-    }
-  }
-  return o;
-}
 
 template <bool kVec>
 __global__ __launch_bounds__(kCfBlock) void contact_field_kernel(ContactArgs a) {
@@ -269,57 +231,8 @@ __global__ __launch_bounds__(kCfBlock) void contact_field_kernel(ContactArgs a) 
     }
   }
 
-  // ---- the record: wave shuffles (fixed tree), then the waves in order ----
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-#pragma unroll
-    for (int k = 0; k < kCfSums; ++k) acc[k] += __shfl_down(acc[k], off, 64);
-    count += __shfl_down(count, off, 64);
-    nslip += __shfl_down(nslip, off, 64);
-    dmax = fmaxf(dmax, __shfl_down(dmax, off, 64));
-  }
-  if (lane == 0) {
-    double* w = s_red + wave * kCfRed;
-#pragma unroll
-    for (int k = 0; k < kCfSums; ++k) w[k] = acc[k];
-    w[14] = (double)count; w[15] = (double)nslip; w[16] = (double)dmax;
-  }
-  __syncthreads();
-  if (tid != 0) return;
-  double s[kCfRed];
-  for (int k = 0; k < 17; ++k) s[k] = s_red[k];
-  for (int w = 1; w < kCfWaves; ++w) {
-    const double* q = s_red + w * kCfRed;
-    for (int k = 0; k < 16; ++k) s[k] += q[k];
-    s[16] = fmax(s[16], q[16]);
-  }
-  double* rec = a.record + (size_t)frame * 16;
-  if (!valid) {
-    for (int k = 0; k < 16; ++k) rec[k] = 0.0;
-    return;
-  }
-  const double cx0 = (double)(W - 1) / 2.0, cy0 = (double)(H - 1) / 2.0;
-  const double mm = (double)a.pixmm, m = mm * 1e-3;  // pixel pitch [mm], [m]
-  rec[0] = s[kFx]; rec[1] = s[kFy]; rec[2] = -s[kFn];
-  rec[3] = -(s[kFni] - cy0 * s[kFn]) * m;                                       // sum ry fz
-  rec[4] = (s[kFnj] - cx0 * s[kFn]) * m;                                        // - sum rx fz
-  rec[5] = ((s[kFyj] - cx0 * s[kFy]) - (s[kFxi] - cy0 * s[kFx])) * m;           // sum rx fy - ry fx
-  rec[6] = s[kFn];
-  rec[7] = s[14] * (double)a.area;
-  rec[8] = s[14];
-  rec[11] = s[16];
-  rec[12] = s[kD] * (mm * mm);
-  rec[13] = s[15];
-  double copx = cx0, copy = cy0, angle = 0.0, aspect = 0.0;
-  if (s[kP] > 0.0) {
-    copx = s[kPj] / s[kP]; copy = s[kPi] / s[kP];
-    const double m20 = s[kPjj] / s[kP] - copx * copx, m02 = s[kPii] / s[kP] - copy * copy, m11 = s[kPij] / s[kP] - copx * copy;
-    angle = 0.5 * atan2(2.0 * m11, m20 - m02);
-    const double mean = 0.5 * (m20 + m02), half = 0.5 * (m20 - m02), rad = sqrt(half * half + m11 * m11);
-    const double lmax = mean + rad, lmin = mean - rad;
-    if (lmax > 0.0) aspect = sqrt(fmax(lmin, 0.0) / lmax);
-  }
-  rec[9] = copx; rec[10] = copy; rec[14] = angle; rec[15] = aspect;
+  // ---- the record: wave shuffles (fixed tree), then the waves in order (contact_terms.h) ----
+  contact_record(acc, count, nslip, dmax, s_red, a.record + (size_t)frame * 16, valid, H, W, a.pixmm, a.area);
 }
 
 int contact_field_chunks(int W, int cols) { return ((W + cols - 1) / cols + kCfChunk - 1) / kCfChunk; }

@@ -12,6 +12,9 @@
 // interval in the slot's box, five floats - stays in LDS per lane for the first kSceneCached live slots (conflict-free reads) and is
 // worked out again from the table for the others: registers cannot be indexed by a list that differs from tile to tile.  A tile no
 // union slot's box meets writes the far clip without a tap.
+// sdf_scene_kernel<true> (tacex_height_map_from_sdf_scene_parts) also says which slot every pixel shows: `own`, one more register in
+// the step loop, follows the comparison inside scene_smin at every fold, and the lane stores one byte beside its depth.  The plain
+// instantiation is the kernel as it was: nothing of the owner is compiled into it.
 // Built with -ffp-contract=off (_build.FILE_FLAGS): every product and sum of the contract is rounded to float32 on its own.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -39,6 +42,7 @@ struct SceneArgs {
   const float* pose;    // (B,K,16)
   const int* ops;       // (B,K)
   float* hm;            // (B,H,W)
+  uint8_t* parts;       // (B,H,W) the owner of every pixel (sdf_scene_kernel<true> alone)
   int num_voxels, P, K, H, W, tiles_x, tiles, max_steps;
   float pixmm, near_clip, far_clip, tol;
 };
@@ -69,6 +73,9 @@ __device__ __forceinline__ bool scene_slot_ray(const float* T, const int* I, flo
   return sdf_clip(bq, ia, hmax, par, lo, hi);
 }
 
+constexpr int kSceneNoOwner = 255;
+
+template <bool IDS>
 __global__ __launch_bounds__(256) void sdf_scene_kernel(SceneArgs a) {
   __shared__ float tab[kSceneMaxSlots][kSlotFloats];
   __shared__ int itab[kSceneMaxSlots][kSlotInts];
@@ -141,9 +148,13 @@ __global__ __launch_bounds__(256) void sdf_scene_kernel(SceneArgs a) {
   }
   __syncthreads();
   const unsigned live_mask = (unsigned)__builtin_amdgcn_readfirstlane((int)masks[0]);
-  float* __restrict__ out = a.hm + (size_t)b * ((size_t)a.H * (size_t)a.W) + (size_t)y * (size_t)a.W + (size_t)x;
+  const size_t pixel = (size_t)b * ((size_t)a.H * (size_t)a.W) + (size_t)y * (size_t)a.W + (size_t)x;
+  float* __restrict__ out = a.hm + pixel;
   if (masks[1] == 0) {  // no union slot meets the tile: nothing to hit
-    if (in_frame) *out = far_clip;
+    if (in_frame) {
+      *out = far_clip;
+      if constexpr (IDS) a.parts[pixel] = (uint8_t)kSceneNoOwner;
+    }
     return;
   }
 
@@ -171,11 +182,13 @@ __global__ __launch_bounds__(256) void sdf_scene_kernel(SceneArgs a) {
   active = active && in_frame;
 
   float depth = far_clip;
+  int owner = kSceneNoOwner;  // (IDS) `own` of the evaluation that assigned the depth
   if (active) {
     const float vox = vox_min;
     float z = lo;
     for (int n = 0; n < a.max_steps; ++n) {
       float f = kSdfTwo30;
+      int own = kSceneNoOwner;  // (IDS) the last slot whose value the comparison inside scene_smin took
       c = 0;
       for (unsigned rest = live_mask; rest; rest &= rest - 1, ++c) {
         const int s = __ffs(rest) - 1;
@@ -210,34 +223,37 @@ __global__ __launch_bounds__(256) void sdf_scene_kernel(SceneArgs a) {
           const float p = u > 0.0f ? u : 0.0f;
           u = sqrtf(e2 + (p * p));
         }
+        if constexpr (IDS) {  // scene_smin(p, q, .) takes q when q < p
+          const bool takes = op == kUnion ? u < f : op == kSubtract ? u < -f : -u < -f;
+          own = takes ? s : own;
+        }
         if (op == kUnion) f = scene_smin(f, u, blend);
         else if (op == kSubtract) f = -scene_smin(-f, u, blend);
         else f = -scene_smin(-f, -u, blend);
       }
-      if (f < a.tol) { depth = z; break; }
+      if (f < a.tol) { depth = z; owner = own; break; }
       z = z + f;
       if (!(z <= hi)) break;
-      if (n == a.max_steps - 1 && f < vox) depth = z;  // the grazing-ray rule
+      if (n == a.max_steps - 1 && f < vox) { depth = z; owner = own; }  // the grazing-ray rule
     }
   }
-  if (in_frame) *out = depth < far_clip ? depth : far_clip;
+  if (in_frame) {
+    *out = depth < far_clip ? depth : far_clip;
+    if constexpr (IDS) a.parts[pixel] = (uint8_t)(depth < far_clip ? owner : kSceneNoOwner);
+  }
 }
 
-}  // namespace
-}  // namespace tacex
-
-extern "C" int tacex_height_map_from_sdf_scene(const float* voxels_dev, int num_voxels, const int32_t* volumes_i_dev, const float* volumes_f_dev,
-                                               int num_volumes, const int32_t* part_ids_dev, const float* part_pose_dev,
-                                               const int32_t* part_ops_dev, int num_slots, float pixmm, float near_clip_mm, float far_clip_mm,
-                                               int max_steps, float tol_mm, float gelpad_height_m, float gelpad_to_camera_min_distance_m,
-                                               float* hm_mm_dev, float* frame_min_dev, float* indent_mm_dev, int32_t* frame_rows_dev,
-                                               int num_frames, int height, int width, void* stream) {
-  using namespace tacex;
-  const char* fn = "tacex_height_map_from_sdf_scene";
+// both entry points: the checks, the march (with the part map when part_map_dev is given), the frame outputs
+int run_sdf_scene(const char* fn, const float* voxels_dev, int num_voxels, const int32_t* volumes_i_dev, const float* volumes_f_dev, int num_volumes,
+                  const int32_t* part_ids_dev, const float* part_pose_dev, const int32_t* part_ops_dev, int num_slots, float pixmm,
+                  float near_clip_mm, float far_clip_mm, int max_steps, float tol_mm, float gelpad_height_m,
+                  float gelpad_to_camera_min_distance_m, float* hm_mm_dev, float* frame_min_dev, float* indent_mm_dev, int32_t* frame_rows_dev,
+                  uint8_t* part_map_dev, bool with_parts, int num_frames, int height, int width, void* stream) {
   if (null_arg(fn, "voxels_dev", voxels_dev) || null_arg(fn, "volumes_i_dev", volumes_i_dev) ||
       null_arg(fn, "volumes_f_dev", volumes_f_dev) || null_arg(fn, "part_ids_dev", part_ids_dev) ||
       null_arg(fn, "part_pose_dev", part_pose_dev) || null_arg(fn, "part_ops_dev", part_ops_dev) || null_arg(fn, "hm_mm_dev", hm_mm_dev) ||
       null_arg(fn, "frame_min_dev", frame_min_dev)) return 2;
+  if (with_parts && null_arg(fn, "part_map_dev", part_map_dev)) return 2;
   if (not_positive(fn, "num_voxels", num_voxels) || not_positive(fn, "num_volumes", num_volumes) ||
       not_positive(fn, "num_frames", num_frames) || not_positive(fn, "height", height) || not_positive(fn, "width", width)) return 2;
   if (num_slots < 1 || num_slots > kSceneMaxSlots) { set_error("%s: num_slots = %d (must be 1..%d)", fn, num_slots, kSceneMaxSlots); return 2; }
@@ -255,10 +271,12 @@ extern "C" int tacex_height_map_from_sdf_scene(const float* voxels_dev, int num_
   a.tiles = a.tiles_x * ((height + kSdfTileH - 1) / kSdfTileH);
   if ((long long)a.tiles * num_frames > 0x7fffffffll) return refuse_image_launch(fn, num_frames, height, width);
   a.voxels = voxels_dev; a.vi = volumes_i_dev; a.vf = volumes_f_dev; a.ids = part_ids_dev; a.pose = part_pose_dev; a.ops = part_ops_dev;
-  a.hm = hm_mm_dev; a.num_voxels = num_voxels; a.P = num_volumes; a.K = num_slots; a.H = height; a.W = width; a.max_steps = max_steps;
-  a.pixmm = pixmm; a.near_clip = near_clip_mm; a.far_clip = far_clip_mm; a.tol = tol_mm;
+  a.hm = hm_mm_dev; a.parts = part_map_dev; a.num_voxels = num_voxels; a.P = num_volumes; a.K = num_slots; a.H = height; a.W = width;
+  a.max_steps = max_steps; a.pixmm = pixmm; a.near_clip = near_clip_mm; a.far_clip = far_clip_mm; a.tol = tol_mm;
   hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(sdf_scene_kernel, dim3((unsigned int)(a.tiles * num_frames)), dim3(256), 0, st, a);
+  const dim3 grid((unsigned int)(a.tiles * num_frames)), block(256);
+  if (with_parts) hipLaunchKernelGGL(sdf_scene_kernel<true>, grid, block, 0, st, a);
+  else hipLaunchKernelGGL(sdf_scene_kernel<false>, grid, block, 0, st, a);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail_hip(e, "sdf_scene_kernel");
   // frame minimum, indentation depth, contact ranges: the statements of tacex_indentation_depth (the row kernel's geometry here)
@@ -266,4 +284,32 @@ extern "C" int tacex_height_map_from_sdf_scene(const float* voxels_dev, int num_
   e = run_frame_outputs(hm_mm_dev, false, nullptr, frame_min_dev, indent_mm_dev, nullptr, nullptr, frame_rows_dev, num_frames, height, width,
                         0.f, 0.f, 0.f, gelpad_height_m, gelpad_to_camera_min_distance_m, st, &what);
   return e == hipSuccess ? 0 : fail_hip(e, what);
+}
+
+}  // namespace
+}  // namespace tacex
+
+extern "C" int tacex_height_map_from_sdf_scene(const float* voxels_dev, int num_voxels, const int32_t* volumes_i_dev, const float* volumes_f_dev,
+                                               int num_volumes, const int32_t* part_ids_dev, const float* part_pose_dev,
+                                               const int32_t* part_ops_dev, int num_slots, float pixmm, float near_clip_mm, float far_clip_mm,
+                                               int max_steps, float tol_mm, float gelpad_height_m, float gelpad_to_camera_min_distance_m,
+                                               float* hm_mm_dev, float* frame_min_dev, float* indent_mm_dev, int32_t* frame_rows_dev,
+                                               int num_frames, int height, int width, void* stream) {
+  return tacex::run_sdf_scene("tacex_height_map_from_sdf_scene", voxels_dev, num_voxels, volumes_i_dev, volumes_f_dev, num_volumes, part_ids_dev,
+                              part_pose_dev, part_ops_dev, num_slots, pixmm, near_clip_mm, far_clip_mm, max_steps, tol_mm, gelpad_height_m,
+                              gelpad_to_camera_min_distance_m, hm_mm_dev, frame_min_dev, indent_mm_dev, frame_rows_dev, nullptr, false,
+                              num_frames, height, width, stream);
+}
+
+extern "C" int tacex_height_map_from_sdf_scene_parts(const float* voxels_dev, int num_voxels, const int32_t* volumes_i_dev,
+                                                     const float* volumes_f_dev, int num_volumes, const int32_t* part_ids_dev,
+                                                     const float* part_pose_dev, const int32_t* part_ops_dev, int num_slots, float pixmm,
+                                                     float near_clip_mm, float far_clip_mm, int max_steps, float tol_mm, float gelpad_height_m,
+                                                     float gelpad_to_camera_min_distance_m, float* hm_mm_dev, float* frame_min_dev,
+                                                     float* indent_mm_dev, int32_t* frame_rows_dev, uint8_t* part_map_dev, int num_frames,
+                                                     int height, int width, void* stream) {
+  return tacex::run_sdf_scene("tacex_height_map_from_sdf_scene_parts", voxels_dev, num_voxels, volumes_i_dev, volumes_f_dev, num_volumes,
+                              part_ids_dev, part_pose_dev, part_ops_dev, num_slots, pixmm, near_clip_mm, far_clip_mm, max_steps, tol_mm,
+                              gelpad_height_m, gelpad_to_camera_min_distance_m, hm_mm_dev, frame_min_dev, indent_mm_dev, frame_rows_dev,
+                              part_map_dev, true, num_frames, height, width, stream);
 }

@@ -181,15 +181,20 @@ class GelSightSensor(SensorBase):
         left as it is."""
         return lens(self._tactile_rgb("lens_image"), out=out, camera=camera)
 
-    def contact_field(self, model, slip: torch.Tensor | None = None, image=False):
+    def contact_field(self, model, slip: torch.Tensor | None = None, image=False, parts=None):
         """The contact force field of the current `data.output["height_map"]`: `model` (a `TactileContactModel` of num_envs frames)
         evaluated in one launch on the current stream -> `ContactField` (net force and torque, centre of pressure, contact area, slip,
         per-cell forces, optionally the traction image).  The per-frame minimum, indentation depth and contact rectangles of the
         indentation-depth provider are reused when they describe this height map; otherwise one `tacex_indentation_depth` fills
         scratch buffers.  `slip` (num_envs, 5) [dx_mm, dy_mm, dtheta_rad, cx_px, cy_px]; None: `slip_from_fots` of a FOTS marker
-        simulator, no shear without one.  No output of the sensor is touched."""
+        simulator, no shear without one.  No output of the sensor is touched.
+        `parts`: an `SdfSceneSource` built with `part_map=True` (the sensor's height-map source) - the call is then
+        `model.parts` with the source's `part_map` and `num_slots` -> `PartContactField`, a record per env and slot; `slip` may be
+        (num_envs, K, 5), a row per slot (`sdf_scene.part_slip`), and a (num_envs, 5) table or `slip_from_fots` is repeated for every slot."""
         if self._group is not None:
             raise RuntimeError("contact_field is not available on a grouped sensor: call the TactileContactModel on the group's buffers")
+        if parts is not None and not getattr(parts, "with_part_map", False):
+            raise ValueError("contact_field: parts must be an SdfSceneSource built with part_map=True")
         hm = self.data.output["height_map"]  # (brings outdated buffers up to date)
         sim, v = self._fused_targets(), self._height_map_version
         rows = getattr(sim, "_frame_rows", None)
@@ -213,6 +218,14 @@ class GelSightSensor(SensorBase):
             from .contact_field import slip_from_fots
 
             slip = slip_from_fots(self.marker_motion_simulator)
+        if parts is not None:
+            labels, L = parts.part_map, parts.num_slots
+            if labels is None or tuple(labels.shape) != tuple(hm.shape):
+                raise RuntimeError(f"contact_field: parts.part_map does not describe the {tuple(hm.shape)} height map (no fill of this "
+                                   "source yet: is it the sensor's height-map source?)")
+            if slip is not None and slip.dim() == 2:  # one rigid motion per env: the same row for every part
+                slip = slip[:, None, :].expand(-1, L, -1).contiguous()
+            return model.parts(hm, fmin, indent, labels, L, slip=slip, frame_rows=rows, image=image)
         return model(hm, fmin, indent, slip=slip, frame_rows=rows, image=image)
 
     def _read_camera_depth(self):

@@ -36,7 +36,10 @@ class SdfSceneSource(_stage.LibrarySource):
     object -> camera, t [mm], scale, level_mm, blend_mm; initially identity beyond the far clip).  The scene's field is a left fold
     over the slots: a union adds a part, a subtraction cuts it out of what the earlier slots built, an intersection keeps what both
     hold; `blend_mm` > 0 rounds the seam with a polynomial smooth minimum of that width.  `local_pose` keeps what `set_pose` wrote,
-    for `set_group_pose`."""
+    for `set_group_pose`.  With `part_map=True` a fill also says which slot every pixel shows
+    (`tacex_height_map_from_sdf_scene_parts`): `part_map`, a (num_envs, H, W) uint8 tensor of slot indices, 255 where nothing was
+    hit - None before the first fill, allocated there and written in place afterwards; the height map and the other outputs keep
+    their bits."""
 
     _owner, _unit, _names = "SdfSceneSource", "voxel", ("voxels", "volumes_i", "volumes_f", "_row_ids")
     volumes_f = _stage.table_attr("rows")
@@ -44,7 +47,7 @@ class SdfSceneSource(_stage.LibrarySource):
     num_volumes = SdfVolumeSource.num_volumes
 
     def __init__(self, volumes, num_envs: int, device, num_slots: int = 2, pixmm: float = 0.0295, gel_top_mm: float = 28.5,
-                 near_clip_mm: float = 24.0, far_clip_mm: float = 29.0, max_steps: int = 32, tol_mm: float = 1e-4):
+                 near_clip_mm: float = 24.0, far_clip_mm: float = 29.0, max_steps: int = 32, tol_mm: float = 1e-4, part_map: bool = False):
         volumes = _stage.profile_list("SdfSceneSource", "volumes", volumes, SdfVolume)
         grids = [v.validate() for v in volumes]
         if not 1 <= int(num_slots) <= MAX_SLOTS:
@@ -61,6 +64,7 @@ class SdfSceneSource(_stage.LibrarySource):
         self.gel_top_mm, self.tol_mm = float(gel_top_mm), float(tol_mm)
         self.near_clip_mm, self.far_clip_mm = float(near_clip_mm), float(far_clip_mm)
         self._surface_points = None
+        self.with_part_map, self.part_map = bool(part_map), None
         B, K, dev = self.num_envs, self.num_slots, self.device
         self.part_ids = torch.full((B, K), -1, dtype=torch.int32, device=dev)
         self.part_ops = torch.zeros((B, K), dtype=torch.int32, device=dev)
@@ -145,10 +149,39 @@ class SdfSceneSource(_stage.LibrarySource):
 
     def _launch(self, voxels, volumes_i, volumes_f, ids, hm, frame_min, indent, rows, gelpad_height, gelpad_to_camera_min_distance):
         dev = self.device
-        with torch.cuda.device(dev):  # (two launches: the march, then the frame outputs of the map)
-            rc = self._lib.tacex_height_map_from_sdf_scene(
-                _lib.ptr(voxels), int(voxels.shape[0]), _lib.ptr(volumes_i), _lib.ptr(volumes_f), self.num_volumes, _lib.ptr(self.part_ids),
+        head = (_lib.ptr(voxels), int(voxels.shape[0]), _lib.ptr(volumes_i), _lib.ptr(volumes_f), self.num_volumes, _lib.ptr(self.part_ids),
                 _lib.ptr(self.part_pose), _lib.ptr(self.part_ops), self.num_slots, self.pixmm, self.near_clip_mm, self.far_clip_mm,
                 self.max_steps, self.tol_mm, gelpad_height, gelpad_to_camera_min_distance, _lib.ptr(hm), _lib.ptr(frame_min),
-                _lib.ptr(indent), _lib.ptr(rows), self.num_envs, int(hm.shape[1]), int(hm.shape[2]), _lib.current_stream_handle(dev))
-        _lib.check(rc, "tacex_height_map_from_sdf_scene")
+                _lib.ptr(indent), _lib.ptr(rows))
+        tail = (self.num_envs, int(hm.shape[1]), int(hm.shape[2]), _lib.current_stream_handle(dev))
+        name = "tacex_height_map_from_sdf_scene"
+        if self.with_part_map:
+            name += "_parts"
+            if self.part_map is None or self.part_map.shape != hm.shape:  # (the first fill; a fill at another resolution)
+                self.part_map = torch.empty(tuple(hm.shape), dtype=torch.uint8, device=dev)
+            _stage.check_tensor(self._owner, "part_map", self.part_map, tuple(hm.shape), torch.uint8, dev, must="must stay")
+            head += (_lib.ptr(self.part_map),)
+        with torch.cuda.device(dev):  # (two launches: the march, then the frame outputs of the map)
+            rc = getattr(self._lib, name)(*head, *tail)
+        _lib.check(rc, name)
+
+
+def part_slip(part_pose: torch.Tensor, reference_pose: torch.Tensor, pixmm: float) -> torch.Tensor:
+    """The (B, K, 5) slip table [dx_mm, dy_mm, dtheta_rad, cx_px, cy_px] of `TactileContactModel.parts` from two (B, K, 16) pose tensors
+    (`POSE_FIELDS`): per slot the in-plane translation of the part's origin since `reference_pose` [mm], the yaw of R R_ref^T about
+    the optical axis, atan2(M[1][0] - M[0][1], M[0][0] + M[1][1]) - the in-plane rotation nearest to M; a tilt alone turns nothing -,
+    and the origin's current pixel as the twist centre.  A task snapshots `SdfSceneSource.part_pose` at first contact
+    (`reference_pose = src.part_pose.clone()`) and calls this every step.  Torch ops on the poses' device, no host sync."""
+    for name, t in (("part_pose", part_pose), ("reference_pose", reference_pose)):
+        if not isinstance(t, torch.Tensor) or t.dim() != 3 or t.shape[2] != 16:
+            raise ValueError(f"part_slip: {name} must be a (B, K, 16) tensor")
+    if part_pose.shape != reference_pose.shape:
+        raise ValueError(f"part_slip: part_pose is {tuple(part_pose.shape)}, reference_pose {tuple(reference_pose.shape)}")
+    if not float(pixmm) > 0:
+        raise ValueError(f"part_slip: pixmm must be > 0, got {pixmm}")
+    p, q = part_pose.double(), reference_pose.to(part_pose.device).double()
+    # M = R R_ref^T: M[i][j] = sum_k R[i][k] R_ref[j][k] (rows 0 and 1 suffice)
+    m = lambda i, j: p[..., 3 * i] * q[..., 3 * j] + p[..., 3 * i + 1] * q[..., 3 * j + 1] + p[..., 3 * i + 2] * q[..., 3 * j + 2]  # noqa: E731
+    yaw = torch.atan2(m(1, 0) - m(0, 1), m(0, 0) + m(1, 1))
+    out = torch.stack((p[..., 9] - q[..., 9], p[..., 10] - q[..., 10], yaw, p[..., 9] / float(pixmm), p[..., 10] / float(pixmm)), dim=-1)
+    return out.float().contiguous()
