@@ -1247,6 +1247,64 @@ int tacex_contact_field_parts(const float* hm_mm_dev, const float* frame_min_dev
                               float pixmm, const int32_t* frame_rows_dev, double* record_dev, float* image_dev, int num_frames, int height,
                               int width, void* stream);
 
+/* Contact point cloud of the optical path: a fixed-size set of K = max_points surface points per env, sampled from the contact pixels
+ * of the height map, in ONE launch on `stream` (tacex_amd/csrc/contact_points.hip): a stream compaction, no atomics, no global
+ * scratch, no host synchronisation.  B = num_frames, any H, W >= 1 with H * W < 2^31.
+ * Inputs: hm_mm_dev (B,H,W) f32, frame_min_dev (B,) f32 and indent_mm_dev (B,) f32 exactly as for tacex_contact_field;
+ *   frame_rows_dev (B,4) int32, nullable: the contact rectangles [row lo, row hi, column lo, column hi] of THESE height maps, as in
+ *   tacex_contact_field.  Pixels are looked for inside the rectangle only (clamped to the image: it can skip pixels, never address
+ *   outside the frame); every output is bit-equal to the call without it, and a frame with an empty rectangle reads no pixel.  (The
+ *   gradient of a selected pixel taps its four neighbours wherever they lie.)
+ *   labels_dev (B,H,W) u8, nullable: a label per pixel, e.g. the part map of tacex_height_map_from_sdf_scene_parts;
+ *   label: -1 selects every label (255 too), 0..254 only the pixels whose label equals it; label >= 0 with a NULL labels_dev is refused;
+ *   pixmm > 0: pixel pitch [mm];  min_depth_mm >= 0;  max_points K in [1, 16384];  pad: 0 = zero fill, 1 = repeat;
+ *   pose_dev (B,12) f32, nullable: a row-major [R | t] per env (row r is R[r][0], R[r][1], R[r][2], t[r]);  unit f32 > 0: the length
+ *   unit of the points in mm^-1 (1e-3: metres);  jitter 0 / not 0, seed u64, frame_offset i64, call u32: below.
+ * Per pixel (row i, column j):
+ *     S = (hm - frame_min) - indent
+ *     d = S < 0 ? -S : 0                                 [mm]; a NaN gives 0
+ *   The pixel is a CONTACT PIXEL iff d > min_depth_mm and it passes the label filter.  With min_depth_mm == 0 and no labels this is
+ *   the pixel set of tacex_contact_field (its record slot [8] is N).
+ * Rank: the N contact pixels of a frame are ranked r = 0..N-1 in row-major order of the whole frame.
+ * Slots: with the offset o (0, or the jitter below), slot k of K takes
+ *     N > K:                     rank floor((k*N + o) / K) in 64-bit integer arithmetic - strictly increasing in k and below N; a pixel
+ *                                of rank r is therefore the source of slot k iff ceil((r*K - o)/N) <= k < ceil(((r+1)*K - o)/N), and
+ *                                that range holds at most one slot;
+ *     N <= K, pad == 0:          rank k for k < N; the slots beyond are invalid;
+ *     N <= K, pad == 1, N > 0:   rank k mod N;
+ *     N == 0:                    every slot is invalid.
+ * Jitter: w = philox4x32_10(ctr = {lo32(g), hi32(g), call, 0x70747363}, key = {lo32(seed), hi32(seed)})[0] (tacex_philox4x32) with
+ *   g = frame_offset + b as a 64-bit two's complement number, and o = (uint64(w) * N) >> 32, which is in [0, N).  Without jitter, or
+ *   when N <= K, o = 0.  A subsample then starts at another rank on every call, env and seed; the ranks stay evenly spaced.
+ * Point of a slot whose pixel is (i, j).  All arithmetic is float32, every operation rounded on its own (no fused multiply-add):
+ *     x = (float(j) - cx0) * pixmm,  y = (float(i) - cy0) * pixmm,  z = S,   with cx0 = float(W-1) / 2, cy0 = float(H-1) / 2 [mm]
+ *   - the camera frame of tacex_contact_field: origin on the pad face at the image centre, x = columns, y = rows, z along the
+ *   optical axis, so z is negative under an indenter.
+ *   Gradient: jl = max(j-1, 0), jr = min(j+1, W-1), gx = (hm[i,jr] - hm[i,jl]) / (float(jr - jl) * pixmm), gx = 0 when W == 1;
+ *     gy likewise along i (gy = 0 when H == 1).  Neighbours need not be in contact.
+ *   Normal: s = sqrtf((gx*gx + gy*gy) + 1),  n = (gx / s, gy / s, -1 / s): the indenter surface's normal pointing into the gel.
+ *   With pose_dev:    q = (unit*x, unit*y, unit*z),  p'[r] = ((R[r][0]*q[0] + R[r][1]*q[1]) + R[r][2]*q[2]) + t[r],
+ *                     n'[r] = (R[r][0]*n[0] + R[r][1]*n[1]) + R[r][2]*n[2]   (not renormalised);
+ *   without:          p' = (unit*x, unit*y, unit*z),  n' = n.
+ *   The penetration is reported as d [mm], untransformed.
+ * Outputs: points_dev (B,K,3) f32, required; each of the following nullable: normals_dev (B,K,3) f32, depth_dev (B,K) f32,
+ *   pixels_dev (B,K,2) int32 [row, col], labels_out_dev (B,K) u8 (the pixel's label; 0 when labels_dev is NULL),
+ *   count_dev (B,2) int32 [N, V], V the number of valid slots: 0 for N = 0, K for N >= K or pad == 1, N otherwise.
+ *   Invalid slots: points, normals and depth 0, pixels -1, labels 255.  Every slot of every given output is written.
+ * An env's outputs depend on its own inputs and g alone, not on the batch it is launched in; the same input gives the same bits.
+ * One workgroup handles one frame and keeps K pixel indices in LDS (4 K bytes).  16-byte row loads are used when W % 4 == 0,
+ * hm_mm_dev is 16-byte aligned (and labels_dev, where the filter reads it, 4-byte aligned); the same bits otherwise.
+ * Returns 2 before any HIP call for a NULL hm_mm_dev, frame_min_dev, indent_mm_dev or points_dev, num_frames, height or width <= 0,
+ * height * width >= 2^31, pixmm or unit <= 0 (or NaN), min_depth_mm < 0 (or NaN), max_points outside [1, 16384], pad other than 0 or
+ * 1, label outside [-1, 254], and label >= 0 with a NULL labels_dev; 2 as well when 4 K bytes exceed the LDS a workgroup can get on
+ * the device.  Added without a change of TACEX_ABI_VERSION: a caller detects it by looking the symbol up. */
+#define TACEX_CONTACT_POINTS_MAX 16384
+int tacex_contact_points(const float* hm_mm_dev, const float* frame_min_dev, const float* indent_mm_dev, const int32_t* frame_rows_dev,
+                         const uint8_t* labels_dev, int label, float pixmm, float min_depth_mm, int max_points, int pad,
+                         const float* pose_dev, float unit, int jitter, uint64_t seed, int64_t frame_offset, uint32_t call,
+                         float* points_dev, float* normals_dev, float* depth_dev, int32_t* pixels_dev, uint8_t* labels_out_dev,
+                         int32_t* count_dev, int num_frames, int height, int width, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

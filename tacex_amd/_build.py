@@ -17,7 +17,7 @@ _TAG = os.environ.get("TACEX_LIB_TAG", "")
 LIB = PKG / (f"libtacex_hip.{_TAG}.so" if _TAG else "libtacex_hip.so")
 STAMP = PKG / (LIB.name + ".stamp")
 _FLAGS_FILE = PKG / f"libtacex_hip.{_TAG}.flags"
-SOURCES = ["taxim_kernels.hip", "taxim_mfma.hip", "taxim_tail.hip", "taxim_stream.hip", "taxim_shadow.hip", "fots_kernels.hip", "fem_kernels.hip", "depth_raster.hip", "camera_model.hip", "lens_model.hip", "contact_field.hip", "contact_parts.hip", "gel_memory.hip", "relief_source.hip", "volume_source.hip", "sdf_scene.hip", "tacex_capi.hip"]
+SOURCES = ["taxim_kernels.hip", "taxim_mfma.hip", "taxim_tail.hip", "taxim_stream.hip", "taxim_shadow.hip", "fots_kernels.hip", "fem_kernels.hip", "depth_raster.hip", "camera_model.hip", "lens_model.hip", "contact_field.hip", "contact_parts.hip", "contact_points.hip", "gel_memory.hip", "relief_source.hip", "volume_source.hip", "sdf_scene.hip", "tacex_capi.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=fast", "-Wno-unused-result"]
 # A/B hook for kernel tuning macros, e.g. TACEX_EXTRA_HIPCC_FLAGS="-DTACEX_MFMA_CH=2" (part of the build digest)
 _STREAM_DEFAULT = "-mllvm -amdgpu-sched-strategy=max-memory-clause"
@@ -45,6 +45,8 @@ FILE_FLAGS = {"taxim_stream.hip": ["-fno-slp-vectorize"] + _stream_flags.split()
               "contact_field.hip": ["-ffp-contract=off"],
               # per-part contact records: the same terms (contact_terms.h), restated in tests/contact_parts_ref.py
               "contact_parts.hip": ["-ffp-contract=off"],
+              # the contact point cloud: the float32 operations of a point are restated in tests/contact_points_ref.py
+              "contact_points.hip": ["-ffp-contract=off"],
               # the gel memory: a * m + c * d is two products and a sum, as tests/gel_memory_ref.py restates it
               "gel_memory.hip": ["-ffp-contract=off"],
               # the relief source: every product and sum of its per-sample contract on its own, as tests/relief_source_ref.py restates it

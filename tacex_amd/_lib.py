@@ -190,6 +190,8 @@ SIGNATURES = {
     "tacex_height_map_from_sdf_scene_parts": (_i, [_vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _i, _f, _f, _f, _i, _f, _f, _f, _vp, _vp, _vp, _vp, _vp, _i,
                                                    _i, _i, _vp]),
     "tacex_contact_field_parts": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _f, _vp, _vp, _vp, _i, _i, _i, _vp]),
+    "tacex_contact_points": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _f, _f, _i, _i, _vp, _f, _i, C.c_uint64, C.c_int64, C.c_uint32, _vp, _vp, _vp, _vp,
+                                  _vp, _vp, _i, _i, _i, _vp]),
 }
 
 _lib = None

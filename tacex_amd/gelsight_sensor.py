@@ -195,6 +195,44 @@ class GelSightSensor(SensorBase):
             raise RuntimeError("contact_field is not available on a grouped sensor: call the TactileContactModel on the group's buffers")
         if parts is not None and not getattr(parts, "with_part_map", False):
             raise ValueError("contact_field: parts must be an SdfSceneSource built with part_map=True")
+        hm, fmin, indent, rows = self._contact_frame_scalars()
+        if slip is None and hasattr(self.marker_motion_simulator, "_traj_state"):
+            from .contact_field import slip_from_fots
+
+            slip = slip_from_fots(self.marker_motion_simulator)
+        if parts is not None:
+            labels, L = self._part_labels("contact_field", parts, hm), parts.num_slots
+            if slip is not None and slip.dim() == 2:  # one rigid motion per env: the same row for every part
+                slip = slip[:, None, :].expand(-1, L, -1).contiguous()
+            return model.parts(hm, fmin, indent, labels, L, slip=slip, frame_rows=rows, image=image)
+        return model(hm, fmin, indent, slip=slip, frame_rows=rows, image=image)
+
+    def contact_points(self, model, parts=None, label: int = -1):
+        """The contact point cloud of the current `data.output["height_map"]`: `model` (a `TactileContactPoints` of num_envs frames)
+        evaluated in one launch on the current stream -> `ContactPoints` (points, normals, penetration, pixel and label per slot, the
+        counts).  The per-frame minimum, indentation depth and contact rectangles are chosen as in `contact_field`.  No output of the
+        sensor is touched.
+        `parts`: an `SdfSceneSource` built with `part_map=True` (the sensor's height-map source) - its `part_map` labels the pixels:
+        every slot then reports its part, and `label` >= 0 keeps the pixels of that part alone."""
+        if self._group is not None:
+            raise RuntimeError("contact_points is not available on a grouped sensor: call the TactileContactPoints on the group's buffers")
+        if parts is not None and not getattr(parts, "with_part_map", False):
+            raise ValueError("contact_points: parts must be an SdfSceneSource built with part_map=True")
+        hm, fmin, indent, rows = self._contact_frame_scalars()
+        labels = None if parts is None else self._part_labels("contact_points", parts, hm)
+        return model(hm, fmin, indent, frame_rows=rows, labels=labels, label=label)
+
+    @staticmethod
+    def _part_labels(what: str, parts, hm: torch.Tensor) -> torch.Tensor:
+        labels = parts.part_map
+        if labels is None or tuple(labels.shape) != tuple(hm.shape):
+            raise RuntimeError(f"{what}: parts.part_map does not describe the {tuple(hm.shape)} height map (no fill of this "
+                               "source yet: is it the sensor's height-map source?)")
+        return labels
+
+    def _contact_frame_scalars(self):
+        """(height map, frame_min, indent, frame_rows) for a contact stage (`contact_field`, `contact_points`): the indentation-depth
+        provider's values when they describe the current height map, otherwise one `tacex_indentation_depth` into scratch buffers."""
         hm = self.data.output["height_map"]  # (brings outdated buffers up to date)
         sim, v = self._fused_targets(), self._height_map_version
         rows = getattr(sim, "_frame_rows", None)
@@ -214,19 +252,7 @@ class GelSightSensor(SensorBase):
                     _lib.ptr(hm), float(getattr(cfg, "gelpad_height", 0.0)), float(getattr(cfg, "gelpad_to_camera_min_distance", 0.0)),
                     _lib.ptr(fmin), _lib.ptr(indent), _lib.ptr(rows), B, H, W, _lib.current_stream_handle(hm.device))
             _lib.check(rc, "tacex_indentation_depth")
-        if slip is None and hasattr(self.marker_motion_simulator, "_traj_state"):
-            from .contact_field import slip_from_fots
-
-            slip = slip_from_fots(self.marker_motion_simulator)
-        if parts is not None:
-            labels, L = parts.part_map, parts.num_slots
-            if labels is None or tuple(labels.shape) != tuple(hm.shape):
-                raise RuntimeError(f"contact_field: parts.part_map does not describe the {tuple(hm.shape)} height map (no fill of this "
-                                   "source yet: is it the sensor's height-map source?)")
-            if slip is not None and slip.dim() == 2:  # one rigid motion per env: the same row for every part
-                slip = slip[:, None, :].expand(-1, L, -1).contiguous()
-            return model.parts(hm, fmin, indent, labels, L, slip=slip, frame_rows=rows, image=image)
-        return model(hm, fmin, indent, slip=slip, frame_rows=rows, image=image)
+        return hm, fmin, indent, rows
 
     def _read_camera_depth(self):
         src = self.cfg.sensor_camera_cfg.depth_source if self.cfg.sensor_camera_cfg is not None else None
